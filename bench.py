@@ -5,9 +5,11 @@ Contract (see the task description): ``python bench.py --gpus N --steps K --warm
 it under ``python -m torch.distributed.run`` (one rank per GPU, RCCL).  A *step* is one full attack of one batch:
 BASELINE.json configs[1] -- VLMO-base white box (random-init, frozen, fp32), batch 64, 40 PGD steps, 384x384 images,
 40-token questions, eps 0.125 / step 0.01 / clip [-1, 1] (the reference's literals) -- followed by black-box scoring and,
-for N > 1, the RCCL all-gather of attack-success bits.  Inputs are synthetic and resident in HBM before the timed
+for N > 1, the RCCL all-gather of attack-success bits.  Inputs are synthetic, seeded and resident in HBM before the timed
 region.  Rank 0 prints ONE JSON line with the aggregate examples/sec over all ranks (weak scaling: every rank attacks
-its own batch of 64), plus
+its own batch of 64) and ``ms_per_step``, the wall-clock milliseconds of one timed step.  A plain run does only that:
+set up, warm up, time the steps (``--dump-outputs DIR``: then write what the last timed step returned as
+``DIR/<name>.npy``), print the line.  ``--full`` adds the auxiliary measurements:
 
   * ``roofline``: the fused sign+clamp+project kernel (``vqa_linf_step``), timed live with HIP events on the launch
     stream inside the timed region; achieved = 16 B/element x elements per launch / mean launch duration, against the
@@ -74,20 +76,36 @@ def parse():
     ap.add_argument("--dense-mlm", action="store_true",
                     help="with --dual: MLM head and cross entropy over all B x L positions (the reference's dense "
                          "closure) instead of the live label rows only -- the 'before' of profiles/r03")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the auxiliary measurements: per-launch kernel timing inside the timed region "
+                         "(roofline, roofline_loss), the platform stream probe and the batch-256 step microbench "
+                         "(platform_stream_probe, roofline_b256), the attention microbench (roofline_attention), the "
+                         "reference-style batch-1 leg and the CPU baseline.  Without it a run sets up, warms up, times "
+                         "its steps and prints the headline figures only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / "
+                         "float64, < 64 MB in all): a fixed seeded sample of the adversarial images, per-sample float64 "
+                         "sums of all of them, the adversarial token ids, the loss trajectory, the black-box answers and "
+                         "the success bits (rank 0's batch)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline-steps", type=int, default=40,
                     help="PGD steps of the CPU sample (default: one full 40-step example, ~10-15 s on 16 cores)")
-    ap.add_argument("--no-b256", action="store_true")
+    ap.add_argument("--no-b256", action="store_true",
+                    help="with --full: skip the stream probe and the batch-256 step microbench")
     ap.add_argument("--no-reference-style", action="store_true",
-                    help="skip the batch-1 leg that drives the drop-in with the reference's own packed closure")
+                    help="with --full: skip the batch-1 leg that drives the drop-in with the reference's own packed closure")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch plumbing only, runs without a GPU: the ranks rendezvous over gloo on the host, gather "
                          "stand-in success bits and rank 0 prints a line whose value is null (no measurement)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.sweep or args.dry_run):
+        ap.error("--dump-outputs writes the outputs of the fixed-batch attack: not with --sweep or --dry-run")
     if args.steps is None:
         args.steps = 1 if args.sweep else 2
     if args.warmup is None:
         args.warmup = 1
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     return args
 
 
@@ -365,6 +383,32 @@ def synthetic_questions(batch, length, seed, device, min_words=4, max_words=12):
         ids[s, 1:1 + k] = body[s, :k]
         ids[s, 1 + k] = 102
     return ids.to(device), (ids != 0).long().to(device), n.tolist()
+
+
+def synthetic_inputs(args, image_size, text_len, device, rank):
+    """One rank's inputs, seeded by the rank alone and so identical from run to run: images U(-1, 1), questions and the
+    mask of substitutable words.  The attack's random start comes from torch's default generators, whose state a fresh
+    process does not fix: ``seed_step`` sets it before every step.  Returns (images, ids, masks, words per question,
+    substitutable-word mask)."""
+    gen = torch.Generator(device=device).manual_seed(1234 + rank)
+    images = torch.empty(args.batch, 3, image_size, image_size, device=device).uniform_(-1, 1, generator=gen)
+    # questions of n ~ U{4..12} words (SURVEY.md section 8d); a joint attack needs its --joint substitutable words
+    ids, masks, n_words = synthetic_questions(args.batch, text_len, seed=100 + rank, device=device,
+                                              min_words=max(4, args.joint), max_words=max(12, args.joint))
+    words = torch.zeros_like(ids, dtype=torch.bool)              # configs[1]: image-only 40-step PGD
+    if args.joint:
+        words[:, 1:1 + min(args.joint, text_len - 2)] = True     # configs[4]: joint image + text attack
+    return images, ids, masks, n_words, words
+
+
+STEP_SEED = 4321
+
+
+def seed_step(rank):
+    """Seed torch's default generators (host and every device) before a step: the random start of the PGD loop (and
+    ALBEF's per-forward token masking) draws from them, so every step of every run with the same arguments starts from
+    the same point.  Host-side only: sets a seed and an offset, launches nothing."""
+    torch.manual_seed(STEP_SEED + rank)
 
 
 def make_config(args):
@@ -807,6 +851,46 @@ def cpu_baseline(args, cfg):
                            "" if steps == args.pgd_steps else ", extrapolated to {} steps".format(args.pgd_steps)))
 
 
+DUMP_IMAGE_BYTES = 32 << 20    # the adversarial-image sample of --dump-outputs; every other output is a few KB
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, res, adv_answers, success):
+    """--dump-outputs: what one step returned to its caller (the attack's BatchResult, the black box's answers on the
+    adversarial pair and the success bits), as ``out_dir/<name>.npy`` in float32 / float64.  The adversarial images (113 MB
+    at batch 64 and 384 px) go out as a fixed seeded sample of whole samples (<= 32 MB, ``adv_images_sample`` with its
+    batch indices) plus float64 sums over every sample; everything else is written whole."""
+    import numpy as np
+
+    def flat(x):                                    # loss trajectory: lists (per block) of floats or tensors
+        if torch.is_tensor(x):
+            return x.detach().double().cpu().reshape(-1).numpy()
+        if isinstance(x, (list, tuple)):
+            return np.concatenate([flat(v) for v in x]) if x else np.zeros(0)
+        return np.asarray([x], dtype=np.float64)
+
+    adv = res.adv_images.detach()
+    b = adv.shape[0]
+    keep = max(1, min(b, 16, DUMP_IMAGE_BYTES // (adv[0].numel() * 4)))
+    index = torch.randperm(b, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+    out = {"adv_images_sample": adv[index.to(adv.device)].float().cpu().numpy(),
+           "adv_images_sample_index": index.double().numpy(),
+           "adv_images_sum_per_sample": adv.reshape(b, -1).sum(dim=1, dtype=torch.float64).cpu().numpy(),
+           "adv_text_ids": res.adv_text_ids.double().cpu().numpy(),
+           "loss": flat(res.loss_lists),
+           "adv_answers": adv_answers.double().cpu().numpy(),
+           "success": success.double().cpu().numpy()}
+    if res.adv_text_ids_mlm is not None:
+        out["adv_text_ids_mlm"] = res.adv_text_ids_mlm.double().cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: {} bytes exceed the {} byte limit".format(total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("outputs of the last timed step: {} arrays, {:.1f} MB in {}".format(len(out), total / 1e6, out_dir))
+
+
 def main():
     args = parse()
     if args.gpus < 1:
@@ -977,15 +1061,8 @@ def main():
 
     ledger = SuccessLedger(world, rank, coll_device, force_collective=use_dist)
 
-    gen = torch.Generator(device=device).manual_seed(1234 + rank)
-    images = torch.empty(args.batch, 3, cfg.image_size, cfg.image_size, device=device).uniform_(-1, 1, generator=gen)
-    # questions of n ~ U{4..12} words; a joint attack needs its --joint substitutable words
-    ids, masks, n_words = synthetic_questions(args.batch, text_len, seed=100 + rank, device=device,
-                                              min_words=max(4, args.joint), max_words=max(12, args.joint))
+    images, ids, masks, n_words, words = synthetic_inputs(args, cfg.image_size, text_len, device, rank)
     n_body = max(n_words)
-    words = torch.zeros_like(ids, dtype=torch.bool)              # configs[1]: image-only 40-step PGD
-    if args.joint:
-        words[:, 1:1 + min(args.joint, text_len - 2)] = True     # configs[4]: joint image + text attack
     clean_answers = black.vqa_answer(images, ids, masks)
     tasks = None
     if args.dual:           # every sample's victim answer occurs in its paraphrase -> old_alg == 0 (adv_attack.py:455-469)
@@ -994,36 +1071,41 @@ def main():
         assert all(t.old_alg == 0 for t in tasks)
 
     def one_step():
+        seed_step(rank)
         if tasks is not None:
             res = attack.attack_batch(images, ids, masks, words, dual=True, tasks=tasks)
         else:
             res = attack.attack_batch(images, ids, masks, words)
         adv_answers = black.vqa_answer(res.adv_images, res.adv_text_ids, masks)
-        ledger.record(adv_answers != clean_answers)     # sample ids default to this rank's interleaved shard
-        return res
+        success = adv_answers != clean_answers
+        ledger.record(success)                          # sample ids default to this rank's interleaved shard
+        return res, adv_answers, success
 
     for i in range(args.warmup):
         one_step()
         torch.cuda.synchronize()
         log("warmup step {} done".format(i))
     ledger.reset()
-    timer = KernelTimer()
-    timer.install()
+    timer = KernelTimer() if args.full else None       # per-launch hip events: --full only
+    if timer:
+        timer.install()
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_step()
+        last = one_step()
     asr = ledger.all_gather_rate(world * args.batch * args.steps)   # RCCL all-gather of the success bits (N > 1); inside the timed region
     fence()
     dt = time.perf_counter() - t0
-    timer.remove()
+    if timer:
+        timer.remove()
     if use_dist:
         t = torch.tensor([dt], device=coll_device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    roof, roof_loss = timer.summary()
     if rank == 0:
         log("timed region: {} steps in {:.2f} s".format(args.steps, dt))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, *last)
 
     if rank == 0:
         total = world * args.batch * args.steps
@@ -1056,12 +1138,13 @@ def main():
             "collective": ({"backend": dist.get_backend(), "world": dist.get_world_size(),
                             "tensor_device": str(coll_device), "calls": ledger.collectives}
                            if use_dist else None),
-            "roofline": roof,
-            "roofline_loss": roof_loss,
         }
-        # auxiliary legs: whatever goes wrong in one of them (absent or stale probe library, out of memory on a shared
-        # box, ...) is reported inside the line -- never allowed to suppress the metric line or to strand the other ranks
-        if not args.no_b256:
+        if args.full:
+            line["roofline"], line["roofline_loss"] = timer.summary()
+        # auxiliary legs (--full): whatever goes wrong in one of them (absent or stale probe library, out of memory on a
+        # shared box, ...) is reported inside the line -- never allowed to suppress the metric line or to strand the other
+        # ranks
+        if args.full and not args.no_b256:
             try:
                 line["platform_stream_probe"] = stream_probe()
             except Exception as exc:
@@ -1070,18 +1153,18 @@ def main():
                 line["roofline_b256"] = step_kernel_microbench(256, cfg.image_size)
             except Exception as exc:
                 line["roofline_b256"] = {"error": "{}: {}".format(type(exc).__name__, str(exc)[:200])}
-        if cfg.dim // cfg.heads == 64:                # the white box's attention runs on csrc/attn.hip
+        if args.full and cfg.dim // cfg.heads == 64:  # the white box's attention runs on csrc/attn.hip
             seq = (n_body + 2 if flavor == "vlmo" else 0) + cfg.n_image_tokens
             try:
                 line["roofline_attention"] = attention_microbench(args.batch, cfg.heads, seq, flavor == "vlmo")
             except Exception as exc:
                 line["roofline_attention"] = {"error": "{}: {}".format(type(exc).__name__, str(exc)[:200])}
-        if not args.no_reference_style and args.model.endswith("_base"):
+        if args.full and not args.no_reference_style and args.model.endswith("_base"):
             try:
                 line["reference_style"] = reference_style_leg(flavor, white, cfg, text_len, args.pgd_steps)
             except Exception as exc:
                 line["reference_style"] = {"error": "{}: {}".format(type(exc).__name__, str(exc)[:200])}
-        if world == 1 and not args.no_cpu_baseline and flavor == "vlmo":
+        if args.full and world == 1 and not args.no_cpu_baseline and flavor == "vlmo":
             try:
                 line["cpu_baseline"] = cpu_baseline(args, cfg)
             except Exception as exc:

@@ -42,7 +42,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
     ctx = multiprocessing.get_context("forkserver")
     world, batch, steps = 2, 4, 2
     argv = ["--gpus", "2", "--steps", str(steps), "--warmup", "1", "--model", "vlmo_tiny", "--batch", str(batch),
-            "--pgd-steps", "6", "--no-cpu-baseline", "--no-b256"]
+            "--pgd-steps", "6", "--full", "--no-cpu-baseline", "--no-b256"]
     port = _free_port()
     outs = [str(tmp_path / "rank{}.out".format(r)) for r in range(world)]
     procs = [ctx.Process(target=_bench_rank, args=(r, world, port, outs[r], argv)) for r in range(world)]

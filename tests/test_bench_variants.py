@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 def test_bench_variant_prints_one_wellformed_line(argv, capsys, monkeypatch):
     import bench
     monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "1", "--warmup", "1", "--batch", "4", "--pgd-steps", "8",
-                                      "--no-cpu-baseline", "--no-b256"] + argv)
+                                      "--full", "--no-cpu-baseline", "--no-b256"] + argv)
     for k in ("RANK", "WORLD_SIZE", "MASTER_ADDR"):
         monkeypatch.delenv(k, raising=False)
     bench.main()

@@ -132,7 +132,8 @@ def test_bench_runs_the_two_configurations_at_full_batch(argv, model, capsys, mo
     """``python bench.py --model albef_base --batch 256`` / ``--model vlmo_large --joint 8 --batch 128`` with a short PGD
     budget (the full 40 steps take minutes): one well-formed line, the step kernel timed at the full batch."""
     import bench
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-b256"] + argv)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline",
+                                      "--no-b256"] + argv)
     for k in ("RANK", "WORLD_SIZE", "MASTER_ADDR", "LOCAL_RANK"):
         monkeypatch.delenv(k, raising=False)
     bench.main()

@@ -15,7 +15,7 @@ tune() {   # tag, bench args...
   [ -n "$RESUME" ] && cp "$RESUME" "$out/raw_${tag}0.csv"
   PYTORCH_TUNABLEOP_ENABLED=1 PYTORCH_TUNABLEOP_TUNING=1 PYTORCH_TUNABLEOP_FILENAME="$out/raw_${tag}.csv" \
     PYTORCH_TUNABLEOP_VERBOSE=0 PYTORCH_TUNABLEOP_MAX_TUNING_DURATION_MS=40 VQA_TUNED_GEMMS=off \
-    python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-b256 "$@" > "$out/tuning_${tag}.json" 2> "$out/tuning_${tag}.err"
+    python3 bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-b256 "$@" > "$out/tuning_${tag}.json" 2> "$out/tuning_${tag}.err"
   ls "$out"/raw_${tag}*.csv
 }
 tune_batch1() {
