@@ -370,6 +370,20 @@ int vqa_ln_bwd(const float* dy0, const float* dy1, const float* x, const float* 
 int vqa_gelu_fwd(const float* h, float* a, size_t n, vqa_stream_t stream);
 int vqa_gelu_bwd(const float* h, const float* da, float* dh, size_t n, vqa_stream_t stream);
 
+/* ---------------------------------------------------------------- encoder GEMMs on the bf16 matrix pipe (csrc/gemm.hip)
+ * C[M, N] = A[M, K] . B (+ bias[N])  with A fp32 (row stride lda, lda % 4 == 0, 16-byte aligned), C fp32 (row stride
+ * ldc) and B a frozen weight packed once into three bf16 planes (b = b0 + b1 + b2, exact): the six products a0b0, a0b1,
+ * a1b0, a0b2, a1b1, a2b0 run on v_mfma_f32_16x16x32_bf16 with A split the same way on the fly ("bf16x6"); error at or
+ * below the fp32 GEMM's.  N % 128 == 0, K % 32 == 0, any M >= 0.  Deterministic (fixed order, no atomics).
+ * vqa_gemm_packed_bytes: bytes of a packed [K, N] operand (0 = unsupported shape).
+ * vqa_gemm_pack_b: packed <- B[k][n] = trans ? w[n * ldw + k] : w[k * ldw + n]  -- trans = 1 packs the forward operand
+ *   W^T of a Linear weight W [out, in] (K = in, N = out), trans = 0 the input-gradient operand W (K = out, N = in).
+ *   Layout: bf16 [K/32][N/16][plane 3][lane 64][8], element (k, n) at lane (n % 16) + 16 * ((k % 32) / 8), slot k % 8. */
+size_t vqa_gemm_packed_bytes(int K, int N);
+int vqa_gemm_pack_b(const float* w, long ldw, int trans, void* packed, int K, int N, vqa_stream_t stream);
+int vqa_gemm_bf16x6(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M, int N,
+                    int K, vqa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,9 @@ SIGNATURES = {
     "vqa_gelu_bwd": (_i, [_p, _p, _p, _sz, _p]),
     "vqa_resize_bicubic_h_u8": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _p, _p]),
     "vqa_resize_bicubic_v_normalize": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _f, _f, _p, _p]),
+    "vqa_gemm_packed_bytes": (_sz, [_i, _i]),
+    "vqa_gemm_pack_b": (_i, [_p, _l, _i, _p, _i, _i, _p]),
+    "vqa_gemm_bf16x6": (_i, [_p, _l, _p, _p, _p, _l, _l, _i, _i, _p]),
 }
 
 _lib = None

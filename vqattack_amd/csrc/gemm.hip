@@ -1,0 +1,241 @@
+// fp32 GEMM of the frozen encoders' projections on the bf16 matrix pipe (gfx950 / MI355X):  C = A . B (+ bias)  with A
+// fp32 [M, K] (row stride lda), B a frozen weight pre-packed into three bf16 planes, C fp32 [M, N] (row stride ldc).
+//
+// Why: gfx950 has no xf32 MFMA and its f32-input MFMA runs at 1/16 of the bf16 rate.  An fp32 value splits exactly into
+// three bf16 pieces  a = a0 + a1 + a2  (a0 = bf16(a), a1 = bf16(a - a0), a2 = bf16(a - a0 - a1), both subtractions exact
+// in fp32), and the six products that carry fp32's precision -- a0b0, a0b1, a1b0, a0b2, a1b1, a2b0 ("bf16x6") -- cost
+// 6/16 of one fp32 MFMA.  The dropped terms a1b2 + a2b1 + a2b2 are <= ~2^-26 |ab| together, below the half-ulp fp32
+// rounds every product to.  Non-finite a (or an a0 that rounds to inf): a1 = a2 = 0, so inf / NaN propagate as in fp32.
+//
+// B (the weight) is split ONCE by vqa_gemm_pack_b into the kernel's fragment order; only A is split on the fly, once per
+// workgroup and k-step, into three LDS planes that every wave then reads as MFMA fragments.
+//
+// Tile: 256 x 128 outputs per workgroup of 8 waves (4 along M x 2 along N, 64 x 64 each = 4 x 4 tiles of
+// v_mfma_f32_16x16x32_bf16), BK = 32.  LDS per k-step: A 16 m-tiles x 3 planes x 1 KiB + B 8 n-tiles x 3 planes x 1 KiB
+// = 72 KiB, double-buffered = 144 KiB (one workgroup per CU, 2 waves per SIMD).  Every LDS image is "fragment order":
+// 1 KiB per (tile, plane), lane l's 16 bytes at l * 16, so every ds_read_b128 / ds_write_b128 of a wave is one linear,
+// conflict-free KiB.  Per k-step a wave issues 24 fragment reads and 96 MFMAs.  The k-loop is: issue the global loads of
+// step k+1 into registers, run the MFMAs of step k, split + write step k+1 into the other buffer, one barrier.
+//
+// Packed B ("vqa_gemm_pack_b"): bf16 [K/32][N/16][3 planes][64 lanes][8]; element (k, n) sits in plane tile
+// (k / 32, n / 16) at lane (n % 16) + 16 * ((k % 32) / 8), slot k % 8 -- the B-operand map of the 16x16x32 MFMA.  The
+// 8 n-tiles x 3 planes a workgroup stages per k-step are therefore one contiguous 24 KiB run.
+//
+// Deterministic: fixed summation order (per k-step the products a2b0, a1b1, a0b2, a1b0, a0b1, a0b0 in turn, k-steps in
+// order), no split-K, no atomics.  Rows >= M are read clamped to row M-1 and never stored.
+#include "common.hpp"
+
+namespace vqa {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+constexpr int kGemmBM = 256, kGemmBN = 128, kGemmBK = 32;
+constexpr int kGemmThreads = 512;
+constexpr int kGemmMT = kGemmBM / 16, kGemmNT = kGemmBN / 16;        // 16 m-tiles, 8 n-tiles per workgroup
+constexpr int kTileBytes = 64 * 16;                                    // one (tile, plane) fragment image: 1 KiB
+constexpr int kGemmABytes = kGemmMT * 3 * kTileBytes;                  // 48 KiB
+constexpr int kGemmBBytes = kGemmNT * 3 * kTileBytes;                  // 24 KiB
+constexpr int kGemmStage = kGemmABytes + kGemmBBytes;                  // 72 KiB
+constexpr int kGemmBPieces = kGemmBBytes / 16 / kGemmThreads;          // 3 x 16 B of B per thread and k-step
+
+// a -> (a0, a1, a2), exact for finite a whose bf16 rounding is finite.  Plain RNE casts (v_cvt_pk_bf16_f32).
+__device__ __forceinline__ void split2(f32x2 a, bf16x2& h0, bf16x2& h1, bf16x2& h2) {
+  h0 = __builtin_convertvector(a, bf16x2);
+  f32x2 r = a - __builtin_convertvector(h0, f32x2);
+  // a0 = +-inf / NaN (a non-finite, or |a| at the top of the range rounding up): no correction terms
+  r.x = __builtin_isfinite(r.x) ? r.x : 0.0f;
+  r.y = __builtin_isfinite(r.y) ? r.y : 0.0f;
+  h1 = __builtin_convertvector(r, bf16x2);
+  h2 = __builtin_convertvector(r - __builtin_convertvector(h1, f32x2), bf16x2);
+}
+
+__device__ __forceinline__ void split8(const f32x4& lo, const f32x4& hi, bf16x8& p0, bf16x8& p1, bf16x8& p2) {
+  bf16x2 a[4], b[4], c[4];
+  split2(f32x2{lo.x, lo.y}, a[0], b[0], c[0]);
+  split2(f32x2{lo.z, lo.w}, a[1], b[1], c[1]);
+  split2(f32x2{hi.x, hi.y}, a[2], b[2], c[2]);
+  split2(f32x2{hi.z, hi.w}, a[3], b[3], c[3]);
+  p0 = bf16x8{a[0].x, a[0].y, a[1].x, a[1].y, a[2].x, a[2].y, a[3].x, a[3].y};
+  p1 = bf16x8{b[0].x, b[0].y, b[1].x, b[1].y, b[2].x, b[2].y, b[3].x, b[3].y};
+  p2 = bf16x8{c[0].x, c[0].y, c[1].x, c[1].y, c[2].x, c[2].y, c[3].x, c[3].y};
+}
+
+struct GemmArgs {
+  const float* A;
+  const bf16x8* B;     // packed planes
+  const float* bias;   // nullable
+  float* C;
+  long lda, ldc, M;
+  int N, K;
+};
+
+__global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_kernel(GemmArgs g) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * kGemmStage];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;                 // this wave's 64 x 64 output block
+  const int ntb = g.N / kGemmBN;
+  const int mtb = static_cast<int>((g.M + kGemmBM - 1) / kGemmBM);
+  // XCD remap (bijective for any grid): consecutive tiles -- the same A row band -- share an XCD's L2
+  const int nwg = mtb * ntb, orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, rem = nwg & 7;
+  const int wg = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (orig >> 3);
+  const int mb = wg / ntb, nb = wg - mb * ntb;
+  const long m0 = static_cast<long>(mb) * kGemmBM;
+  const int n0 = nb * kGemmBN;
+  const int nk = g.K / kGemmBK;
+  const int nt16 = g.N / 16;
+
+  // staging: this thread splits 2 (row, 8-k chunk) pieces of A per k-step -- m-tiles 2*wave, 2*wave+1, row lane & 15,
+  // chunk lane >> 4 -- and copies 3 x 16 B of packed B
+  const float* arow[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    long r = m0 + (2 * wave + j) * 16 + (lane & 15);
+    r = r < g.M ? r : g.M - 1;
+    arow[j] = g.A + r * g.lda + 8 * (lane >> 4);
+  }
+  const bf16x8* bsrc = g.B + static_cast<size_t>(nb) * kGemmNT * 3 * 64;
+  const size_t bstep = static_cast<size_t>(nt16) * 3 * 64;            // bf16x8 per k-step of packed B
+
+  f32x4 ra[2][2];
+  bf16x8 rb[kGemmBPieces];
+  auto load = [&](int kt) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      ra[j][0] = *reinterpret_cast<const f32x4*>(arow[j] + kt * kGemmBK);
+      ra[j][1] = *reinterpret_cast<const f32x4*>(arow[j] + kt * kGemmBK + 4);
+    }
+#pragma unroll
+    for (int p = 0; p < kGemmBPieces; ++p) rb[p] = bsrc[kt * bstep + p * kGemmThreads + tid];
+  };
+  auto store = [&](int s) {
+    char* base = smem + s * kGemmStage;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      bf16x8 p0, p1, p2;
+      split8(ra[j][0], ra[j][1], p0, p1, p2);
+      bf16x8* dst = reinterpret_cast<bf16x8*>(base) + (2 * wave + j) * 3 * 64 + lane;
+      dst[0] = p0;
+      dst[64] = p1;
+      dst[128] = p2;
+    }
+    bf16x8* bdst = reinterpret_cast<bf16x8*>(base + kGemmABytes);
+#pragma unroll
+    for (int p = 0; p < kGemmBPieces; ++p) bdst[p * kGemmThreads + tid] = rb[p];
+  };
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+  load(0);
+  store(0);
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const int cur = kt & 1;
+    load(kt + 1 < nk ? kt + 1 : kt);          // the last step reloads its own tile into the idle buffer: no branch
+    __builtin_amdgcn_sched_barrier(0);        // keep the loads ahead of the MFMAs (the scheduler sinks them otherwise)
+    const bf16x8* sa = reinterpret_cast<const bf16x8*>(smem + cur * kGemmStage) + wm * 4 * 3 * 64 + lane;
+    const bf16x8* sb = reinterpret_cast<const bf16x8*>(smem + cur * kGemmStage + kGemmABytes) + wn * 4 * 3 * 64 + lane;
+    bf16x8 fa[3][4], fb[3][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int p = 0; p < 3; ++p) {
+        fa[p][i] = sa[(i * 3 + p) * 64];
+        fb[p][i] = sb[(i * 3 + p) * 64];
+      }
+    // small terms first; each product sweeps all 16 accumulators (independent MFMAs back to back)
+    constexpr int kPa[6] = {2, 1, 0, 1, 0, 0}, kPb[6] = {0, 1, 2, 0, 1, 0};
+    // the split of step k+1 sits between the two halves: half a step of MFMAs covers the loads' latency, and its VALU
+    // work fills the gaps of the second half
+#pragma unroll
+    for (int t = 0; t < 6; ++t) {
+      if (t == 3) store(cur ^ 1);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kPa[t]][i], fb[kPb[t]][j], acc[i][j], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+
+  // epilogue: accumulator register r of tile (i, j) is row (lane >> 4) * 4 + r, column lane & 15
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int col = n0 + wn * 64 + j * 16 + (lane & 15);
+    const float bv = g.bias ? g.bias[col] : 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const long row = m0 + wm * 64 + i * 16 + (lane >> 4) * 4 + r;
+        if (row < g.M) g.C[row * g.ldc + col] = g.bias ? acc[i][j][r] + bv : acc[i][j][r];
+      }
+  }
+}
+
+// One thread per (k-tile, n-tile, lane): 8 consecutive k of one column, split into the three planes.
+__global__ __launch_bounds__(kBlock) void gemm_pack_b_kernel(const float* __restrict__ w, long ldw, int trans,
+                                                             bf16x8* __restrict__ out, int K, int N) {
+  const long total = static_cast<long>(K / 32) * (N / 16) * 64;
+  for (long idx = static_cast<long>(blockIdx.x) * blockDim.x + threadIdx.x; idx < total;
+       idx += static_cast<long>(gridDim.x) * blockDim.x) {
+    const int l = static_cast<int>(idx & 63);
+    const long tile = idx >> 6;                           // kt * (N / 16) + nt
+    const int nt = static_cast<int>(tile % (N / 16)), kt = static_cast<int>(tile / (N / 16));
+    const int n = nt * 16 + (l & 15), k = kt * 32 + 8 * (l >> 4);
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = trans ? w[static_cast<long>(n) * ldw + k + e] : w[static_cast<long>(k + e) * ldw + n];
+    bf16x8 p0, p1, p2;
+    split8(f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}, p0, p1, p2);
+    out[(tile * 3 + 0) * 64 + l] = p0;
+    out[(tile * 3 + 1) * 64 + l] = p1;
+    out[(tile * 3 + 2) * 64 + l] = p2;
+  }
+}
+
+}  // namespace vqa
+
+using namespace vqa;
+
+extern "C" {
+
+size_t vqa_gemm_packed_bytes(int K, int N) {
+  if (K <= 0 || N <= 0 || K % kGemmBK || N % kGemmBN) return 0;
+  return static_cast<size_t>(K) * N * 3 * sizeof(__bf16);
+}
+
+int vqa_gemm_pack_b(const float* w, long ldw, int trans, void* packed, int K, int N, vqa_stream_t stream) {
+  clear_stale_error();
+  if (!w || !packed) return VQA_ERR_NULL;
+  if (K <= 0 || N <= 0 || K % kGemmBK || N % kGemmBN || (trans != 0 && trans != 1)) return VQA_ERR_SHAPE;
+  if (ldw < (trans ? K : N)) return VQA_ERR_SHAPE;
+  if (!aligned4(w) || !aligned16(packed)) return VQA_ERR_ALIGN;
+  const long work = static_cast<long>(K / 32) * (N / 16) * 64;
+  gemm_pack_b_kernel<<<blocks_for(work, kBlock), kBlock, 0, static_cast<hipStream_t>(stream)>>>(
+      w, ldw, trans, static_cast<bf16x8*>(packed), K, N);
+  return launch_status();
+}
+
+int vqa_gemm_bf16x6(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M, int N,
+                    int K, vqa_stream_t stream) {
+  clear_stale_error();
+  if (!A || !packed || !C) return VQA_ERR_NULL;
+  if (M < 0 || N <= 0 || K <= 0 || K % kGemmBK || N % kGemmBN || lda < K || lda % 4 || ldc < N) return VQA_ERR_SHAPE;
+  if ((M + kGemmBM - 1) / kGemmBM * (N / kGemmBN) > 0x7fffffffL) return VQA_ERR_SHAPE;
+  if (!aligned16(A) || !aligned16(packed) || !aligned4(C) || (bias && !aligned4(bias))) return VQA_ERR_ALIGN;
+  if (M == 0) return VQA_OK;
+  GemmArgs g{A, static_cast<const bf16x8*>(packed), bias, C, lda, ldc, M, N, K};
+  const int grid = static_cast<int>((M + kGemmBM - 1) / kGemmBM * (N / kGemmBN));
+  gemm_bf16x6_kernel<<<grid, kGemmThreads, 0, static_cast<hipStream_t>(stream)>>>(g);
+  return launch_status();
+}
+
+}  // extern "C"

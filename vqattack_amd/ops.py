@@ -703,3 +703,61 @@ def gelu_bwd(h, da, out=None):
         with _on(h):
             check(lib().vqa_gelu_bwd(_p(h), _p(da), _p(out), h.numel(), stream_for(h)), "vqa_gelu_bwd")
     return out
+
+
+class PackedWeight:
+    """A frozen [K, N] GEMM operand packed for ``vqa_gemm_bf16x6``: three bf16 planes in the kernel's fragment order
+    (``include/vqattack_hip.h``), held as raw bytes."""
+    __slots__ = ("data", "K", "N")
+
+    def __init__(self, data, K, N):
+        self.data, self.K, self.N = data, K, N
+
+
+def gemm_shape_ok(N, K):
+    """Shapes the bf16x6 kernel covers: N % 128 == 0, K % 32 == 0 (any row count)."""
+    return N > 0 and K > 0 and N % 128 == 0 and K % 32 == 0
+
+
+def gemm_workgroups(M, N):
+    """Grid of one ``vqa_gemm_bf16x6`` launch: 256 x 128 output tiles."""
+    return -(-M // 256) * (N // 128)
+
+
+def gemm_pack(w, trans):
+    """Pack a weight once.  ``trans=True``: the forward operand ``w.t()`` of a Linear weight ``w`` [out, in]
+    (K = in, N = out); ``trans=False``: ``w`` itself, the input-gradient operand (K = out, N = in)."""
+    dev_f32(w, "w")
+    if w.dim() != 2:
+        raise ValueError("w must be 2-D, got shape {}".format(tuple(w.shape)))
+    K, N = (w.shape[1], w.shape[0]) if trans else (w.shape[0], w.shape[1])
+    nbytes = lib().vqa_gemm_packed_bytes(K, N)
+    if nbytes == 0:
+        raise ValueError("vqa_gemm_pack_b does not cover K={}, N={}".format(K, N))
+    data = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    with _on(w):
+        check(lib().vqa_gemm_pack_b(_p(w), w.shape[1], int(bool(trans)), _p(data), K, N, stream_for(w)), "vqa_gemm_pack_b")
+    return PackedWeight(data, K, N)
+
+
+def gemm(a, packed, bias=None, out=None):
+    """``out = a @ B (+ bias)`` on the bf16 matrix pipe (bf16x6, fp32-grade), B a ``PackedWeight``.  ``a``: fp32 (M, K)
+    with unit column stride and a row stride that is a multiple of 4 floats."""
+    dev_f32(a, "a", contiguous=False)
+    if a.dim() != 2 or a.shape[1] != packed.K or a.stride(1) != 1 or a.stride(0) % 4:
+        raise ValueError("a must be (M, {}) with unit column stride and a row stride % 4 == 0, got shape {} strides {}"
+                         .format(packed.K, tuple(a.shape), a.stride()))
+    M = a.shape[0]
+    if out is None:
+        out = torch.empty(M, packed.N, dtype=torch.float32, device=a.device)
+    dev_f32(out, "out")
+    if tuple(out.shape) != (M, packed.N):
+        raise ValueError("out must be ({}, {}), got {}".format(M, packed.N, tuple(out.shape)))
+    if bias is not None:
+        dev_f32(bias, "bias"), _rows_ok("bias", bias, packed.N)
+    same_device(a, packed.data, bias, out)
+    if M:
+        with _on(a):
+            check(lib().vqa_gemm_bf16x6(_p(a), a.stride(0), _p(packed.data), ptr(bias), _p(out), packed.N, M, packed.N,
+                                        packed.K, stream_for(a)), "vqa_gemm_bf16x6")
+    return out

@@ -16,19 +16,59 @@ loss kernel's gradient of that feature map (+ the layer-scaled branch gradient).
 ``torch.autograd.Function`` whose outputs are the per-layer feature maps and the final normalised states, so callers
 (the ``model_fn`` closures, the loss kernels' ``torch.autograd.backward(outputs, grads)``) see ordinary tensors.
 """
+import os
+
 import torch
 
 from .. import attention as _attn
 from .. import ops
 
+# Encoder GEMMs run on the bf16x6 kernel (csrc/gemm.hip: fp32-grade products on the bf16 matrix pipe) where it covers
+# the shape and its grid has at least MIN_WORKGROUPS workgroups (one 256 x 128 output tile each, one per CU at a time);
+# below that it cannot fill the 256 CUs and the library fp32 GEMM is faster.  Measured per shape (tools/gemm_bench.py,
+# VLMO-base): 1.21-1.41x at 888-2664 workgroups and at the text expert's 240 (2560 x 3072), 0.45x at its 60
+# (2560 x 768).  VQA_GEMM=library restores the library everywhere.
+MIN_WORKGROUPS = 192
+
+
+def _kernel_gemms():
+    return os.environ.get("VQA_GEMM", "") != "library"
+
+
+def _pack(w):
+    """(forward operand w.t(), input-gradient operand w) of a Linear weight w [out, in], packed once for the kernel;
+    None where the kernel does not cover the shape or VQA_GEMM=library."""
+    if not _kernel_gemms() or not (ops.gemm_shape_ok(w.shape[0], w.shape[1]) and ops.gemm_shape_ok(w.shape[1], w.shape[0])):
+        return (None, None)
+    return (ops.gemm_pack(w, trans=True), ops.gemm_pack(w, trans=False))
+
+
+def _linear(a, w, bias, packed):
+    """a @ w.t() + bias (a Linear layer's forward)."""
+    if packed[0] is not None and ops.gemm_workgroups(a.shape[0], packed[0].N) >= MIN_WORKGROUPS and _kernel_gemms():
+        return ops.gemm(a, packed[0], bias)
+    return torch.addmm(bias, a, w.t())
+
+
+def _linear_grad(g, w, packed):
+    """g @ w (the input gradient of a Linear layer)."""
+    if packed[1] is not None and ops.gemm_workgroups(g.shape[0], packed[1].N) >= MIN_WORKGROUPS and _kernel_gemms():
+        return ops.gemm(g, packed[1])
+    return torch.mm(g, w)
+
 
 class LayerSpec:
-    """Frozen parameters of one block, in the form the stages consume (plain fp32 device tensors)."""
-    __slots__ = ("ln1", "wqkv", "bqkv", "wproj", "bproj", "gamma1", "ln2", "mlp", "gamma2", "eps")
+    """Frozen parameters of one block, in the form the stages consume (plain fp32 device tensors), and every weight
+    packed for the GEMM kernel: ``packed[name] = (forward operand, input-gradient operand)`` for "qkv", "proj" and
+    "fc1_e" / "fc2_e" of expert e (``_pack``; 12 bytes per parameter)."""
+    __slots__ = ("ln1", "wqkv", "bqkv", "wproj", "bproj", "gamma1", "ln2", "mlp", "gamma2", "eps", "packed")
 
     def __init__(self, ln1, wqkv, bqkv, wproj, bproj, gamma1, ln2, mlp, gamma2, eps):
         self.ln1, self.wqkv, self.bqkv, self.wproj, self.bproj = ln1, wqkv, bqkv, wproj, bproj
         self.gamma1, self.ln2, self.mlp, self.gamma2, self.eps = gamma1, ln2, mlp, gamma2, eps
+        self.packed = dict(qkv=_pack(wqkv), proj=_pack(wproj))
+        for e, (w1, _b1, w2, _b2) in enumerate(mlp):
+            self.packed["fc1_%d" % e], self.packed["fc2_%d" % e] = _pack(w1), _pack(w2)
 
 
 class EncoderSpec:
@@ -130,12 +170,12 @@ def _forward(x0, call, save):
             ops.ln_fwd(x, lay.ln1[0], lay.ln1[1], y, mean1, rstd1, lay.eps, r0=pend[0], r1=pend[1], rscale=pend[2],
                        x_out=x_l, period=s if pend[1] is not None else 0, split=t if pend[1] is not None else 0)
             feats.append(x_l)
-        qkv = torch.addmm(lay.bqkv, y, lay.wqkv.t())
+        qkv = _linear(y, lay.wqkv, lay.bqkv, lay.packed["qkv"])
         del y
         qkv5 = qkv.view(b, s, 3, spec.heads, _attn.HEAD_DIM)
         q, k, v, bias_t, bstr, hole = _attention_inputs(qkv5, None if call.biases is None else call.biases[li], save)
         o, lse, scores = _attn._forward(q, k, v, bias_t, bstr, scale, save_scores=save, key_hole=hole)
-        p = torch.addmm(lay.bproj, o.view(rows, d), lay.wproj.t())
+        p = _linear(o.view(rows, d), lay.wproj, lay.bproj, lay.packed["proj"])
         x1 = torch.empty(b, s, d, dtype=f32, device=dev)
         mean2, rstd2 = torch.empty(rows, dtype=f32, device=dev), torch.empty(rows, dtype=f32, device=dev)
         two = len(lay.mlp) == 2
@@ -148,10 +188,10 @@ def _forward(x0, call, save):
             ops.ln_fwd(x_l, lay.ln2[0][0], lay.ln2[0][1], ys[0], mean2, rstd2, lay.eps, r0=p, rscale=lay.gamma1, x_out=x1)
         del p
         hs, ms = [], []
-        for ye, (w1, b1, w2, b2) in zip(ys, lay.mlp):
-            h = torch.addmm(b1, ye, w1.t())
+        for e, (ye, (w1, b1, w2, b2)) in enumerate(zip(ys, lay.mlp)):
+            h = _linear(ye, w1, b1, lay.packed["fc1_%d" % e])
             a = ops.gelu_fwd(h)
-            ms.append(torch.addmm(b2, a, w2.t()))
+            ms.append(_linear(a, w2, b2, lay.packed["fc2_%d" % e]))
             hs.append(h)
             del a
         del ys
@@ -208,10 +248,10 @@ def _backward(saved, call, g_feats, g_states, shape):
         lay, sv = spec.layers[li], saved[li]
         two = len(lay.mlp) == 2
         dys = []
-        for dme, h, (w1, _b1, w2, _b2) in zip(dm, sv["hs"], lay.mlp):
-            da = torch.mm(dme, w2)                # (rows_e, 4D)
+        for e, (dme, h, (w1, _b1, w2, _b2)) in enumerate(zip(dm, sv["hs"], lay.mlp)):
+            da = _linear_grad(dme, w2, lay.packed["fc2_%d" % e])      # (rows_e, 4D)
             ops.gelu_bwd(h, da)                   # in place: dh
-            dys.append(torch.mm(da, w1))
+            dys.append(_linear_grad(da, w1, lay.packed["fc1_%d" % e]))
             del da
         del dm
         dx1 = torch.empty(rows, d, dtype=torch.float32, device=dev)
@@ -220,14 +260,14 @@ def _backward(saved, call, g_feats, g_states, shape):
                    gamma1=lay.ln2[1][0] if two else None, g_a=g, rscale=lay.gamma1,
                    dr0=dp if lay.gamma1 is not None else None, period=s if two else 0, split=t if two else 0)
         del dys, g
-        do = torch.mm(dp, lay.wproj)
+        do = _linear_grad(dp, lay.wproj, lay.packed["proj"])
         dqkv = torch.empty_like(sv["qkv"])
         qkv5, dqkv5 = sv["qkv"].view(b, s, 3, spec.heads, _attn.HEAD_DIM), dqkv.view(b, s, 3, spec.heads, _attn.HEAD_DIM)
         _attn._backward(qkv5[:, :, 0], qkv5[:, :, 1], qkv5[:, :, 2], sv["bias"], sv["bstr"], sv["o"], sv["lse"],
                         do.view(b, s, spec.heads, _attn.HEAD_DIM), dqkv5[:, :, 0], dqkv5[:, :, 1], dqkv5[:, :, 2], scale,
                         scores=sv["scores"])
         del do, dp
-        dy1 = torch.mm(dqkv, lay.wqkv)
+        dy1 = _linear_grad(dqkv.view(rows, -1), lay.wqkv, lay.packed["qkv"])
         del dqkv
         dx_l = torch.empty(rows, d, dtype=torch.float32, device=dev)
         if li > 0:

@@ -9,7 +9,9 @@ winners; the result (a CSV of shape -> solution index, with the PyTorch / ROCm /
 is tracked under ``vqattack_amd/tuning/``.  ``enable()`` loads it with tuning switched OFF: shapes in the file run the
 recorded solution, every other shape the library default; a file recorded for another software stack fails TunableOp's
 validators and is ignored (library defaults everywhere) -- so this is never a correctness dependency, and the
-arithmetic stays the library's fp32 GEMM.  Every recorded entry is checked on the GPU for run-to-run bit stability and
+arithmetic of the GEMMs it covers stays the library's fp32 GEMM.  Since the bf16x6 kernel (``csrc/gemm.hip``) took over
+the large encoder GEMMs, the file matters only for the shapes ``_fused.py`` still sends to the library (small grids, or
+``VQA_GEMM=library``).  Every recorded entry is checked on the GPU for run-to-run bit stability and
 against the default solution (``tests/test_tuned_gemms.py``), and a white-box attack step with the file active is
 required to be bitwise reproducible.
 """
