@@ -350,7 +350,9 @@ int vqa_resize_bicubic_v_normalize(const uint8_t* src, int h_in, int w, int c, c
  *
  * vqa_ln_fwd: optional prologue  x_out = x + rscale * r  (r0 != NULL; r given whole as r0, or split as r0 / r1;
  *   rscale NULL = 1), then  y = LayerNorm(x_out; gamma, beta, eps)  with (gamma1, beta1) for segment-1 rows when given,
- *   y written whole (y1 == NULL) or split (y0 / y1); mean[row], rstd[row] saved for the backward.  Without a prologue
+ *   y written whole (y1 == NULL) or split (y0 / y1); mean[row], rstd[row] saved for the backward.  The statistics are
+ *   taken on the row centred on its first element, so rows far from zero or nearly constant keep their spread; the
+ *   backward reads rstd and forms x - mean from x in the same way (bitwise what the forward used).  Without a prologue
  *   x_out is not written.  16 B/element with prologue, 8 without.  Replaces torch.addcmul + torch.cat + two slice copies
  *   + F.layer_norm per stage (multiway_transformer.py:186-199).
  * vqa_ln_bwd: dx = (g_a ? g_a : 0) + (g_inj ? g_inj : 0) + dLayerNorm/dx(dy; x, mean, rstd, gamma)  (frozen gamma/beta:

@@ -147,8 +147,10 @@ def test_key_hole_equals_the_dense_padding_mask(b, h, s):
 # ---- the reference's own resolution: 480 x 480 images = 30 x 30 + 1 = 901 image tokens (ALBEF_attack/configs/VQA.yaml:10,
 # vlmo/config.py:283-299).  VLMo: 40 text + 901 = 941 tokens, 915 after the padding trim of a 12-word batch; ALBEF's
 # fusion layers: <= 25 text queries over the 901 image keys (multiway_transformer.py:88-118, xbert.py cross attention).
-# More key tiles than any 384-px case (30 instead of 19-20), a ragged last tile (941 = 29 * 32 + 13), the lazy-max
-# rescale over a longer row, and saved scores / dS^T workspaces at (8 * 128) x (30 * 32) per (batch, head).
+# More key tiles than any 384-px case (30 instead of 19-20), a ragged last tile (941 = 29 * 32 + 13), and saved scores /
+# dS^T workspaces at (8 * 128) x (30 * 32) per (batch, head).  At these unit-variance statistics no row's max rises by
+# more than kLazyMax after its first tile, so the forward's lazy-max rescale does not fire here: test_attention_fp64.py
+# drives it with trained-model statistics.
 @pytest.mark.parametrize("s", [915, 941])
 @pytest.mark.parametrize("form", ["saved_scores", "ds_workspace", "recompute"])
 def test_self_attention_at_the_480px_token_counts(s, form, monkeypatch):

@@ -354,17 +354,21 @@ __global__ __launch_bounds__(kBlock, 2) void attn_fwd_kernel(const float* __rest
       if (HAS_BIAS && more) bnext = load_bias_tile(bp, k0 + kTile);
       __builtin_amdgcn_sched_barrier(0);         // keep every load ahead of the MFMA chain that hides its latency
       VQA_STAMP(0);                              // segment 0: the prefetches' address work and issue
-      f32x16 st = bcur;                          // S^T = bias + K . (scale Q)^T, key on the accumulator row
-      if (k0 < hole_hi && k0 + kTile > hole_lo) {   // a tile that overlaps the hole (at most two of ~19): -inf goes into
-#pragma unroll                                      // the initial accumulator, so the saved scores carry it too
+      // S^T = K . (scale Q)^T + bias, key on the accumulator row.  The chain starts from zero and the bias is added
+      // once: started from the bias tile, every partial sum of the chain would be rounded at the bias' magnitude (a
+      // trained position bias or a key ramp of tens), 4-5x the score error of the library's attention.
+      f32x16 st = {0};
+#pragma unroll
+      for (int s = 0; s < 32; ++s) st = mfma(Ks[s], qf[s], st);
+      VQA_STAMP(1);                              // segment 1: the S chain's issue (its last MFMA still runs)
+      if (HAS_BIAS) st += bcur;
+      if (k0 < hole_hi && k0 + kTile > hole_lo) {   // a tile that overlaps the hole (at most two of ~19): -inf, and
+#pragma unroll                                      // the saved scores carry it too
         for (int i = 0; i < 16; ++i) {
           const int key = k0 + acc_row(i, h);
           st[i] = (key >= hole_lo && key < hole_hi) ? -INFINITY : st[i];
         }
       }
-#pragma unroll
-      for (int s = 0; s < 32; ++s) st = mfma(Ks[s], qf[s], st);
-      VQA_STAMP(1);                              // segment 1: the S chain's issue (its last MFMA still runs)
       if (STORE_S) sraw = st;                    // stored at the end of the tile (see there)
       if (k0 + kTile > d.Sk) {                   // last, partial tile: keys beyond Sk never win the softmax
 #pragma unroll
@@ -490,7 +494,7 @@ __global__ __launch_bounds__(kBlock) void attn_fwd_combine_kernel(const float* _
 //   S^T = bias + K . (scale Q)^T (key rows in the accumulator),  P^T = exp(S^T - LSE),  dP^T = V . dO^T,
 //   dS^T = P^T o (dP^T - delta),  dQ^T += K^T . dS^T  (sum over the key = the accumulator's row index: registers feed
 //   the MFMA).  Also computes delta[b, h, q] = sum_d dO . O for its queries and stores it for the dK / dV kernel.
-// Same instruction diet as the forward: bias tile = initial accumulator, exp through one fma, packed subtract /
+// Same instruction diet as the forward: the bias added once after the S chain, exp through one fma, packed subtract /
 // multiply for dS, masks in the last tile only.  K and V tiles are interleaved in LDS (dimensions d, d + 32 adjacent):
 // the row reads of the first two products use immediate offsets 2 s, the column reads of the third are one ds_read_b64.
 template <bool HAS_BIAS>
@@ -558,13 +562,14 @@ __global__ __launch_bounds__(kBlock, 3) void attn_bwd_dq_kernel(const float* __r
       tv = load_tile_next(cv, kt + 1);
     }
     if (active) {
-      f32x16 st = {0}, dp = {0};
-      if (HAS_BIAS) st = load_bias_tile(bp, k0);   // the initial accumulator of the S^T chain ...
+      f32x16 st = {0}, dp = {0}, bt = {0};
+      if (HAS_BIAS) bt = load_bias_tile(bp, k0);   // added to S^T after its chain (the forward's rounding) ...
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int s = 0; s < 32; ++s) dp = mfma(Vr[2 * s], gf[s], dp);   // ... which starts 32 MFMAs after its loads
 #pragma unroll
       for (int s = 0; s < 32; ++s) st = mfma(Kr[2 * s], qf[s], st);
+      if (HAS_BIAS) st += bt;
       if (k0 + kTile > d.Sk) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) st[i] = k0 + acc_row(i, h) < d.Sk ? st[i] : -INFINITY;
@@ -733,7 +738,7 @@ __global__ __launch_bounds__(kBlock, 2) void attn_bwd_dq_staged_kernel(const flo
 //   row index).  The per-query constants -LSE log2 e and -delta ride in LDS next to the tiles, four consecutive
 //   accumulator rows per 16-byte read; -delta is the INITIAL accumulator of the dP chain (dS = P o dP is then one
 //   multiply per element); the bias of this lane's key for the tile's query rows is 16 dword loads from a uniform row
-//   base + a per-lane 32-bit offset, prefetched one tile ahead into the initial accumulator of the S chain.
+//   base + a per-lane 32-bit offset, prefetched one tile ahead and added to the S chain's result.
 template <bool HAS_BIAS, bool STORE_DS, bool FROM_SCORES, bool SPLIT = false>
 __global__ __launch_bounds__(kBlock, 2) void attn_bwd_dkv_kernel(const float* __restrict__ q,
                                                                  const float* __restrict__ k,
@@ -769,7 +774,7 @@ __global__ __launch_bounds__(kBlock, 2) void attn_bwd_dkv_kernel(const float* __
   const float* vp = v + b * d.v_sb + head * d.v_sh + static_cast<long>(kl) * d.v_ss + 32 * h;
   const float* qb = q + b * d.q_sb + head * d.q_sh;
   const float* gb = go + b * go_sb + head * go_sh;
-  // The S chain's initial accumulator is the bias tile, a (query row, key) matrix of one (batch, head) -- unless the
+  // The bias tile, a (query row, key) matrix of one (batch, head), is added to the S chain's result -- unless the
   // forward saved its scores (bias included): then the scores replace the chain (they come through LDS, see below).
   constexpr bool kInit = HAS_BIAS && !FROM_SCORES;
   const long init_sr = d.bias_sr;
@@ -895,7 +900,7 @@ __global__ __launch_bounds__(kBlock, 2) void attn_bwd_dkv_kernel(const float* __
       __builtin_amdgcn_sched_barrier(0);
       VQA_STAMP(0);                                // segment 0: the prefetches' address work and issue
       // dP's chain starts from -delta of its query rows (the accumulator's rows), so dS = P o dP needs no subtraction
-      f32x16 st = bcur;
+      f32x16 st = {0};
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const f32x4 nd = *reinterpret_cast<const f32x4*>(Ds + 8 * g);
@@ -923,6 +928,7 @@ __global__ __launch_bounds__(kBlock, 2) void attn_bwd_dkv_kernel(const float* __
           st = mfma(Qr[2 * s], kf[s], st);
           dp = mfma(Gr[2 * s], vf[s], dp);
         }
+        if (kInit) st += bcur;                     // the bias after the chain, rounded as in the forward
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const f32x4 nl = *reinterpret_cast<const f32x4*>(Ls + 8 * g);

@@ -66,6 +66,26 @@ __device__ __forceinline__ void store_vec(const f32x4 (&v)[NCH], float* __restri
   }
 }
 
+// The first element of the row (lane 0's first value), uniform over the wave.
+__device__ __forceinline__ float row_pivot(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
+}
+
+// v -= pivot over the row's D elements (0 beyond them); returns the row sum of the centred values.  x - pivot is exact
+// wherever x lies within a factor 2 of the pivot -- the rows whose mean a plain fp32 sum gets wrong.
+template <int NCH>
+__device__ __forceinline__ float centre_on_pivot(f32x4 (&v)[NCH], float pivot, int lane, int D) {
+  float s = 0.0f;
+#pragma unroll
+  for (int k = 0; k < NCH; ++k) {
+    const int d = (k * kWave + lane) * 4;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[k][e] = d < D ? v[k][e] - pivot : 0.0f;
+    s += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
+  }
+  return wave_sum(s);
+}
+
 struct LnFwdArgs {
   const float *x, *r0, *r1, *rscale;
   float* x_out;
@@ -101,17 +121,17 @@ __global__ __launch_bounds__(kBlock) void ln_fwd_kernel(LnFwdArgs A) {
       }
       store_vec<NCH>(x, A.x_out + static_cast<long>(row) * A.D, lane, A.D);
     }
-    float s1 = 0.0f;
-#pragma unroll
-    for (int k = 0; k < NCH; ++k) s1 += (x[k][0] + x[k][1]) + (x[k][2] + x[k][3]);
-    const float mean = wave_sum(s1) * inv_d;
+    // statistics of the row centred on its first element: a row far from zero, or nearly constant, keeps its spread
+    const float pivot = row_pivot(x[0][0]);
+    const float mean_c = centre_on_pivot<NCH>(x, pivot, lane, A.D) * inv_d;
+    const float mean = pivot + mean_c;
     float s2 = 0.0f;
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
       const int d = (k * kWave + lane) * 4;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float c = d < A.D ? x[k][e] - mean : 0.0f;
+        const float c = d < A.D ? x[k][e] - mean_c : 0.0f;
         x[k][e] = c;
         s2 += c * c;
       }
@@ -157,14 +177,18 @@ __global__ __launch_bounds__(kBlock) void ln_bwd_kernel(LnBwdArgs A) {
 #pragma unroll
       for (int k = 0; k < NCH; ++k) g[k] = g[k] * w[k];
     }
-    const float mean = A.mean[row], rstd = A.rstd[row];
+    // x - mean exactly as the forward formed it (the same pivot, sum and order: bitwise the same values); the saved
+    // mean = pivot + mean_c is rounded, and subtracting it would lose a near-constant row's spread
+    const float rstd = A.rstd[row];
+    const float pivot = row_pivot(xh[0][0]);
+    const float mean_c = centre_on_pivot<NCH>(xh, pivot, lane, A.D) * inv_d;
     float c1 = 0.0f, c2 = 0.0f;
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
       const int d = (k * kWave + lane) * 4;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float h = d < A.D ? (xh[k][e] - mean) * rstd : 0.0f;
+        const float h = d < A.D ? (xh[k][e] - mean_c) * rstd : 0.0f;
         xh[k][e] = h;
         c1 += g[k][e];
         c2 += g[k][e] * h;

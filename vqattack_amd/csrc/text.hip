@@ -33,6 +33,28 @@ __global__ __launch_bounds__(kBlock) void gather_rows_kernel(const float* __rest
   }
 }
 
+// The embedding's LayerNorm statistics are taken on the row centred on its first element (lane 0's first value): e -= pivot
+// over the D elements, returns the row sum.  A near-constant row -- word + type + position nearly equal over the width,
+// at BERT's eps = 1e-12 -- keeps its spread, which a plain fp32 mean would round away.  The kernels below then use
+// e - mean for the centred values, and the LayerNorm output does not depend on the pivot.
+template <int NCH>
+__device__ __forceinline__ float centre_on_pivot(f32x4 (&e)[NCH], int lane, int D) {
+  const float pivot = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, e[0][0]), 0));
+  float s = 0.0f;
+#pragma unroll
+  for (int ch = 0; ch < NCH; ++ch) {
+    const int d = (ch * kWave + lane) * 4;
+    if (d < D) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        e[ch][j] -= pivot;
+        s += e[ch][j];
+      }
+    }
+  }
+  return wave_sum(s);
+}
+
 // One wave per candidate {sample, position, grad row, vocab id}.
 template <int NCH>
 __global__ __launch_bounds__(kBlock) void cand_dir_sim_kernel(
@@ -48,7 +70,6 @@ __global__ __launch_bounds__(kBlock) void cand_dir_sim_kernel(
     const float* po = e_ori + (static_cast<long>(s) * L + p) * D;
     const float* pg = grad + (static_cast<long>(s) * K + k) * D;
     f32x4 e[NCH];
-    float sum = 0.0f;
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch) {
       const int d = (ch * kWave + lane) * 4;
@@ -59,13 +80,12 @@ __global__ __launch_bounds__(kBlock) void cand_dir_sim_kernel(
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           e[ch][j] = (w[j] + t[j]) + q[j];   // BertEmbeddings: inputs_embeds + token_type, then + position
-          sum += e[ch][j];
         }
       } else {
         e[ch] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
       }
     }
-    const float mean = wave_sum(sum) / static_cast<float>(D);
+    const float mean = centre_on_pivot<NCH>(e, lane, D) / static_cast<float>(D);   // of e - pivot (see there)
     float var = 0.0f;
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch) {
@@ -126,7 +146,6 @@ __global__ __launch_bounds__(kBlock) void embed_tokens_kernel(const float* __res
     const float* pw = word + static_cast<long>(triples[3 * i + 2]) * D;
     const float* pp = pos + static_cast<long>(triples[3 * i + 1]) * D;
     f32x4 e[NCH];
-    float sum = 0.0f;
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch) {
       const int d = (ch * kWave + lane) * 4;
@@ -137,13 +156,12 @@ __global__ __launch_bounds__(kBlock) void embed_tokens_kernel(const float* __res
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           e[ch][j] = (w[j] + t[j]) + q[j];
-          sum += e[ch][j];
         }
       } else {
         e[ch] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
       }
     }
-    const float mean = wave_sum(sum) / static_cast<float>(D);
+    const float mean = centre_on_pivot<NCH>(e, lane, D) / static_cast<float>(D);   // of e - pivot (see there)
     float var = 0.0f;
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch) {
