@@ -70,23 +70,56 @@ def mlm_proposer(checkpoint, vocab_file, device):
     return model, banned
 
 
+def answer_scoring(flavor, vocab, vocab_file, tables_dir):
+    """``AnswerScoring`` for the reference's answer-string mode: the answer vocabulary (list of strings), the BERT
+    ``vocab.txt`` and the directory holding the clean-answer table (``albef_ans_table*`` / ``vlmo_ans_table*``)."""
+    from vqattack_amd.attack.answers import AnswerScoring
+    from vqattack_amd.attack.dataset import load_tables
+    from vqattack_amd.attack.wordpiece import WordPiece
+    if not vocab_file:
+        raise SystemExit("scoring by answer string needs the BERT vocabulary (vocab file)")
+    clean = load_tables(tables_dir, flavor)["clean_answers"] if tables_dir else None
+    if not clean:
+        raise SystemExit("scoring by answer string needs the clean-answer table {}_ans_table.txt in the tables "
+                         "directory".format(flavor))
+    return AnswerScoring(flavor, vocab, clean, WordPiece(vocab_file))
+
+
 def load_checkpoint(path):
     """``torch.load(path, map_location='cpu')`` of a reference checkpoint (adv_attack.py:83,96; vlmo_module.py:690) --
     tensors only (``weights_only``): a checkpoint is data, never code."""
-    return torch.load(path, map_location="cpu", weights_only=True)
+    import pickle
+    try:
+        return torch.load(path, map_location="cpu", weights_only=True)
+    except pickle.UnpicklingError as e:
+        raise SystemExit(
+            "{}: the checkpoint holds more than tensors and containers ({}), and it is never unpickled as code here.  "
+            "Export a tensors-only copy once, where the checkpoint was written:\n  python -c \"import torch; "
+            "ck = torch.load('{}', map_location='cpu', weights_only=False); torch.save({{k: ck[k] for k in ('model', "
+            "'state_dict', 'module') if k in ck}}, 'tensors_only.pth')\"".format(path, str(e).splitlines()[0], path))
 
 
-def finish(rank, world, result, out_json=None):
+def finish(rank, world, result, out_json=None, strings_file=None):
+    """Print ``acc_vqa`` + the sweep line; rank 0 writes ``adv_txt.json`` and, in the answer-string mode, the reference's
+    string file (``strings_file``: ``adv_txt_dict_albef.txt`` / ``adv_txt_dict_VLMO_BASE.txt``, json ``{qid: text}``,
+    adv_attack.py:734-735 / vlmo_module.py:2095-2097) and ``adv_success.json`` (``{qid: 0/1}``) next to it."""
     if rank == 0:
         print("acc_vqa", result["asr"], result["n_total"], flush=True)     # the reference's final print (vlmo_module.py:2122)
         print("sweep", json.dumps({k: (round(v, 3) if isinstance(v, float) else v) for k, v in result.items()
                                    if k in ("n_local", "seconds", "examples_per_sec_local", "gradient_steps", "n_batches",
                                             "mean_batch", "collectives", "input_seconds", "input_blocked_seconds",
-                                            "writer_seconds", "skipped")}), flush=True)
+                                            "writer_seconds", "skipped", "skipped_misaligned", "scoring_seconds")}),
+              flush=True)
         if out_json:       # result["adv_text"] holds EVERY rank's samples (run_sweep gathers them): the complete output
             os.makedirs(os.path.dirname(os.path.abspath(out_json)), exist_ok=True)
             with open(out_json, "w") as f:
                 json.dump(result["adv_text"], f)
+        if strings_file and "adv_text_str" in result:
+            os.makedirs(os.path.dirname(os.path.abspath(strings_file)), exist_ok=True)
+            with open(strings_file, "w") as f:
+                f.write(json.dumps(result["adv_text_str"]))
+            with open(os.path.join(os.path.dirname(os.path.abspath(strings_file)), "adv_success.json"), "w") as f:
+                json.dump(result["success"], f)
     if dist.is_initialized():
         if rank == 0:
             print("dist_backend", dist.get_backend(), "world", dist.get_world_size(), "collectives",

@@ -13,11 +13,17 @@ File inputs instead of the synthetic set (``attack/dataset.py``): ``questions=``
 tables: ``right_part``, ``vlmo_ans_table``, ``vilt_ans_table_for_chatgpt``, ``chatgpt_all_5k``, ``all_correct_ans``).
 8-bit images are resized + normalised on the device (Pillow-exact), the next batch's files are read while the current
 one is attacked; ``attack_dir=`` receives ``<question_id>.pt`` and ``adv_txt.json``.
+
+``id2answer=`` (the answer vocabulary as JSON: a list, or ``{id: answer}``; the reference's dill-pickled
+``id2answer.txt`` is refused with the one-line export) turns on the reference's scoring: ``acc_vqa`` counts answer
+strings that differ from ``vlmo_ans_table`` (``vqattack_amd/attack/answers.py``), and ``adv_txt_dict_VLMO_BASE.txt`` is
+written to ``attack_dir``.
 """
 import os
 import sys
 
-from _common import file_source, finish, init_distributed, load_checkpoint, mlm_proposer, seed_everything
+from _common import (answer_scoring, file_source, finish, init_distributed, load_checkpoint, mlm_proposer,
+                     seed_everything)
 
 import torch.distributed as dist  # noqa: E402  (after _common: it sets the HSA IPC mode before torch loads)
 
@@ -30,7 +36,8 @@ NAMED = {
 }
 DEFAULTS = dict(arch="vlmo_base", image_size=384, max_text_len=40, per_gpu_batchsize=64, seed=1, test_only=True,
                 n_samples=128, image_only=False, attack_dir="", dual_every=0, mixed=False, questions="", image_root="",
-                vocab_file="", tables_dir="", pretrain_path="", load_path="", mlm_checkpoint="", sim_threshold=0.95)
+                vocab_file="", tables_dir="", pretrain_path="", load_path="", mlm_checkpoint="", sim_threshold=0.95,
+                id2answer="")
 
 
 def parse(argv):
@@ -81,14 +88,26 @@ def main():
     if cfg["questions"]:
         source = file_source("vlmo", cfg["questions"], cfg["image_root"], mcfg.max_text_len, mcfg.image_size,
                              cfg["vocab_file"], cfg["tables_dir"], joint=not cfg["image_only"])
+    scoring = None
+    if cfg["id2answer"]:
+        from vqattack_amd.attack.answers import load_id2answer
+        if source is None:
+            raise SystemExit("id2answer= scores file inputs: give questions=")
+        try:
+            vocab = load_id2answer(cfg["id2answer"])
+        except ValueError as e:
+            raise SystemExit(str(e))
+        scoring = answer_scoring("vlmo", vocab, cfg["vocab_file"], cfg["tables_dir"])
     res = run_sweep("vlmo", white, black, vlmo.VlmoAttackAdapters(white), cfg["n_samples"], cfg["per_gpu_batchsize"],
                     mcfg.image_size, mcfg.max_text_len, device, rank, world, joint=not cfg["image_only"],
                     save_dir=cfg["attack_dir"] or None, seed=cfg["seed"],
                     max_words=4 if cfg["arch"] == "vlmo_tiny" else 12, dual_every=cfg["dual_every"], mixed=cfg["mixed"],
                     force_collective=dist.is_initialized(), source=source, mlm_logits_fn=proposer, banned_ids=banned,
-                    config=AttackConfig(sim_threshold=cfg["sim_threshold"]))      # adv_attack.py:303: 0.95
+                    config=AttackConfig(sim_threshold=cfg["sim_threshold"]),      # adv_attack.py:303: 0.95
+                    scoring=scoring)
     # adversarial images <qid>.pt and the adversarial-text json go to attack_dir (vlmo_module.py:166-167,2059-2062,2095-2097)
-    finish(rank, world, res, os.path.join(cfg["attack_dir"], "adv_txt.json") if cfg["attack_dir"] else None)
+    finish(rank, world, res, os.path.join(cfg["attack_dir"], "adv_txt.json") if cfg["attack_dir"] else None,
+           os.path.join(cfg["attack_dir"], "adv_txt_dict_VLMO_BASE.txt") if cfg["attack_dir"] and scoring else None)
 
 
 if __name__ == "__main__":

@@ -248,6 +248,9 @@ class VqaFilePairs(_Uint8Source):
         self.flavor, self.text_len, self.image_root = flavor, text_len, image_root
         self.skipped = 0
         rows, self.qids, self.files, self.tasks, self.questions = [], [], [], [], []
+        # per sample: the annotation's ``answer`` / ``dataset`` fields and the question's (words, piece ids per word) --
+        # what answer-string scoring reads (attack/answers.py)
+        self.answers, self.datasets, self.word_pieces = [], [], []
         stop = set(stop_words)
         tail = ()
         if flavor != "albef":                                 # the VLMO copy appends ' .' to the paraphrase
@@ -285,12 +288,22 @@ class VqaFilePairs(_Uint8Source):
             self.qids.append(qid)
             self.files.append(os.path.join(image_root, a["image"]))
             self.questions.append(a.get("question"))
+            self.answers.append(a.get("answer"))
+            self.datasets.append(a.get("dataset"))
+            self.word_pieces.append((list(words), [tuple(p) for p in pieces]))
             self.tasks.append(self._task(a, qid, tables, tokenizer, tail))
         self.n = len(rows)
         self.ids = torch.tensor([r[0] for r in rows], dtype=torch.int64).reshape(self.n, text_len)
         self.masks = torch.tensor([r[1] for r in rows], dtype=torch.int64).reshape(self.n, text_len)
         self.attackable = torch.tensor([r[2] for r in rows], dtype=torch.bool).reshape(self.n, text_len)
         self._init_pipeline(image_size, workers)
+
+    def annotation(self, i):
+        """The fields of sample ``i``'s annotation entry that the reference's alignment check reads."""
+        ann = {"question_id": self.qids[i], "answer": self.answers[i]}
+        if self.datasets[i] is not None:
+            ann["dataset"] = self.datasets[i]
+        return ann
 
     def _task(self, a, qid, tables, tok, tail):
         """Loss mode + MLM task of one question from the tables (adv_attack.py:428-558)."""

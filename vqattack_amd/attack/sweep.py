@@ -11,6 +11,7 @@ import time
 import numpy as np
 import torch
 
+from .answers import victim_input
 from .asr import SuccessLedger, shard_indices
 from .runner import AttackConfig, BatchedVQAttack
 from .schedule import bucket_by_schedule, gradient_steps
@@ -71,7 +72,7 @@ def synthetic_images(qids, image_size, device):
 def run_sweep(flavor, white, black, adapters, n_samples, batch, image_size, text_len, device, rank=0, world=1,
               config=None, joint=True, save_dir=None, log_every=50, seed=0, max_words=12, dual_every=0, mixed=False,
               attack=None, force_collective=False, collective_device=None, progress=None, source=None,
-              mlm_logits_fn=None, banned_ids=None):
+              mlm_logits_fn=None, banned_ids=None, scoring=None):
     """Returns ``dict(asr, n_total, n_local, seconds, examples_per_sec_local, gradient_steps, n_batches, mean_batch,
     global_steps, batch_global_steps, gather_seconds, adv_text, collectives, input_seconds, input_blocked_seconds,
     writer_seconds)`` on every rank: ``seconds`` is this rank's attack + scoring time (device drained, the ``.pt`` writer
@@ -91,7 +92,16 @@ def run_sweep(flavor, white, black, adapters, n_samples, batch, image_size, text
     ``mixed=False``: samples are bucketed by (schedule, loss mode) and every batch is schedule-pure
     (``BatchedVQAttack.attack_batch``).  ``mixed=True``: ONE bucket -- samples are batched in index order whatever their
     word counts and loss modes (``attack_mixed``: prefix scheduling, dual-loss samples alternate feature and MLM steps
-    inside the shared white-box pass)."""
+    inside the shared white-box pass).
+
+    ``scoring``: an ``answers.AnswerScoring`` (answer vocabulary, clean-answer table, tokenizer) turns on the reference's
+    answer-string scoring (file sources only): misaligned samples (``answers.aligned``) are skipped before bucketing and
+    counted in ``skipped_misaligned`` -- the reference's ALBEF ``evaluate`` instead ends its whole run at the first one
+    (``return dict()``, adv_attack.py:422-427), this sweep skips and counts; the victim reads the adversarial question as
+    the reference's ``adv_text`` string, re-tokenised (``answers.victim_input``); the success bit is
+    ``vocab[after] != table[qid]`` and no clean victim call is made; the rate is over the scored samples of all ranks.
+    Adds ``skipped_misaligned``, ``scoring_seconds`` (host time of the string round trip), ``adv_text_str``
+    (``{qid: adversarial question string}``) and ``success`` (``{qid: 0/1}``) to the result.  Without it nothing changes."""
     if source is None:
         from .dataset import SyntheticPairs
         source = SyntheticPairs(n_samples, text_len, image_size, flavor, seed=seed, joint=joint, max_words=max_words,
@@ -100,8 +110,22 @@ def run_sweep(flavor, white, black, adapters, n_samples, batch, image_size, text
     ids, masks, att, tasks = source.ids, source.masks, source.attackable, source.tasks
     text_len = ids.shape[1]
     dual = torch.tensor([t.old_alg == 0 for t in tasks], dtype=torch.bool)
-    mine = shard_indices(n_samples, rank, world)
+    # the samples that are scored, in source order; the ledger and the row gather address them by position in this list
+    order = list(range(n_samples))
+    if scoring is not None:
+        if not hasattr(source, "annotation"):
+            raise ValueError("answer-string scoring needs file inputs (attack/dataset.py::VqaFilePairs)")
+        n_vocab = int(getattr(black.cfg, "n_answers", len(scoring.vocab)))
+        if n_vocab > len(scoring.vocab):
+            raise ValueError("the victim predicts {} answers, the answer vocabulary has {}".format(n_vocab,
+                                                                                              len(scoring.vocab)))
+        order = [i for i in range(n_samples) if scoring.is_aligned(source.annotation(i))]
+        table_index = scoring.table_index([source.qids[i] for i in order])      # host, once; -1 = not in the vocabulary
+    position = {i: p for p, i in enumerate(order)}
+    n_scored = len(order)
+    mine = [order[j] for j in shard_indices(n_scored, rank, world)]
     device = torch.device(device)
+    score_dt = 0.0
     if attack is None:
         attack = BatchedVQAttack(adapters, flavor, white.embedding_tables(), config or AttackConfig(),
                                  banned_ids=banned_ids)
@@ -139,7 +163,7 @@ def run_sweep(flavor, white, black, adapters, n_samples, batch, image_size, text
         if at + 1 < len(plan):
             source.prefetch(plan[at + 1][1])          # the next batch's files are read while this one is attacked
         tid, tmask, tatt = ids[index].to(device), masks[index].to(device), att[index].to(device)
-        clean = black.vqa_answer(images, tid, tmask)
+        clean = black.vqa_answer(images, tid, tmask) if scoring is None else None
         if key == -2:
             batch_tasks = [tasks[q] for q in index]
             res = attack.attack_mixed(images, tid, tmask, tatt, mlm_logits_fn=mlm_logits_fn,
@@ -149,15 +173,27 @@ def run_sweep(flavor, white, black, adapters, n_samples, batch, image_size, text
                                       tasks=[tasks[q] for q in index])
         else:
             res = attack.attack_batch(images, tid, tmask, tatt, mlm_logits_fn=mlm_logits_fn)
-        after = black.vqa_answer(res.adv_images, res.adv_text_ids, tmask)
-        ledger.record(after != clean, sample_ids=index)
+        pos = [position[i] for i in index]
+        if scoring is None:
+            after = black.vqa_answer(res.adv_images, res.adv_text_ids, tmask)
+            ledger.record(after != clean, sample_ids=pos)
+        else:
+            # the reference's victim reads the adversarial STRING: rows -> adv_text -> the victim's own tokenisation
+            ts = time.perf_counter()
+            strings = [scoring.adv_string(source, i, r) for i, r in zip(index, res.adv_text_ids[:, :text_len].tolist())]
+            rows = [victim_input(flavor, s, scoring.tokenizer, text_len) for s in strings]
+            vid = torch.tensor([r[0] for r in rows], dtype=torch.int64).to(device)
+            vmask = torch.tensor([r[1] for r in rows], dtype=torch.int64).to(device)
+            score_dt += time.perf_counter() - ts
+            after = black.vqa_answer(res.adv_images, vid, vmask)
+            ledger.record(scoring.decide(after, table_index[pos]), sample_ids=pos)
         # per-sample gradient steps, the same quantity on the bucketed and on the mixed path
         steps += res.sample_steps or res.gradient_steps * (1 if key == -2 else len(index))
         batch_global_steps.append(int(res.global_steps or (res.gradient_steps if key != -2 else 0)))
         if key != -2:
             assert res.gradient_steps == gradient_steps(n_words, attack.cfg.budget)
         adv_rows.append(res.adv_text_ids[:, :text_len])        # stays on the device until the sweep's one gather
-        adv_index += index
+        adv_index += pos
         if writer is not None:
             writer.write(res.adv_images, [source.qids[i] for i in index])
         done += len(index)
@@ -177,20 +213,31 @@ def run_sweep(flavor, white, black, adapters, n_samples, batch, image_size, text
         writer_dt = time.perf_counter() - tw
     dt = time.perf_counter() - t0
     t1 = time.perf_counter()
-    asr = ledger.all_gather_rate(n_samples)
+    if scoring is None:
+        asr = ledger.all_gather_rate(n_scored)
+    else:                                                  # the same one gather, keeping the per-sample bits
+        bits, bit_ids = ledger.all_gather_bits(n_scored)
+        asr = float(bits.float().mean().item()) if bits.numel() else None
     # the sweep's second output: every sample's adversarial question on every rank (rank 0 writes the json the reference
     # writes at the end, adv_attack.py:734-735 / vlmo_module.py:2095-2097) -- one small all-gather of (index, ids) rows
     rows = torch.cat(adv_rows) if adv_rows else torch.zeros(0, text_len, dtype=torch.int64, device=device)
-    all_q, all_rows = ledger.all_gather_rows(adv_index, rows, n_samples)
+    all_q, all_rows = ledger.all_gather_rows(adv_index, rows, n_scored)
     all_q, all_rows = all_q.cpu(), all_rows.cpu()          # drains the gathers
     gather_dt = time.perf_counter() - t1
-    adv_text = {str(source.qids[q]): row for q, row in zip(all_q.tolist(), all_rows.tolist())}
+    adv_text = {str(source.qids[order[q]]): row for q, row in zip(all_q.tolist(), all_rows.tolist())}
+    extra = {}
+    if scoring is not None:
+        extra = dict(skipped_misaligned=n_samples - n_scored, scoring_seconds=score_dt,
+                     adv_text_str={str(source.qids[order[q]]): scoring.adv_string(source, order[q], row)
+                                   for q, row in zip(all_q.tolist(), all_rows.tolist())},
+                     success={str(source.qids[order[q]]): int(b)
+                              for q, b in zip([] if bit_ids is None else bit_ids.tolist(), bits.tolist())})
     input_dt, blocked_dt = float(getattr(source, "seconds_images", 0.0)), float(getattr(source, "seconds_blocked", 0.0))
     source.close()
-    return dict(asr=asr, n_total=n_samples, n_local=len(mine), seconds=dt,
+    return dict(asr=asr, n_total=n_scored, n_local=len(mine), seconds=dt,
                 examples_per_sec_local=len(mine) / dt if dt > 0 else None, gradient_steps=steps, adv_text=adv_text,
                 n_batches=n_batches, mean_batch=(len(mine) / n_batches if n_batches else 0.0),
                 global_steps=sum(batch_global_steps), batch_global_steps=batch_global_steps, gather_seconds=gather_dt,
                 n_dual_local=int(sum(bool(dual[i]) for i in mine)), input_seconds=input_dt,
                 input_blocked_seconds=blocked_dt, writer_seconds=writer_dt, skipped=int(getattr(source, "skipped", 0)),
-                collectives=ledger.collectives)
+                collectives=ledger.collectives, **extra)

@@ -10,7 +10,17 @@ number = id); ``tests/test_file_inputs.py`` compares it with the ``tokenizers`` 
 Only what the attack reads is provided: the attack works on WORDS (whitespace-separated pieces of the question,
 ``Adv_attack._tokenize`` adv_attack.py:141-154) and their piece ids.
 """
+import re
 import unicodedata
+
+SPECIAL_TOKENS = ("[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]")
+_SPECIAL_SPLIT = re.compile("(" + "|".join(re.escape(t) for t in SPECIAL_TOKENS) + ")")
+
+
+def convert_tokens_to_string(tokens):
+    """``BertTokenizer.convert_tokens_to_string`` (ALBEF ``models/tokenization_bert.py:240-243``; the transformers
+    library's is the same): join at spaces, glue ``##`` pieces, strip."""
+    return " ".join(tokens).replace(" ##", "").strip()
 
 
 def _is_punctuation(ch):
@@ -97,7 +107,15 @@ class WordPiece:
         return out
 
     def tokenize(self, text):
-        return [p for tok in self.basic(text) for p in self.pieces(tok)]
+        """Word pieces of ``text``.  Special tokens anywhere in the text stay one token, as the library tokenizers'
+        no-split tokens do (``'yes[SEP]'`` -> ``yes``, ``[SEP]``: the reference's answer rows, adv_attack.py:396)."""
+        out = []
+        for part in _SPECIAL_SPLIT.split(text):
+            if part in SPECIAL_TOKENS:
+                out.append(part)
+            elif part:
+                out += [p for tok in self.basic(part) for p in self.pieces(tok)]
+        return out
 
     def word_ids(self, word):
         """Piece ids of one whitespace-separated word (``tokenizer.tokenize(word)`` in ``_tokenize``)."""

@@ -226,9 +226,9 @@ class FrozenAlbef(nn.Module):
         return checkpoint.load_albef(self, state_dict, strict=strict)
 
     def set_answer_list(self, answer_ids):
-        """Replace the synthetic answer list by tokenised answers (n, L) int64: ``[BOS] pieces [SEP] pad...`` rows as
-        ``tokenizer(answer_list, padding='longest')`` with the first id overwritten by ``bos`` produces them
-        (adv_attack.py:407-409, model_vqa.py:149-155)."""
+        """Replace the synthetic answer list by tokenised answers (n, L) int64; decoding starts from ``answer_ids[0, 0]``
+        (model_vqa.py:149-155).  The reference's rows are ``tokenizer(answer + '[SEP]', padding='longest')`` of ALBEF's
+        tokenizer, ``[CLS] pieces [SEP] pad...`` (adv_attack.py:396-397): ``attack.answers.albef_answer_ids``."""
         if not self.has_vqa:
             raise RuntimeError("this FrozenAlbef was built without the VQA decoder")
         self.answer_ids = answer_ids.to(self.answer_ids.device, torch.long).contiguous()
