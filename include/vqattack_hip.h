@@ -209,6 +209,11 @@ int vqa_sum_partials(const float* partial, int count, float* dst, int accumulate
  * A label that is neither ignore_index nor in [0, V) makes the loss NaN and ORs VQA_FLAG_BAD_LABEL into *flag
  * (flag nullable); torch raises a device assert for it, it is never silently ignored.
  * exp() is the hardware exponential (v_exp_f32, ~2 ulp); parity with torch is stated as 1e-4 relative in the tests.
+ * The row's logsumexp - logits[r, t] is formed as  log c + log1p(s / c) - (logits[r, t] - m)  with m the row max, c the
+ * number of elements equal to it and s the sum of exp(x - m) over the others: a row whose label is predicted with p ~ 1
+ * keeps a loss down to 1e-8 accurate to 4e-6 relative, whatever common offset the logits carry (asserted in
+ * tests/test_loss_fp64.py).  -inf logits (a masked vocabulary) contribute 0 and get a zero gradient; a row that is
+ * entirely -inf, or that holds a NaN anywhere, has a NaN loss, as in torch.
  * Replaces F.cross_entropy(out[0].view(-1, 30522), y[0][...].view(-1), ignore_index=-100), its K-fold repetition for
  * 3-d labels and the autograd backward: A-ch/attacks/fast_gradient_method.py:131-142, V-ch/...:115-126.
  * A row whose K labels are all ignore_index -- every position but the [MASK]-ed answer pieces in the reference's

@@ -215,6 +215,8 @@ def _cos_ref(a, b, mask=None):
 @pytest.mark.parametrize("rows0,rows1,d", [(13, 617, 768), (3, 17, 16), (25, 40, 1024), (1, 13, 768), (2, 3, 2048),
                                           (2, 5, 260)], ids=str)
 def test_neg_cos_rows(rows0, rows1, d):
+    """Independent unit-Gaussian rows against torch fp32; the attack's regime (a = b + small, outlier channels, rows at
+    cos_eps) is tested against float64 in tests/test_loss_fp64.py."""
     ops = _ops()
     r = np.random.RandomState(23)
     a = torch.from_numpy(r.standard_normal((rows0, rows1, d)).astype(np.float32))

@@ -1,6 +1,8 @@
 """CPU checks that the trained-statistics inputs of ``tests/trained_stats.py`` do what they are for: the attention cases
 drive the forward kernel's lazy-max rescale, mask whole key tiles and give the loop split a masked part and a part far
 below the row max; the exact GEMM operands split into exactly the planes they were built from."""
+import math
+
 import numpy as np
 import pytest
 import torch
@@ -126,3 +128,146 @@ def test_exact_gemm_operands_split_into_their_planes_and_sum_exactly(pa, pb):
     # a dropped product (a1b2, a2b1, a2b2) never contributes
     for i, j in ((1, 2), (2, 1), (2, 2)):
         assert not (a_planes[i] @ b_planes[j]).any()
+
+
+# ------------------------------------------------------------------------- loss / text-scoring inputs (fp64 only)
+@pytest.mark.parametrize("kind", ts.PAIR_KINDS)
+@pytest.mark.parametrize("delta", ts.DELTAS)
+def test_feature_pairs_are_as_far_apart_as_they_claim(kind, delta):
+    a, b = ts.feature_pair(kind, delta, 3, 40, 768)
+    if delta == 0.0:
+        assert torch.equal(a, b)
+        return
+    rel = (a.double() - b.double()).norm(dim=-1) / b.double().norm(dim=-1)
+    assert float(rel.min()) >= delta / 2 and float(rel.max()) <= delta * 2, (float(rel.min()), float(rel.max()))
+    if delta <= 1e-3:
+        val, _ = ts.neg_cos64(a.double(), b.double())
+        assert float((-val).min()) > 1.0 - 1e-5
+    if kind != "plain":
+        assert float(b[..., 7].abs().median() / b[..., 8].abs().median()) > 100.0
+    if kind == "scaled":
+        norms = b.double().norm(dim=-1) / (300.0 * 2 ** 0.5)
+        assert float(norms.min()) < 1e-2 and float(norms.max()) > 1e2
+
+
+def test_degenerate_rows_lie_on_the_intended_side_of_cos_eps():
+    a, b = ts.feature_pair("degenerate", 1e-3, 3, 40, 768)
+    na, nb = a.double().view(-1, 768).norm(dim=-1), b.double().view(-1, 768).norm(dim=-1)
+    rows = ts.DEGENERATE_ROWS
+    for r in rows["a_zero"] + rows["both_zero"]:
+        assert float(na[r]) == 0.0
+    for r in rows["b_zero"] + rows["both_zero"]:
+        assert float(nb[r]) == 0.0
+    for r in rows["a_tiny"]:
+        assert 0.0 < float(na[r]) < 0.2 * ts.COS_EPS and float(nb[r]) > 1.0
+    for r in rows["b_tiny"]:
+        assert 0.0 < float(nb[r]) < 0.2 * ts.COS_EPS and float(na[r]) > 1.0
+    for r in rows["a_above"]:
+        assert ts.COS_EPS * 2 < float(na[r]) < ts.COS_EPS * 4
+    for r in rows["b_above"]:
+        assert ts.COS_EPS * 2 < float(nb[r]) < ts.COS_EPS * 4
+    val, grad = ts.neg_cos64(a.double(), b.double())
+    assert bool(torch.isfinite(val).all()) and bool(torch.isfinite(grad).all())
+    # the closed form is what autograd gives for torch's own float64 cosine on every row -- except 0 < |a| <= eps, where
+    # torch clamps the norm outside autograd and lets a gradient through it (off by |a| / eps = 10 % here); the kernel
+    # follows the header: nothing flows through a clamped norm
+    x = a.double().clone().requires_grad_(True)
+    c = torch.nn.CosineSimilarity(dim=-1, eps=ts.COS_EPS)(x, b.double())
+    (gx,) = torch.autograd.grad((-c).sum(), x)
+    scale = grad.abs().amax(-1).clamp_min(1e-300)
+    rel = ((gx - grad).abs().amax(-1) / scale).view(-1)
+    clamped = torch.zeros_like(rel, dtype=torch.bool)
+    clamped[list(rows["a_tiny"])] = True
+    assert float(rel[~clamped].max()) < 1e-9
+    assert 0.05 < float(rel[clamped].min()) and float(rel[clamped].max()) < 0.2
+    assert float((-c.detach() - val).abs().max()) < 1e-12
+
+
+@pytest.mark.parametrize("kind", list(ts.MLM_KINDS))
+@pytest.mark.parametrize("v,k", [(30522, 1), (30522, 3), (33334, 8)])
+def test_mlm_rows_are_peaked_and_their_labels_sit_on_the_edge_lanes(kind, v, k):
+    rows = 48
+    x, labels, margin = ts.mlm_logits(kind, rows, v, k)
+    live = ts.live_rows(rows)
+    assert len(live) * 3 <= rows + 2 and bool((labels[:, [r for r in range(rows) if r not in live]] == ts.IGNORE).all())
+    assert sorted(set(margin[live].tolist())) == list(range(len(ts.MARGINS)))
+    row64, _ = ts.ce_rows_torch(x.double(), labels, 0)
+    w0 = 1.0 / len(live)
+    for r in live:
+        t = int(labels[0, r])
+        assert float(x[r, t]) == float(x[r].max()) and math.isfinite(float(x[r, t]))
+        only0 = bool((labels[1:, r] == ts.IGNORE).all()) if k > 1 else True
+        if ts.MARGINS[int(margin[r])] >= 15.0 and only0:
+            assert 0.0 < float(row64[r]) / w0 < 1e-4, (r, float(row64[r]))
+    if k > 1:
+        r = live[1]
+        assert int(labels[1, r]) == int(labels[0, r])
+        assert any(int(labels[kk, q]) not in (ts.IGNORE, int(labels[0, q])) for kk in range(1, k) for q in live)
+    # head / tail lanes of the register kernel (row_geom): at V = 30522 odd rows have a two-element head, even rows a
+    # two-element tail; the forced positions land on them
+    on_head = on_tail = body = 0
+    for r in live:
+        head, nquad, tail0 = ts.row_geom(r, v)
+        assert head == (2 if r % 2 else 0) and v - tail0 == (0 if r % 2 else 2)
+        t = int(labels[0, r])
+        on_head += t < head
+        on_tail += t >= tail0
+        body += head <= t < tail0
+    assert on_head >= 4 and on_tail >= 4 and body >= 4
+    if kind == "masked":
+        for r in live:
+            # every lane's first element of the streaming fallback (256 lanes, pairs or single floats) is -inf, except
+            # where a label sits; a third of the row is masked overall; no label is masked
+            first = x[r, :2 * ts.CE_BLOCK]
+            assert int(torch.isinf(first).sum()) >= 2 * ts.CE_BLOCK - 1
+            assert bool(torch.isinf(x[r, :ts.MASKED_HEAD]).sum() >= ts.MASKED_HEAD - k)
+            assert 0.25 < float(torch.isinf(x[r]).float().mean()) < 0.40
+            for kk in range(k):
+                if int(labels[kk, r]) != ts.IGNORE:
+                    assert math.isfinite(float(x[r, int(labels[kk, r])]))
+        assert bool(torch.isfinite(row64[live]).all())
+
+
+@pytest.mark.parametrize("d", [768, 1024])
+def test_text_tables_near_synonyms_and_the_pair_cap(d):
+    """Near-synonym candidates move the embedding by < 10 % of its length, and at a gap of 1e-5 fewer than 2 % of the
+    candidate pairs of a (sample, position) are too close to rank (float64 scores alone)."""
+    tabs = ts.text_tables(d)
+    ori, cand, syn = ts.text_candidates(tabs)
+    assert cand.shape[0] == ts.TEXT_SAMPLES * ts.TEXT_POSITIONS * ts.TEXT_CANDS
+    pos = torch.arange(ts.TEXT_LEN)[None].expand_as(ori)
+    e_ori = ts.bert_embed(tabs, ori, pos, torch.float32)
+    s64, rel = ts.dir_sim(tabs, e_ori, cand, torch.float64)
+    assert int(syn.sum()) == ts.TEXT_SAMPLES * ts.TEXT_POSITIONS
+    assert float(rel[syn].max()) < 0.1 and float(rel[~syn].min()) > 0.5
+    assert float(tabs["gamma"].abs().max()) == 8.0
+    gabs = tabs["grad"].abs()
+    assert 1e-8 < float(gabs.median()) < 1e-6 and float(gabs.max()) > 50.0 * float(gabs.median())
+    left, _ = ts.left_out_pairs(s64, 1e-5, ts.TEXT_CANDS)
+    assert left <= 0.02, left
+
+
+@pytest.mark.parametrize("e", [64, 512])
+def test_greedy_cases_are_decidable_and_hold_a_close_call(e):
+    case = ts.greedy_case(e)
+    assert case["ori"].shape == (ts.GREEDY_B, ts.GREEDY_L)
+    for thr in ts.GREEDY_THRESHOLDS:
+        new_id, rank, smallest, risen = ts.greedy_accept64(case, thr)
+        left = float((smallest <= ts.GREEDY_MARGIN).mean())
+        assert left <= 0.05, (thr, left)
+        # sample 0: accepted once, then a later candidate misses the risen threshold by 1e-5 .. 1e-3
+        assert int((new_id[0] >= 0).sum()) >= 1
+        assert risen[0] and ts.GREEDY_MARGIN < min(risen[0]) < 1e-3, risen[0]
+        assert smallest[0] > ts.GREEDY_MARGIN
+    # the exact-tie candidates are reached after an acceptance at the lower thresholds
+    new_id, _, _, _ = ts.greedy_accept64(case, 0.5)
+    assert sum(int((new_id[s] >= 0).sum()) >= 1 for s in range(1, 9)) >= 4
+    assert float(np.mean([(new_id[s] >= 0).sum() for s in range(ts.GREEDY_B)])) >= 1.0
+
+
+def test_image_gradients_are_small_and_heavy_tailed():
+    g = ts.image_grads((4, 3, 96, 96))
+    nz = g[g != 0].abs()
+    assert 0.005 < float((g == 0).float().mean()) < 0.02
+    assert 1e-7 < float(nz.median()) < 1e-6 and float(nz.max()) > 1e-5 and float(nz.min()) < 1e-8
+    assert float(g.double().flatten(1).norm(dim=1).min()) > 1e-6

@@ -207,3 +207,320 @@ def exact_operands(pa, pb, m, n, k, seed=0):
     a_planes = np.where(keep[None], a_planes, 0.0)
     b_val, b_planes = _planes_value((k, n), pb, rng)
     return a_val.astype(np.float32), b_val.astype(np.float32), a_planes, b_planes
+
+
+# ------------------------------------------------------------------------------------------------ feature-loss pairs
+# Inside an attack the two operands of the cosine loss are the adversarial and the clean feature map of ONE model:
+# a = b + small.  The gradient  kb b + ka a  is then the difference of two nearly equal vectors.
+COS_EPS = 1e-6                                     # nn.CosineSimilarity(eps=1e-6), ops._COS_EPS
+PAIR_KINDS = ("plain", "outliers", "scaled")
+DELTAS = (0.0, 1e-5, 1e-3, 1e-1, 1.0)
+TINY_NORM, ABOVE_NORM = 1e-7, 3e-6                 # row norms below / just above COS_EPS
+# flat row indices of the ``degenerate`` kind (needs >= 13 rows)
+DEGENERATE_ROWS = dict(a_zero=(0, 1), b_zero=(2, 3), both_zero=(4,), a_tiny=(5, 6), b_tiny=(7, 8), a_above=(9, 10),
+                       b_above=(11, 12))
+
+
+def feature_pair(kind, delta, rows0, rows1, d, seed=0):
+    """(a, b) fp32 (rows0, rows1, D) on the CPU.  ``b``: unit Gaussian; ``outliers``: two channels at x300 (massive
+    activations); ``scaled``: the outlier rows times a per-row scale drawn log-uniformly from 1e-3 .. 1e3.
+    ``a = fp32(b64 + delta * n)`` with n Gaussian of the row's own rms, so |a - b| / |b| ~ delta; delta = 0: a is b, bit
+    for bit.  ``degenerate``: plain rows, the first 13 replaced per DEGENERATE_ROWS (exact zeros, norms 1e-7 and 3e-6)."""
+    g = torch.Generator().manual_seed(seed * 1000 + d)
+    b = torch.randn(rows0, rows1, d, generator=g)
+    n = torch.randn(rows0, rows1, d, generator=g)
+    scale = torch.exp(torch.empty(rows0, rows1, 1).uniform_(math.log(1e-3), math.log(1e3), generator=g))
+    if kind in ("outliers", "scaled"):
+        b[..., [7, d // 2 + 3]] *= 300.0
+    if kind == "scaled":
+        b = b * scale
+    elif kind not in ("plain", "outliers", "degenerate"):
+        raise ValueError(kind)
+    b64 = b.double()
+    if delta == 0.0:
+        a = b.clone()
+    else:
+        rms = b64.norm(dim=-1, keepdim=True) / math.sqrt(d)
+        a = (b64 + delta * rms * n.double()).float()
+    if kind == "degenerate":
+        af, bf = a.view(-1, d), b.view(-1, d)
+        for name, rows in DEGENERATE_ROWS.items():
+            for r in rows:
+                for t, tag in ((af, "a"), (bf, "b")):
+                    if name.startswith(tag) or name == "both_zero":
+                        if name.endswith("zero"):
+                            t[r] = 0.0
+                        else:
+                            want = TINY_NORM if name.endswith("tiny") else ABOVE_NORM
+                            t[r] = (t[r].double() * (want / t[r].double().norm())).float()
+    return a, b
+
+
+def neg_cos64(a, b, w=None, eps=COS_EPS):
+    """The header's formula in the dtype of ``a`` (pass float64): per-row -c = -(a / max(|a|, eps)) . (b / max(|b|, eps))
+    and d(-c)/da = -( b / (dna dnb) - [|a| > eps] c a / |a|^2 ) (nothing flows through a clamped norm), times the row
+    weight ``w``.  Returns (row values, gradient)."""
+    na, nb = a.norm(dim=-1, keepdim=True), b.norm(dim=-1, keepdim=True)
+    inv = 1.0 / (na.clamp_min(eps) * nb.clamp_min(eps))
+    c = (a * b).sum(-1, keepdim=True) * inv
+    ka = torch.where(na > eps, c / (na * na).clamp_min(1e-300), torch.zeros_like(c))
+    grad = -(b * inv - ka * a)
+    val = -c.squeeze(-1)
+    if w is not None:
+        val, grad = val * w, grad * w.unsqueeze(-1)
+    return val, grad
+
+
+# ---------------------------------------------------------------------------------------------------- MLM logits
+# A trained MLM head predicts the masked answer piece with p ~ 1: the row's loss is 1e-2 .. 1e-7.
+MARGINS = (0.0, 5.0, 10.0, 15.0, 20.0, 30.0)
+MLM_KINDS = {"off0": 0.0, "off+50": 50.0, "off-50": -50.0, "masked": 0.0}
+IGNORE = -100
+MASKED_HEAD = 1024                                 # leading entries of a ``masked`` row that are all -inf
+CE_BLOCK = 256                                     # threads of the streaming fallback (csrc/ce.hip, kBlock)
+
+
+def live_rows(rows):
+    """Every third row is live (>= 2/3 dead); consecutive live rows alternate parity."""
+    return list(range(1, rows, 3))
+
+
+def forced_position(j, v):
+    """Label position of the j-th live row: 0 / 1 on odd rows and V-1 / V-2 on even rows (the register kernel's head and
+    tail lanes at V = 30522), the row's argmax (None), a random one (-1)."""
+    return (0, v - 1, 1, v - 2, None, -1)[j % 6]
+
+
+def margin_index(j, seed):
+    return (j + j // 6 + seed) % len(MARGINS)
+
+
+def row_geom(r, v):
+    """``row_geom`` of csrc/ce.hip: (head, nquad, tail0); lanes t < head own x[t], lanes 8 + t own x[tail0 + t]."""
+    head = (4 - (r * v) % 4) % 4
+    nquad = (v - head) // 4
+    return head, nquad, head + 4 * nquad
+
+
+def mlm_logits(kind, rows, v, k, seed=0):
+    """(logits fp32 (rows, V), labels int64 (K, rows), margin index per row (-1 dead)) on the CPU.  ``2 randn + offset``;
+    label set 0 of the j-th live row sits at ``forced_position`` and is lifted to row max + MARGINS[margin_index];
+    sets 1 .. K-1 are live on every fourth live row at random positions, and on the second live row set 1 repeats set 0's
+    label.  ``masked``: a random 30 % of each row and its first MASKED_HEAD entries are -inf, the labels are not."""
+    g = torch.Generator().manual_seed(seed * 7919 + v + 31 * k + list(MLM_KINDS).index(kind))
+    x = 2.0 * torch.randn(rows, v, generator=g) + MLM_KINDS[kind]
+    labels = torch.full((k, rows), IGNORE, dtype=torch.int64)
+    margin = torch.full((rows,), -1, dtype=torch.int64)
+    if kind == "masked":
+        x[torch.rand(rows, v, generator=g) < 0.3] = float("-inf")
+        x[:, :MASKED_HEAD] = float("-inf")
+    for j, r in enumerate(live_rows(rows)):
+        pos = forced_position(j, v)
+        if pos is None:
+            pos = int(x[r].argmax())
+        elif pos < 0:
+            pos = int(torch.randint(2, v - 2, (1,), generator=g))
+        margin[r] = margin_index(j, seed)
+        x[r, pos] = float(x[r].max()) + MARGINS[int(margin[r])]
+        labels[0, r] = pos
+        for kk in range(1, k):
+            if (j + kk) % 4 == 0:
+                other = int(torch.randint(MASKED_HEAD, v, (1,), generator=g))
+                if kind == "masked" and not math.isfinite(float(x[r, other])):
+                    x[r, other] = MLM_KINDS[kind]
+                labels[kk, r] = other
+    if k > 1 and len(live_rows(rows)) > 1:
+        r = live_rows(rows)[1]
+        labels[1, r] = labels[0, r]
+    return x, labels, margin
+
+
+def ce_weights(labels, rows_per_sample, dtype):
+    """w[k, r] = 1 / #{valid labels of set k in r's group} on live entries, 0 elsewhere (``vqa_ce_rows``'s mean)."""
+    k, rows = labels.shape
+    rpg = rows if rows_per_sample in (0, None) else rows_per_sample
+    groups = -(-rows // rpg)
+    valid = (labels != IGNORE)
+    pad = groups * rpg - rows
+    vp = torch.nn.functional.pad(valid, (0, pad)).view(k, groups, rpg)
+    count = vp.sum(-1, keepdim=True).expand(k, groups, rpg).reshape(k, groups * rpg)[:, :rows].to(dtype)
+    return torch.where(valid, 1.0 / count.clamp_min(1.0), torch.zeros((), dtype=dtype, device=labels.device))
+
+
+def ce_rows_torch(logits, labels, rows_per_sample):
+    """(row losses, gradient) of sum_k mean-CE in the dtype of ``logits`` through torch's own cross_entropy + autograd."""
+    x = logits.clone().requires_grad_(True)
+    w = ce_weights(labels, rows_per_sample, logits.dtype)
+    per = torch.stack([torch.nn.functional.cross_entropy(x, lab, ignore_index=IGNORE, reduction="none") for lab in labels])
+    row = (per * w).sum(0)
+    (grad,) = torch.autograd.grad(row.sum(), x)
+    return row.detach(), grad
+
+
+# --------------------------------------------------------------------------------------------------- text tables
+SYN_STEP = 1e-3                                    # near-synonym: word[j] = word[i] + SYN_STEP * randn
+TEXT_SAMPLES, TEXT_POSITIONS, TEXT_CANDS = 3, 4, 48
+TEXT_LEN = 12
+
+
+def text_tables(d, v=600, seed=0):
+    """BERT-like embedding tables on the CPU: word rows 0.05 randn with two channels at x20, ids [v/2, v) near-synonyms of
+    ids [0, v/2) (word[i + v/2] = word[i] + 1e-3 randn), gamma with one x8 entry; ``grad`` rows (TEXT_SAMPLES, TEXT_LEN, D)
+    at 1e-7 with a heavy tail."""
+    g = torch.Generator().manual_seed(seed * 13 + d)
+    half = v // 2
+    word = torch.randn(v, d, generator=g) * 0.05
+    word[:, [5, d // 3]] *= 20.0
+    word[half:] = (word[:half].double() + SYN_STEP * torch.randn(half, d, generator=g).double()).float()
+    pos = torch.randn(TEXT_LEN, d, generator=g) * 0.02
+    type_emb = torch.randn(2, d, generator=g) * 0.01
+    gamma = 1.0 + 0.3 * torch.randn(d, generator=g)
+    gamma[11] = 8.0
+    beta = 0.3 * torch.randn(d, generator=g)
+    grad = 1e-7 * torch.randn(TEXT_SAMPLES, TEXT_LEN, d, generator=g) * torch.exp(
+        torch.randn(TEXT_SAMPLES, TEXT_LEN, d, generator=g))
+    return dict(word=word, pos=pos, type_emb=type_emb, gamma=gamma, beta=beta, ln_eps=1e-12, grad=grad)
+
+
+def text_candidates(tabs, seed=0):
+    """(ori ids (S, L) int64, cand int32 (n, 4), synonym flag (n,)): TEXT_POSITIONS positions per sample with TEXT_CANDS
+    candidates each; the first is a near-synonym of the original word, the next two of each other.  Every other candidate
+    reads a gradient row that is NOT its position (the kernel takes both from the row: columns 1 and 2)."""
+    v = tabs["word"].shape[0]
+    half = v // 2
+    g = torch.Generator().manual_seed(seed + 77)
+    ori = torch.randint(1, half, (TEXT_SAMPLES, TEXT_LEN), generator=g)
+    rows, syn = [], []
+    for s in range(TEXT_SAMPLES):
+        for p in (1, 3, 6, 10)[:TEXT_POSITIONS]:
+            o = int(ori[s, p])
+            other = int(torch.randint(1, half, (1,), generator=g))
+            ids = [o + half, other, other + half] + [int(t) for t in torch.randperm(v - 1, generator=g)[:TEXT_CANDS] + 1]
+            ids = [t for i, t in enumerate(ids) if t != o and t not in ids[:i]][:TEXT_CANDS]
+            for i, t in enumerate(ids):
+                rows.append((s, p, (p + 1 + i % 3) % TEXT_LEN if i % 2 else p, t))
+                syn.append(i == 0)
+    return ori, torch.tensor(rows, dtype=torch.int32), torch.tensor(syn)
+
+
+def bert_embed(tabs, ids, positions, dtype):
+    """LayerNorm(word[id] + type[0] + pos[p]) in ``dtype`` (tables may live on any device)."""
+    e = (tabs["word"][ids].to(dtype) + tabs["type_emb"][0].to(dtype)) + tabs["pos"][positions].to(dtype)
+    return torch.nn.functional.layer_norm(e, e.shape[-1:], tabs["gamma"].to(dtype), tabs["beta"].to(dtype),
+                                          tabs["ln_eps"])
+
+
+def dir_sim(tabs, e_ori, cand, dtype):
+    """The header's formula of ``vqa_cand_dir_sim`` in ``dtype`` with the GIVEN fp32 ``e_ori``: scores (n,) and |d| / |e|."""
+    s, p, k, v = (cand[:, i].long() for i in range(4))
+    e = bert_embed(tabs, v, p, dtype)
+    dvec = e - e_ori[s, p].to(dtype)
+    gvec = tabs["grad"][s, k].to(dtype)
+    nd, ng = dvec.norm(dim=-1, keepdim=True), gvec.norm(dim=-1, keepdim=True)
+    u, w = dvec / nd.clamp_min(1e-12), gvec / ng.clamp_min(1e-12)
+    score = (u * w).sum(-1) / (u.norm(dim=-1).clamp_min(1e-6) * w.norm(dim=-1).clamp_min(1e-6))
+    return score, (nd.squeeze(-1) / e.norm(dim=-1))
+
+
+def left_out_pairs(s64, gap, per_group):
+    """Share of candidate pairs (within each group of ``per_group`` consecutive scores) closer than ``gap``, and the mask
+    (groups, n, n) of the pairs that remain."""
+    sc = s64.view(-1, per_group)
+    diff = (sc[:, :, None] - sc[:, None, :]).abs()
+    upper = torch.triu(torch.ones(per_group, per_group, dtype=torch.bool, device=s64.device), 1)[None]
+    decided = (diff > gap) & upper
+    return 1.0 - float(decided.sum()) / float(upper.sum() * sc.shape[0]), decided
+
+
+# ------------------------------------------------------------------------------------------------ greedy acceptance
+GREEDY_B, GREEDY_L, GREEDY_V = 64, 24, 2000
+GREEDY_THRESHOLDS = (0.95, 0.8, 0.5)
+GREEDY_MARGIN = 1e-5
+CLOSE_STEP = 0.1                                   # sample 0: candidates are table rows 0.1 randn away from the original
+
+
+def greedy_case(e, seed=0):
+    """dict(table (V, E) fp32, ori (B, L) int64 with padding, cand int32 (n, 4), scores fp32 (n,)) on the CPU.  Five
+    positions x three candidates per sample.  Sample 0's candidates are near-synonyms (CLOSE_STEP) of its own words: the
+    first one is accepted, the threshold rises to ~1 - 1e-4, and the later ones miss it by 1e-5 .. 1e-3.  Samples 1 .. 8
+    carry a candidate that proposes the word already there, visited after an acceptance: an exact tie with the risen
+    threshold, which `>` rejects."""
+    g = torch.Generator().manual_seed(seed * 17 + e)
+    table = torch.randn(GREEDY_V, e, generator=g)
+    ori = torch.randint(1, GREEDY_V // 2, (GREEDY_B, GREEDY_L), generator=g)
+    for s in range(GREEDY_B):
+        ori[s, 10 + s % 14:] = 0                                 # 10 .. 23 tokens, padded with id 0
+    rows, scores = [], []
+    for s in range(GREEDY_B):
+        n_tok = 10 + s % 14
+        positions = torch.randperm(n_tok, generator=g)[:5].tolist()
+        for i, p in enumerate(positions):
+            for c in range(3):
+                rows.append((s, p, p, int(torch.randint(GREEDY_V // 2, GREEDY_V, (1,), generator=g))))
+                scores.append(float(torch.rand(1, generator=g)) * 0.5)
+        if 1 <= s <= 8:                                           # the no-op candidate: lowest score, visited last
+            free = [p for p in range(n_tok) if p not in positions][0]
+            rows.append((s, free, free, int(ori[s, free])))
+            scores.append(-1.0)
+    # sample 0: five near-synonym candidates, best score first
+    rows0 = [i for i, r in enumerate(rows) if r[0] == 0]
+    for n, i in enumerate(rows0):
+        p = rows[i][1]
+        syn = GREEDY_V - 1 - n
+        table[syn] = (table[int(ori[0, p])].double() + CLOSE_STEP * torch.randn(e, generator=g).double()).float()
+        rows[i] = (0, p, p, syn)
+        scores[i] = 1.0 - 0.01 * n
+    return dict(table=table, ori=ori, cand=torch.tensor(rows, dtype=torch.int32), scores=torch.tensor(scores))
+
+
+def greedy_accept64(case, threshold):
+    """The loop of ``attack/text_update.py::greedy_accept`` with the bag-of-embeddings similarity in float64.  Returns
+    (new_id (B, L), rank (B, L), smallest |sim - threshold at that moment| per sample, per sample the margins of the
+    comparisons made AFTER the threshold had risen).  A candidate that proposes the word already in place after an
+    acceptance reproduces the risen threshold by construction (same ids, same arithmetic): an exact tie, rejected by
+    `>`, which no rounding can move -- it records no margin."""
+    table = case["table"].double().numpy()
+    ori_all, cand, scores = case["ori"].numpy(), case["cand"].numpy(), case["scores"].numpy()
+    b, length = ori_all.shape
+    new_id = np.full((b, length), -1, dtype=np.int64)
+    rank = np.full((b, length), -1, dtype=np.int64)
+    smallest = np.full(b, np.inf)
+    risen = [[] for _ in range(b)]
+
+    def mean(ids):
+        return table[[t for t in ids if t != 0]].mean(0)
+
+    for s in range(b):
+        mine = np.nonzero(cand[:, 0] == s)[0]
+        order = sorted(mine, key=lambda i: scores[i], reverse=True)
+        cur = ori_all[s].copy()
+        mo = mean(ori_all[s])
+        thr, taken = threshold, set()
+        for i in order:
+            p, v = int(cand[i, 1]), int(cand[i, 3])
+            if p in taken:
+                continue
+            if v == cur[p] and taken:
+                continue                                          # exact tie with the risen threshold
+            trial = cur.copy()
+            trial[p] = v
+            mt = mean(trial)
+            sim = float(mo @ mt / (np.linalg.norm(mo) * np.linalg.norm(mt) + 1e-12))
+            smallest[s] = min(smallest[s], abs(sim - thr))
+            if taken:
+                risen[s].append(abs(sim - thr))
+            if sim > thr:
+                thr = sim
+                new_id[s, p], rank[s, p] = v, len(taken)
+                taken.add(p)
+                cur = trial
+    return new_id, rank, smallest, risen
+
+
+# --------------------------------------------------------------------------------------------------- image gradients
+def image_grads(shape, seed=0):
+    """Image gradients of the feature loss: ``1e-6 randn exp(randn)`` (heavy-tailed, 1e-5 .. 1e-8) with 1 % exact zeros."""
+    g = torch.Generator().manual_seed(seed + 5)
+    x = 1e-6 * torch.randn(shape, generator=g) * torch.exp(torch.randn(shape, generator=g))
+    x[torch.rand(shape, generator=g) < 0.01] = 0.0
+    return x

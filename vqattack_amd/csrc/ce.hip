@@ -9,6 +9,9 @@
 // A-ch/attacks/fast_gradient_method.py:136-139).  The workgroup that finishes last folds the per-row losses in row
 // order into the scalar loss (relaxed two-level arrival counters, common.hpp): no second launch.
 // exp is the hardware v_exp_f32 path (__expf, ~2 ulp); the tests state 1e-4 relative against torch.
+// sum exp(x - m) is kept as (count of elements at the max) + (sum over the rest) and the loss is formed as
+// log(sum) - (x[t] - m): peaked rows (p ~ 1, loss down to 1e-8) keep 4e-6 relative accuracy at any common offset of the
+// logits (asserted, with the figures before and after, in tests/test_loss_fp64.py).
 // A label that is neither ignore_index nor in [0, V) poisons the loss with NaN and ORs VQA_FLAG_BAD_LABEL into *flag
 // (torch device-asserts on such a label; it is never silently dropped).
 // Algorithmic bytes: 4*V read + 4*V written per live row (8*V); a dead row (all labels ignore_index: zero gradient,
@@ -73,7 +76,7 @@ struct RowLabels {
 template <int MAXK>
 __device__ __forceinline__ RowLabels<MAXK> read_labels(const int64_t* __restrict__ labels, int K, long rows, long r,
                                                        int V, long ignore_index, const CeNorm& norm,
-                                                       const float* __restrict__ x, float lse) {
+                                                       const float* __restrict__ x, float m, float log_s) {
   RowLabels<MAXK> L;
   L.wsum = 0.0f;
   L.loss = 0.0f;
@@ -89,7 +92,9 @@ __device__ __forceinline__ RowLabels<MAXK> read_labels(const int64_t* __restrict
           L.lab[k] = t;
           L.wk[k] = norm.inv_count[k * norm.groups + r / norm.rpg];
           L.wsum += L.wk[k];
-          L.loss += L.wk[k] * (lse - x[t]);
+          // logsumexp - x[t] as log(s) - (x[t] - m): m + log(s) would round at ulp(m), which is the whole loss of a row
+          // whose label is predicted with p ~ 1 (x[t] == m, s = 1 + 1e-5) once the logits carry a common offset
+          L.loss += L.wk[k] * (log_s - (x[t] - m));
         } else {
           L.bad = true;
         }
@@ -145,11 +150,31 @@ __device__ __forceinline__ void fold_row_losses(const CeFold& fold, const float*
   }
 }
 
-__device__ __forceinline__ void online_merge(float& m, float& s, float m2, float s2) {
+// Softmax statistics of a set of logits as (m, c, s): the max, how many elements equal it, and the sum of exp(x - m) over
+// the OTHERS, so that sum exp = c + s.  A row whose label is predicted with p ~ 1 has c = 1 and s = 1e-2 .. 1e-7; a running
+// sum that carried the 1 would round every later term at ulp(1), and log(c + s) = log c + log1p(s / c) keeps the small
+// part exact (figures before and after, against float64: tests/test_loss_fp64.py::test_ce_rows_against_fp64).
+__device__ __forceinline__ void online_add(float& c, float& s, float v, float m) {
+  const bool top = (v == m);
+  c += top ? 1.0f : 0.0f;
+  s += top ? 0.0f : expf(v - m);
+}
+
+__device__ __forceinline__ void online_merge(float& m, float& c, float& s, float m2, float c2, float s2) {
   const float mm = fmaxf(m, m2);
-  s = s * expf(m - mm) + s2 * expf(m2 - mm);
+  if (mm == -INFINITY) {              // two sets without a finite element: nothing to rescale (-inf - -inf is NaN), but
+    s += s2;                          // a NaN met among -inf elements lives in s and must reach the row
+    c += c2;
+    return;
+  }
+  if (m != mm) { s = (s + c) * expf(m - mm); c = 0.0f; }
+  if (m2 != mm) { s2 = (s2 + c2) * expf(m2 - mm); c2 = 0.0f; }
+  s += s2;
+  c += c2;
   m = mm;
 }
+
+__device__ __forceinline__ float log_sum(float c, float s) { return logf(c) + log1pf(s / c); }
 
 // ---- streaming fallback (any V, strided / unaligned rows): two sweeps, the second re-reads the row from L2 ----
 template <bool GRAD, int MAXK>
@@ -159,7 +184,7 @@ __global__ __launch_bounds__(kBlock) void ce_rows_kernel(const float* __restrict
                                                          float* __restrict__ grad, float* __restrict__ row_loss,
                                                          float gscale, int* __restrict__ flag,
                                                          unsigned char* __restrict__ row_state) {
-  __shared__ float lds_m[kWaves], lds_s[kWaves];
+  __shared__ float lds_m[kWaves], lds_c[kWaves], lds_s[kWaves];
   const long r = blockIdx.x;
   if (row_is_dead(labels, K, rows, r, ignore_index)) {       // nothing to learn from this row: zero loss, zero gradient
     if (threadIdx.x == 0) row_loss[r] = 0.0f;
@@ -175,38 +200,48 @@ __global__ __launch_bounds__(kBlock) void ce_rows_kernel(const float* __restrict
   const float* x = logits + r * row_stride;
   const bool vec = ((reinterpret_cast<uintptr_t>(x) & 7u) == 0);
   // ---- sweep 1: online softmax statistics
-  float m = -INFINITY, s = 0.0f;
+  float m = -INFINITY, c = 0.0f, s = 0.0f;
   const int v2 = vec ? V / 2 : 0;
   for (int j = threadIdx.x; j < v2; j += kBlock) {
     f32x2 v = reinterpret_cast<const f32x2*>(x)[j];
     const float mm = fmaxf(m, fmaxf(v[0], v[1]));
-    s = s * expf(m - mm) + expf(v[0] - mm) + expf(v[1] - mm);
-    m = mm;
+    // only -inf so far (a vocabulary mask): nothing to add, and -inf - -inf is NaN.  fmaxf drops a NaN operand, so a
+    // NaN element is let through by name: it poisons s, as in torch and in the register kernel
+    if (mm != -INFINITY || v[0] != v[0] || v[1] != v[1]) {
+      if (m != mm) { s = (s + c) * expf(m - mm); c = 0.0f; }
+      online_add(c, s, v[0], mm);
+      online_add(c, s, v[1], mm);
+      m = mm;
+    }
   }
   for (int j = 2 * v2 + threadIdx.x; j < V; j += kBlock) {
     const float v = x[j];
     const float mm = fmaxf(m, v);
-    s = s * expf(m - mm) + expf(v - mm);
-    m = mm;
+    if (mm != -INFINITY || v != v) {
+      if (m != mm) { s = (s + c) * expf(m - mm); c = 0.0f; }
+      online_add(c, s, v, mm);
+      m = mm;
+    }
   }
-  if (s == 0.0f) m = -INFINITY;   // lanes that saw nothing
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float m2 = __shfl_xor(m, off, kWave), s2 = __shfl_xor(s, off, kWave);
-    if (m2 != -INFINITY || m != -INFINITY) online_merge(m, s, m2, s2);
+  for (int off = 32; off > 0; off >>= 1) {     // lanes that saw nothing (or only -inf) still hold m = -inf, c = s = 0
+    const float m2 = __shfl_xor(m, off, kWave), c2 = __shfl_xor(c, off, kWave), s2 = __shfl_xor(s, off, kWave);
+    online_merge(m, c, s, m2, c2, s2);
   }
   if ((threadIdx.x & (kWave - 1)) == 0) {
     lds_m[threadIdx.x / kWave] = m;
+    lds_c[threadIdx.x / kWave] = c;
     lds_s[threadIdx.x / kWave] = s;
   }
   __syncthreads();
   m = lds_m[0];
+  c = lds_c[0];
   s = lds_s[0];
 #pragma unroll
   for (int w = 1; w < kWaves; ++w)
-    if (lds_m[w] != -INFINITY || m != -INFINITY) online_merge(m, s, lds_m[w], lds_s[w]);
-  const float lse = m + logf(s);
-  const RowLabels<MAXK> L = read_labels<MAXK>(labels, K, rows, r, V, ignore_index, norm, x, lse);
+    online_merge(m, c, s, lds_m[w], lds_c[w], lds_s[w]);
+  const RowLabels<MAXK> L = read_labels<MAXK>(labels, K, rows, r, V, ignore_index, norm, x, m, log_sum(c, s));
+  s += c;                                      // sum exp(x - m)
   if (threadIdx.x == 0) {
     row_loss[r] = L.loss;
     if (L.bad && flag) atomicOr(flag, VQA_FLAG_BAD_LABEL);
@@ -280,7 +315,7 @@ __global__ __launch_bounds__(THREADS, WGPC * THREADS / 256) void ce_rows_reg_ker
     int* __restrict__ flag, CeFold fold, unsigned char* __restrict__ row_state) {
   constexpr int kQuads = kRegFloats / 4 / THREADS;
   constexpr int kWavesT = THREADS / kWave;
-  __shared__ float lds[kWavesT];
+  __shared__ float lds[kWavesT], lds_c[kWavesT];
   const long r = blockIdx.x;
   const RowGeom cur = row_geom(logits, r, V);
   if (row_is_dead(labels, K, rows, r, ignore_index)) {       // workgroup-uniform: no logits load, no exp, zeros out
@@ -325,32 +360,44 @@ __global__ __launch_bounds__(THREADS, WGPC * THREADS / 256) void ce_rows_reg_ker
   for (int w = 1; w < kWavesT; ++w) m = fmaxf(m, lds[w]);
   __syncthreads();
   ve = __expf(ve - m);                              // exp(-inf) = 0 for lanes without an edge element
-  float s = ve;
+  // sum exp = c + s: the elements at the max (exp = 1 exactly) are counted, the others summed -- see online_add
+  float c = (ve == 1.0f) ? 1.0f : 0.0f;
+  float s = (ve == 1.0f) ? 0.0f : ve;
 #pragma unroll
   for (int i = 0; i < kQuads; ++i) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       v[i][e] = __expf(v[i][e] - m);
-      s += v[i][e];
+      const bool top = (v[i][e] == 1.0f);
+      c += top ? 1.0f : 0.0f;
+      s += top ? 0.0f : v[i][e];
     }
   }
   s = wave_sum(s);
-  if ((threadIdx.x & (kWave - 1)) == 0) lds[threadIdx.x / kWave] = s;
+  c = wave_sum(c);
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    lds[threadIdx.x / kWave] = s;
+    lds_c[threadIdx.x / kWave] = c;
+  }
   __syncthreads();
   s = lds[0];
+  c = lds_c[0];
 #pragma unroll
-  for (int w = 1; w < kWavesT; ++w) s += lds[w];
-  const float lse = m + logf(s);
-  const RowLabels<MAXK> L = read_labels<MAXK>(labels, K, rows, r, V, ignore_index, norm, cur.x, lse);
+  for (int w = 1; w < kWavesT; ++w) {
+    s += lds[w];
+    c += lds_c[w];
+  }
+  const RowLabels<MAXK> L = read_labels<MAXK>(labels, K, rows, r, V, ignore_index, norm, cur.x, m, log_sum(c, s));
+  s += c;                                           // sum exp(x - m)
   if (threadIdx.x == 0) {
     __hip_atomic_store(row_loss + r, L.loss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (L.bad && flag) atomicOr(flag, VQA_FLAG_BAD_LABEL);
   }
   if (GRAD) {
     float* g = grad + r * static_cast<long>(V);
-    const float c = L.wsum / s;
+    const float w_over_s = L.wsum / s;
     if (edge >= 0) {
-      float val = c * ve;
+      float val = w_over_s * ve;
 #pragma unroll
       for (int k = 0; k < MAXK; ++k) val -= (L.lab[k] == edge) ? L.wk[k] : 0.0f;
       g[edge] = gscale * val;
@@ -363,7 +410,7 @@ __global__ __launch_bounds__(THREADS, WGPC * THREADS / 256) void ce_rows_reg_ker
         f32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          float val = c * v[i][e];
+          float val = w_over_s * v[i][e];
 #pragma unroll
           for (int k = 0; k < MAXK; ++k) val -= (L.lab[k] == cur.head + 4 * j + e) ? L.wk[k] : 0.0f;
           o[e] = gscale * val;
