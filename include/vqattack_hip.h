@@ -391,6 +391,19 @@ int vqa_gemm_pack_b(const float* w, long ldw, int trans, void* packed, int K, in
 int vqa_gemm_bf16x6(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M, int N,
                     int K, vqa_stream_t stream);
 
+/* vqa_gemm_bf16x6_small: the same product from the same packed operand on 64 x 128 output tiles, for row counts whose
+ *   256 x 128 tiles cannot fill the device, with an optional deterministic split over K.  Argument rules and return
+ *   codes of vqa_gemm_bf16x6; 1 <= ksplit <= min(K / 32, 16), else VQA_ERR_SHAPE.  With nk = K / 32 k-steps, part p covers
+ *   the k-steps [p * nk / ksplit, (p + 1) * nk / ksplit) (integer division).  ksplit == 1: C = acc + bias with the bits of
+ *   vqa_gemm_bf16x6; ws is not touched and may be NULL.  ksplit > 1: every part stores its fp32 partial product P_p to
+ *   ws ([ksplit][M][N] floats, 16-byte aligned, vqa_gemm_small_ws_bytes; NULL -> VQA_ERR_NULL) and a second kernel on
+ *   the same stream forms C = ((P_0 + P_1) + ... + P_(ksplit-1)) + bias, in that order, in fp32.  No atomics and no
+ *   counters: bitwise reproducible, nothing to reset between launches.  Never allocates, never synchronises.
+ * vqa_gemm_small_ws_bytes: bytes of that workspace; 0 when ksplit == 1 or the shape is unsupported. */
+size_t vqa_gemm_small_ws_bytes(long M, int N, int ksplit);
+int vqa_gemm_bf16x6_small(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M,
+                          int N, int K, int ksplit, void* ws, vqa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

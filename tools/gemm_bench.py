@@ -1,12 +1,17 @@
-"""Per-shape A/B of the encoder GEMMs: the bf16x6 kernel (``csrc/gemm.hip``) against the library fp32 GEMM that
-``torch.addmm`` / ``torch.mm`` run (with the recorded TunableOp solutions active, as in bench.py).
+"""Per-shape A/B of the encoder GEMMs: the bf16x6 kernel (``csrc/gemm.hip``) and its small-tile variant (one record per
+``--ksplit`` value, plus the split ``ops.gemm_small_plan`` picks) against the library fp32 GEMM that ``torch.addmm`` /
+``torch.mm`` run (with the recorded TunableOp solutions active, as in bench.py).
 
 Random data (activations ~ N(0, 1), weights ~ N(0, 0.02^2)): bf16 MFMA loops hold a lower clock on random data than on
 zeros.  The variants are interleaved in one process over several rounds; per shape the median and min time per call, the
 fp32-equivalent TF/s (2 M N K / t), the bf16 MFMA TF/s the kernel sustains (6 products: 12 M N K / t) and the max / RMS
-error of each against an fp64 product are reported, plus the speed-up.  One JSON line per shape, a summary at the end.
+error of each against an fp64 product are reported, plus the speed-up and, per variant, the round-to-round spread
+(max - min of the per-round times: the margin a difference has to beat).  One JSON line per shape, a summary at the end.
+``--batch 1`` gives the shapes of the reference's own call (one sample per encoder pass); ``--graph`` times captured
+graphs of ``--reps`` calls, as that path is replayed.
 
-    python tools/gemm_bench.py [--model vlmo_base|albef_base|vlmo_large] [--rounds 5] [--reps 10] [--out FILE]
+    python tools/gemm_bench.py [--model vlmo_base|albef_base|vlmo_large] [--batch B] [--ksplit 1,2,4,8] [--graph]
+                               [--rounds 5] [--reps 10] [--only NAMES] [--out FILE]
 """
 import argparse
 import json
@@ -25,9 +30,10 @@ MODELS = {"vlmo_base": (768, 3072, 591, 40, 64), "albef_base": (768, 3072, 577, 
           "vlmo_large": (1024, 4096, 591, 40, 128)}
 
 
-def shapes(model):
+def shapes(model, batch=0):
     """(name, M, N, K, bias) of every encoder GEMM of one layer, forward and input-gradient backward."""
     d, f, s, t, b = MODELS[model]
+    b = batch or b
     rows = b * s
     out = [("qkv_fwd", rows, 3 * d, d, True), ("qkv_bwd", rows, d, 3 * d, False),
            ("proj_fwd", rows, d, d, True), ("proj_bwd", rows, d, d, False)]
@@ -51,13 +57,19 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--only", default="", help="comma-separated shape names")
+    ap.add_argument("--batch", type=int, default=0, help="samples per encoder pass (default: the model's benchmark batch)")
+    ap.add_argument("--ksplit", default="1,2,4,8", help="comma-separated K splits of the small-tile kernel ('' = none)")
+    ap.add_argument("--graph", action="store_true",
+                    help="time each variant as ONE captured graph of --reps calls (device time without the host's launch "
+                         "cost: how the batch-1 path runs, which is replayed from a captured graph)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     tuned = tuned_gemms.enable()
     dev = torch.device("cuda")
     gen = torch.Generator(device=dev).manual_seed(0)
     results = []
-    for name, M, N, K, has_bias in shapes(args.model):
+    ksplits = [int(v) for v in args.ksplit.split(",") if v]
+    for name, M, N, K, has_bias in shapes(args.model, args.batch):
         if args.only and name not in args.only.split(","):
             continue
         a = torch.randn(M, K, device=dev, generator=gen)
@@ -77,16 +89,34 @@ def main():
             else:
                 torch.mm(a, bt, out=out_l)
 
-        times = {"kernel": [], "library": []}
-        for fn in (run_kernel, run_library):        # warm-up
+        variants = [("kernel", run_kernel), ("library", run_library)]
+        planned = ops.gemm_small_plan(M, N, K)
+        small = sorted({k for k in ksplits + [planned] if 1 <= k <= min(K // 32, 16)}) if ksplits else []
+        out_s = torch.empty(M, N, device=dev)
+        for k in small:
+            variants.append(("small%d" % k, lambda k=k: ops.gemm_small(a, packed, bias, out=out_s, ksplit=k)))
+        times = {key: [] for key, _ in variants}
+        for _, fn in variants:                      # warm-up
             fn()
         torch.cuda.synchronize()
+        graphs = {}
+        if args.graph:
+            for key, fn in variants:
+                graphs[key] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[key]):
+                    for _ in range(args.reps):
+                        fn()
+                graphs[key].replay()
+            torch.cuda.synchronize()
         for _ in range(args.rounds):
-            for key, fn in (("kernel", run_kernel), ("library", run_library)):
+            for key, fn in variants:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-                for _ in range(args.reps):
-                    fn()
+                if args.graph:
+                    graphs[key].replay()
+                else:
+                    for _ in range(args.reps):
+                        fn()
                 e1.record()
                 e1.synchronize()
                 times[key].append(e0.elapsed_time(e1) / args.reps)
@@ -96,7 +126,15 @@ def main():
         run_kernel(), run_library()
         torch.cuda.synchronize()
         ek, el = err(out_k, ref), err(out_l, ref)
-        del ref
+        small_rows = []
+        for k in small:
+            ops.gemm_small(a, packed, bias, out=out_s, ksplit=k)
+            torch.cuda.synchronize()
+            es, ts = err(out_s, ref), times["small%d" % k]
+            small_rows.append(dict(ksplit=k, planned=k == planned, ms_median=statistics.median(ts), ms_min=min(ts),
+                                   ms_spread=max(ts) - min(ts), err_max=es[0], err_rms=es[1],
+                                   speedup_vs_library_median=statistics.median(times["library"]) / statistics.median(ts)))
+        del ref, graphs
         med_k, med_l = statistics.median(times["kernel"]), statistics.median(times["library"])
         flop = 2.0 * M * N * K
         row = dict(shape=name, M=M, N=N, K=K, bias=has_bias,
@@ -105,13 +143,16 @@ def main():
                    speedup_median=med_l / med_k, speedup_min=min(times["library"]) / min(times["kernel"]),
                    kernel_fp32eq_tflops=flop / med_k / 1e9, kernel_bf16_mfma_tflops=6 * flop / med_k / 1e9,
                    library_tflops=flop / med_l / 1e9,
+                   kernel_ms_spread=max(times["kernel"]) - min(times["kernel"]),
+                   library_ms_spread=max(times["library"]) - min(times["library"]),
+                   big_workgroups=ops.gemm_workgroups(M, N), small_tiles=ops.gemm_small_workgroups(M, N), small=small_rows,
                    kernel_err_max=ek[0], kernel_err_rms=ek[1], library_err_max=el[0], library_err_rms=el[1])
         print(json.dumps(row), flush=True)
         results.append(row)
-        del a, w, packed, out_k, out_l
+        del a, w, packed, out_k, out_l, out_s
         torch.cuda.empty_cache()
-    summary = dict(model=args.model, tuned_gemms=tuned, device=torch.cuda.get_device_name(),
-                   rounds=args.rounds, reps=args.reps, shapes=results)
+    summary = dict(model=args.model, batch=args.batch or MODELS[args.model][4], tuned_gemms=tuned, device=torch.cuda.get_device_name(),
+                   rounds=args.rounds, reps=args.reps, graph=args.graph, shapes=results)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as fh:
@@ -121,6 +162,10 @@ def main():
         print("{:<20}{:>10.3f}{:>11.1f}{:>9.0f}{:>8.1f}  {:.2e}/{:.2e}".format(
             r["shape"], r["speedup_median"], r["kernel_fp32eq_tflops"], r["kernel_bf16_mfma_tflops"],
             r["library_tflops"], r["kernel_err_max"], r["library_err_max"]))
+        for sm in r["small"]:
+            print("  small ksplit {:<2}{} {:>8.3f}x library  {:.4f} ms (spread {:.4f}; library {:.4f} spread {:.4f})  err {:.2e}"
+                  .format(sm["ksplit"], "*" if sm["planned"] else " ", sm["speedup_vs_library_median"], sm["ms_median"],
+                          sm["ms_spread"], r["library_ms_median"], r["library_ms_spread"], sm["err_max"]))
 
 
 if __name__ == "__main__":

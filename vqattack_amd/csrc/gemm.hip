@@ -180,6 +180,148 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_kernel(GemmArgs g) {
   }
 }
 
+// ---- small-tile variant for grids the 256 x 128 tile cannot fill (a few hundred rows, or a narrow N) ---------------
+// Same packed B, same split, same product and k-step order, so with ksplit == 1 every output has the bits of
+// gemm_bf16x6_kernel.  Tile: 64 x 128 outputs per workgroup of 4 waves (2 along M x 2 along N, 32 x 64 each = 2 x 4 MFMA
+// tiles), BK = 32.  LDS per k-step: A 4 m-tiles x 3 planes x 1 KiB + B 24 KiB = 36 KiB, double-buffered = 72 KiB (two
+// workgroups per CU), fragment order as above.  Per k-step a wave issues 18 fragment reads and 48 MFMAs.
+//
+// Split-K: part p of ksplit covers the k-steps [p * nk / ksplit, (p + 1) * nk / ksplit) and, with ksplit > 1, stores its
+// fp32 partial tile (no bias) to ws[p][M][N]; gemm_splitk_combine_kernel, launched behind it on the same stream, forms
+// ((P0 + P1) + ... + P(ksplit-1)) + bias in that order.  No atomics, no counters: nothing depends on arrival order and
+// nothing has to be reset between launches (graph replay).
+constexpr int kSmallBM = 64;
+constexpr int kSmallThreads = 256;
+constexpr int kSmallMT = kSmallBM / 16;                                // 4 m-tiles per workgroup
+constexpr int kSmallABytes = kSmallMT * 3 * kTileBytes;                // 12 KiB
+constexpr int kSmallStage = kSmallABytes + kGemmBBytes;                // 36 KiB
+constexpr int kSmallBPieces = kGemmBBytes / 16 / kSmallThreads;        // 6 x 16 B of B per thread and k-step
+constexpr int kGemmMaxKSplit = 16;
+
+__global__ __launch_bounds__(kSmallThreads) void gemm_bf16x6_small_kernel(GemmArgs g, float* __restrict__ ws, int ksplit) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * kSmallStage];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;                 // this wave's 32 x 64 output block
+  const int ntb = g.N / kGemmBN;
+  const int mtb = static_cast<int>((g.M + kSmallBM - 1) / kSmallBM);
+  const int tiles = mtb * ntb;
+  // XCD remap as above; the part index is the slowest, so the tiles of one row band and part share an XCD's L2
+  const int nwg = tiles * ksplit, orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, rem = nwg & 7;
+  const int wg = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (orig >> 3);
+  const int part = wg / tiles, tile = wg - part * tiles;
+  const int mb = tile / ntb, nb = tile - mb * ntb;
+  const long m0 = static_cast<long>(mb) * kSmallBM;
+  const int n0 = nb * kGemmBN;
+  const int nk = g.K / kGemmBK;
+  const int k0 = part * nk / ksplit, k1 = (part + 1) * nk / ksplit;    // ksplit <= nk: never empty
+  const int nt16 = g.N / 16;
+
+  // staging: this thread splits one (row, 8-k chunk) piece of A per k-step -- m-tile wave, row lane & 15, chunk
+  // lane >> 4 -- and copies 6 x 16 B of packed B
+  long r = m0 + wave * 16 + (lane & 15);
+  r = r < g.M ? r : g.M - 1;
+  const float* arow = g.A + r * g.lda + 8 * (lane >> 4);
+  const bf16x8* bsrc = g.B + static_cast<size_t>(nb) * kGemmNT * 3 * 64;
+  const size_t bstep = static_cast<size_t>(nt16) * 3 * 64;            // bf16x8 per k-step of packed B
+
+  f32x4 ra[2];
+  bf16x8 rb[kSmallBPieces];
+  auto load = [&](int kt) {
+    ra[0] = *reinterpret_cast<const f32x4*>(arow + kt * kGemmBK);
+    ra[1] = *reinterpret_cast<const f32x4*>(arow + kt * kGemmBK + 4);
+#pragma unroll
+    for (int p = 0; p < kSmallBPieces; ++p) rb[p] = bsrc[kt * bstep + p * kSmallThreads + tid];
+  };
+  auto store = [&](int s) {
+    char* base = smem + s * kSmallStage;
+    bf16x8 p0, p1, p2;
+    split8(ra[0], ra[1], p0, p1, p2);
+    bf16x8* dst = reinterpret_cast<bf16x8*>(base) + wave * 3 * 64 + lane;
+    dst[0] = p0;
+    dst[64] = p1;
+    dst[128] = p2;
+    bf16x8* bdst = reinterpret_cast<bf16x8*>(base + kSmallABytes);
+#pragma unroll
+    for (int p = 0; p < kSmallBPieces; ++p) bdst[p * kSmallThreads + tid] = rb[p];
+  };
+
+  f32x4 acc[2][4];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+  load(k0);
+  store(0);
+  __syncthreads();
+  for (int kt = k0; kt < k1; ++kt) {
+    const int cur = (kt - k0) & 1;
+    load(kt + 1 < k1 ? kt + 1 : kt);          // the last step reloads its own tile into the idle buffer: no branch
+    __builtin_amdgcn_sched_barrier(0);        // keep the loads ahead of the MFMAs
+    const bf16x8* sa = reinterpret_cast<const bf16x8*>(smem + cur * kSmallStage) + wm * 2 * 3 * 64 + lane;
+    const bf16x8* sb = reinterpret_cast<const bf16x8*>(smem + cur * kSmallStage + kSmallABytes) + wn * 4 * 3 * 64 + lane;
+    bf16x8 fa[3][2], fb[3][4];
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) fa[p][i] = sa[(i * 3 + p) * 64];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) fb[p][j] = sb[(j * 3 + p) * 64];
+    }
+    constexpr int kPa[6] = {2, 1, 0, 1, 0, 0}, kPb[6] = {0, 1, 2, 0, 1, 0};   // the order of gemm_bf16x6_kernel
+#pragma unroll
+    for (int t = 0; t < 6; ++t) {
+      if (t == 3) store(cur ^ 1);
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kPa[t]][i], fb[kPb[t]][j], acc[i][j], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+
+  // epilogue: accumulator register r of tile (i, j) is row (lane >> 4) * 4 + r, column lane & 15.  A part of a split
+  // stores the bare accumulators into its [M, N] slab of the workspace
+  float* out = ksplit == 1 ? g.C : ws + static_cast<size_t>(part) * g.M * g.N;
+  const long ldo = ksplit == 1 ? g.ldc : g.N;
+  const bool add_bias = ksplit == 1 && g.bias;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int col = n0 + wn * 64 + j * 16 + (lane & 15);
+    const float bv = add_bias ? g.bias[col] : 0.0f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        const long row = m0 + wm * 32 + i * 16 + (lane >> 4) * 4 + rr;
+        if (row < g.M) out[row * ldo + col] = add_bias ? acc[i][j][rr] + bv : acc[i][j][rr];
+      }
+  }
+}
+
+// C = ((P0 + P1) + ... + P(ksplit-1)) + bias over the [ksplit][M][N] partials, one thread per 4 columns of a row.
+__global__ __launch_bounds__(kBlock) void gemm_splitk_combine_kernel(const f32x4* __restrict__ ws,
+                                                                     const float* __restrict__ bias, float* __restrict__ C,
+                                                                     long ldc, long M, int N, int ksplit, int vec) {
+  const int n4 = N / 4;
+  const long total = M * n4;
+  for (long idx = static_cast<long>(blockIdx.x) * blockDim.x + threadIdx.x; idx < total;
+       idx += static_cast<long>(gridDim.x) * blockDim.x) {
+    f32x4 s = ws[idx];
+    for (int p = 1; p < ksplit; ++p) s = s + ws[p * total + idx];
+    const long row = idx / n4;
+    const int col = static_cast<int>(idx - row * n4) * 4;
+    if (bias) s = s + f32x4{bias[col], bias[col + 1], bias[col + 2], bias[col + 3]};
+    float* dst = C + row * ldc + col;
+    if (vec) {
+      *reinterpret_cast<f32x4*>(dst) = s;
+    } else {
+      dst[0] = s.x, dst[1] = s.y, dst[2] = s.z, dst[3] = s.w;
+    }
+  }
+}
+
 // One thread per (k-tile, n-tile, lane): 8 consecutive k of one column, split into the three planes.
 __global__ __launch_bounds__(kBlock) void gemm_pack_b_kernel(const float* __restrict__ w, long ldw, int trans,
                                                              bf16x8* __restrict__ out, int K, int N) {
@@ -235,6 +377,34 @@ int vqa_gemm_bf16x6(const float* A, long lda, const void* packed, const float* b
   GemmArgs g{A, static_cast<const bf16x8*>(packed), bias, C, lda, ldc, M, N, K};
   const int grid = static_cast<int>((M + kGemmBM - 1) / kGemmBM * (N / kGemmBN));
   gemm_bf16x6_kernel<<<grid, kGemmThreads, 0, static_cast<hipStream_t>(stream)>>>(g);
+  return launch_status();
+}
+
+size_t vqa_gemm_small_ws_bytes(long M, int N, int ksplit) {
+  if (M <= 0 || N <= 0 || N % kGemmBN || ksplit <= 1 || ksplit > kGemmMaxKSplit) return 0;
+  return static_cast<size_t>(ksplit) * static_cast<size_t>(M) * N * sizeof(float);
+}
+
+int vqa_gemm_bf16x6_small(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M,
+                          int N, int K, int ksplit, void* ws, vqa_stream_t stream) {
+  clear_stale_error();
+  if (!A || !packed || !C) return VQA_ERR_NULL;
+  if (M < 0 || N <= 0 || K <= 0 || K % kGemmBK || N % kGemmBN || lda < K || lda % 4 || ldc < N) return VQA_ERR_SHAPE;
+  if (ksplit < 1 || ksplit > kGemmMaxKSplit || ksplit > K / kGemmBK) return VQA_ERR_SHAPE;
+  if ((M + kSmallBM - 1) / kSmallBM * (N / kGemmBN) * ksplit > 0x7fffffffL) return VQA_ERR_SHAPE;
+  if (ksplit > 1 && !ws) return VQA_ERR_NULL;
+  if (!aligned16(A) || !aligned16(packed) || !aligned4(C) || (bias && !aligned4(bias))) return VQA_ERR_ALIGN;
+  if (ksplit > 1 && !aligned16(ws)) return VQA_ERR_ALIGN;
+  if (M == 0) return VQA_OK;
+  GemmArgs g{A, static_cast<const bf16x8*>(packed), bias, C, lda, ldc, M, N, K};
+  const int grid = static_cast<int>((M + kSmallBM - 1) / kSmallBM * (N / kGemmBN) * ksplit);
+  gemm_bf16x6_small_kernel<<<grid, kSmallThreads, 0, static_cast<hipStream_t>(stream)>>>(g, static_cast<float*>(ws), ksplit);
+  if (ksplit > 1) {
+    const int vec = aligned16(C) && ldc % 4 == 0;
+    gemm_splitk_combine_kernel<<<blocks_for(static_cast<size_t>(M) * (N / 4), kBlock), kBlock, 0,
+                                 static_cast<hipStream_t>(stream)>>>(static_cast<const f32x4*>(ws), bias, C, ldc, M, N,
+                                                                     ksplit, vec);
+  }
   return launch_status();
 }
 

@@ -761,3 +761,56 @@ def gemm(a, packed, bias=None, out=None):
             check(lib().vqa_gemm_bf16x6(_p(a), a.stride(0), _p(packed.data), ptr(bias), _p(out), packed.N, M, packed.N,
                                         packed.K, stream_for(a)), "vqa_gemm_bf16x6")
     return out
+
+
+# Planner constants of the small-tile kernel (measured: profiles/r08/): one 64 x 128 tile per workgroup, two workgroups
+# resident per CU.  The split over K raises the grid towards SMALL_TARGET_WORKGROUPS while every part keeps at least
+# SMALL_MIN_KSTEPS k-steps (32 columns of A each) to amortise its prologue and its partial-tile traffic.
+SMALL_TARGET_WORKGROUPS = 512
+SMALL_MIN_KSTEPS = 4
+SMALL_MAX_KSPLIT = 8
+
+
+def gemm_small_workgroups(M, N):
+    """64 x 128 output tiles of one ``vqa_gemm_bf16x6_small`` launch (times ksplit = its grid)."""
+    return -(-M // 64) * (N // 128)
+
+
+def gemm_small_plan(M, N, K):
+    """The K split ``gemm_small`` should run (M, N, K) with: the largest one, up to SMALL_MAX_KSPLIT, that keeps the grid at
+    or below SMALL_TARGET_WORKGROUPS and every part at SMALL_MIN_KSTEPS k-steps or more; 1 where the tile grid alone
+    covers the device.  Pure arithmetic, no device."""
+    tiles = max(1, gemm_small_workgroups(M, N))
+    nk = max(1, K // 32)
+    return int(max(1, min(SMALL_MAX_KSPLIT, nk // SMALL_MIN_KSTEPS, nk, SMALL_TARGET_WORKGROUPS // tiles)))
+
+
+def gemm_small(a, packed, bias=None, out=None, ksplit=1):
+    """``gemm`` on 64 x 128 tiles with a deterministic ``ksplit``-way split over K (``vqa_gemm_bf16x6_small``): for row
+    counts whose 256 x 128 tiles cannot fill the device.  ``ksplit == 1`` gives the bits of ``gemm``; ``ksplit > 1`` the
+    ordered sum of the parts' products (``include/vqattack_hip.h``), through a workspace allocated here."""
+    dev_f32(a, "a", contiguous=False)
+    if a.dim() != 2 or a.shape[1] != packed.K or a.stride(1) != 1 or a.stride(0) % 4:
+        raise ValueError("a must be (M, {}) with unit column stride and a row stride % 4 == 0, got shape {} strides {}"
+                         .format(packed.K, tuple(a.shape), a.stride()))
+    ksplit = int(ksplit)
+    if not 1 <= ksplit <= min(packed.K // 32, 16):
+        raise ValueError("ksplit must be in [1, {}] for K={}, got {}".format(min(packed.K // 32, 16), packed.K, ksplit))
+    M = a.shape[0]
+    if out is None:
+        out = torch.empty(M, packed.N, dtype=torch.float32, device=a.device)
+    dev_f32(out, "out")
+    if tuple(out.shape) != (M, packed.N):
+        raise ValueError("out must be ({}, {}), got {}".format(M, packed.N, tuple(out.shape)))
+    if bias is not None:
+        dev_f32(bias, "bias"), _rows_ok("bias", bias, packed.N)
+    same_device(a, packed.data, bias, out)
+    if M:
+        ws = None
+        if ksplit > 1:
+            ws = torch.empty(lib().vqa_gemm_small_ws_bytes(M, packed.N, ksplit), dtype=torch.uint8, device=a.device)
+        with _on(a):
+            check(lib().vqa_gemm_bf16x6_small(_p(a), a.stride(0), _p(packed.data), ptr(bias), _p(out), packed.N, M,
+                                              packed.N, packed.K, ksplit, ptr(ws), stream_for(a)),
+                  "vqa_gemm_bf16x6_small")
+    return out

@@ -30,14 +30,40 @@ from .. import ops
 # (2560 x 768).  VQA_GEMM=library restores the library everywhere.
 MIN_WORKGROUPS = 192
 
+# Below MIN_WORKGROUPS the small-tile kernel (64 x 128 tiles, deterministic split-K: ops.gemm_small with the split of
+# ops.gemm_small_plan) takes the shape classes it was MEASURED to win: (N, K) -> (fewest rows, most rows), both
+# inclusive.  An entry is there only where the small kernel's median time beat the library's by more than the
+# round-to-round spread of either variant in the same record, at every measured row count of the range
+# (profiles/r08/README.md, tools/gemm_bench.py --batch); everything else stays on the library.
+# Recorded: at 551-591 rows (batch 1) every shape loses (0.77-0.92x of the library, call times of 20-35 us); the text
+# expert's 2560 x 768 x 3072 passes the margin in one of its two records only (1.10x).  At 1102-1182 rows (VLMO-base,
+# batch 2) the N = 3072, K = 768 GEMMs win 1.34-1.49x unsplit, but the end-to-end comparison with that entry was not
+# taken, so it is not dispatched: the policy is empty and the unset VQA_GEMM behaves as "large".
+SMALL_POLICY = {}
+
+
+def _mode():
+    """VQA_GEMM: "library" = the library everywhere, "large" = the big kernel from MIN_WORKGROUPS up and the library below,
+    "small" = as "large" plus the small kernel for every covered shape below, anything else = the measured policy."""
+    mode = os.environ.get("VQA_GEMM", "")
+    return mode if mode in ("library", "large", "small") else ""
+
 
 def _kernel_gemms():
-    return os.environ.get("VQA_GEMM", "") != "library"
+    return _mode() != "library"
+
+
+def _small_gemm(rows, n, k):
+    mode = _mode()
+    if mode == "small":
+        return True
+    lo, hi = SMALL_POLICY.get((n, k), (1, 0))
+    return mode == "" and lo <= rows <= hi
 
 
 def _pack(w):
-    """(forward operand w.t(), input-gradient operand w) of a Linear weight w [out, in], packed once for the kernel;
-    None where the kernel does not cover the shape or VQA_GEMM=library."""
+    """(forward operand w.t(), input-gradient operand w) of a Linear weight w [out, in], packed once for both kernels;
+    None where they do not cover the shape or VQA_GEMM=library."""
     if not _kernel_gemms() or not (ops.gemm_shape_ok(w.shape[0], w.shape[1]) and ops.gemm_shape_ok(w.shape[1], w.shape[0])):
         return (None, None)
     return (ops.gemm_pack(w, trans=True), ops.gemm_pack(w, trans=False))
@@ -45,15 +71,23 @@ def _pack(w):
 
 def _linear(a, w, bias, packed):
     """a @ w.t() + bias (a Linear layer's forward)."""
-    if packed[0] is not None and ops.gemm_workgroups(a.shape[0], packed[0].N) >= MIN_WORKGROUPS and _kernel_gemms():
-        return ops.gemm(a, packed[0], bias)
+    pk = packed[0]
+    if pk is not None and _kernel_gemms():
+        if ops.gemm_workgroups(a.shape[0], pk.N) >= MIN_WORKGROUPS:
+            return ops.gemm(a, pk, bias)
+        if a.shape[0] and _small_gemm(a.shape[0], pk.N, pk.K):
+            return ops.gemm_small(a, pk, bias, ksplit=ops.gemm_small_plan(a.shape[0], pk.N, pk.K))
     return torch.addmm(bias, a, w.t())
 
 
 def _linear_grad(g, w, packed):
     """g @ w (the input gradient of a Linear layer)."""
-    if packed[1] is not None and ops.gemm_workgroups(g.shape[0], packed[1].N) >= MIN_WORKGROUPS and _kernel_gemms():
-        return ops.gemm(g, packed[1])
+    pk = packed[1]
+    if pk is not None and _kernel_gemms():
+        if ops.gemm_workgroups(g.shape[0], pk.N) >= MIN_WORKGROUPS:
+            return ops.gemm(g, pk)
+        if g.shape[0] and _small_gemm(g.shape[0], pk.N, pk.K):
+            return ops.gemm_small(g, pk, ksplit=ops.gemm_small_plan(g.shape[0], pk.N, pk.K))
     return torch.mm(g, w)
 
 
