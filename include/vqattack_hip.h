@@ -358,7 +358,8 @@ int vqa_resize_bicubic_v_normalize(const uint8_t* src, int h_in, int w, int c, c
  *   y written whole (y1 == NULL) or split (y0 / y1); mean[row], rstd[row] saved for the backward.  The statistics are
  *   taken on the row centred on its first element, so rows far from zero or nearly constant keep their spread; the
  *   backward reads rstd and forms x - mean from x in the same way (bitwise what the forward used).  Without a prologue
- *   x_out is not written.  16 B/element with prologue, 8 without.  Replaces torch.addcmul + torch.cat + two slice copies
+ *   x_out is not written; with one, x_out may be NULL (a forward-only caller that never reads the sum: 12 B/element).
+ *   16 B/element with prologue, 8 without.  Replaces torch.addcmul + torch.cat + two slice copies
  *   + F.layer_norm per stage (multiway_transformer.py:186-199).
  * vqa_ln_bwd: dx = (g_a ? g_a : 0) + (g_inj ? g_inj : 0) + dLayerNorm/dx(dy; x, mean, rstd, gamma)  (frozen gamma/beta:
  *   input gradient only); dy whole (dy1 == NULL) or split; g_a = gradient arriving over the residual path, g_inj = the
@@ -366,6 +367,16 @@ int vqa_resize_bicubic_v_normalize(const uint8_t* src, int h_in, int w, int c, c
  *   dr = rscale * dx (rscale NULL = 1) written whole or split (dr1): the gradient of the branch the forward prologue
  *   added.  20-28 B/element.  Replaces layer_norm's backward, the gradient-accumulation adds, addcmul's backward and the
  *   slice / cat backward copies.
+ * vqa_ln_bwd_post: the same stage of a POST-LN block  y = LayerNorm(s),  s = x + f(x)  -- the BERT fusion encoder of
+ *   ALBEF, reference ALBEF_attack/models/xbert.py BertSelfOutput.forward / BertOutput.forward
+ *   (hidden_states = self.LayerNorm(hidden_states + input_tensor)), forward by vqa_ln_fwd with r0 / x_out (x_out = s):
+ *   ds = dLayerNorm/dx((dy_a + (dy_b ? dy_b : 0)) + (g_inj ? g_inj : 0); s, rstd, gamma)  -- the gradients that reach y
+ *   (at most three in a BERT layer: the next layer's residual path, the input gradient of its packed q/k/v projection,
+ *   the loss kernel's gradient of this feature map) are summed in that fixed order BEFORE the LayerNorm backward, which
+ *   vqa_ln_bwd (sum after) cannot express.  ds is the gradient of x over the residual path AND of the branch f(x); it is
+ *   written once.  The LayerNorm arithmetic is vqa_ln_bwd's: with dy_b == g_inj == NULL the result has the bits of
+ *   vqa_ln_bwd(dy_a, ...) without g_a / g_inj.  12-20 B/element.  Replaces layer_norm's backward, the add's backward and
+ *   the gradient-accumulation adds.
  * vqa_gelu_fwd / vqa_gelu_bwd: a = gelu(h) / dh = da * gelu'(h), exact erf form (nn.GELU() of the reference's Mlp,
  *   multiway_transformer.py:36-55); dh may alias da. */
 int vqa_ln_fwd(const float* x, const float* r0, const float* r1, const float* rscale, float* x_out,
@@ -374,6 +385,8 @@ int vqa_ln_fwd(const float* x, const float* r0, const float* r1, const float* rs
 int vqa_ln_bwd(const float* dy0, const float* dy1, const float* x, const float* mean, const float* rstd,
                const float* gamma0, const float* gamma1, const float* g_a, const float* g_inj, const float* rscale,
                float* dx, float* dr0, float* dr1, long rows, int D, long period, long split, vqa_stream_t stream);
+int vqa_ln_bwd_post(const float* dy_a, const float* dy_b, const float* g_inj, const float* s, const float* rstd,
+                    const float* gamma, float* ds, long rows, int D, vqa_stream_t stream);
 int vqa_gelu_fwd(const float* h, float* a, size_t n, vqa_stream_t stream);
 int vqa_gelu_bwd(const float* h, const float* da, float* dh, size_t n, vqa_stream_t stream);
 

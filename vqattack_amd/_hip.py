@@ -67,6 +67,7 @@ SIGNATURES = {
     "vqa_attn_bwd_ws_floats": (_l, [_i, _i, _i, _i]),
     "vqa_ln_fwd": (_i, [_p] * 13 + [_l, _i, _l, _l, _f, _p]),
     "vqa_ln_bwd": (_i, [_p] * 13 + [_l, _i, _l, _l, _p]),
+    "vqa_ln_bwd_post": (_i, [_p] * 7 + [_l, _i, _p]),
     "vqa_gelu_fwd": (_i, [_p, _p, _sz, _p]),
     "vqa_gelu_bwd": (_i, [_p, _p, _p, _sz, _p]),
     "vqa_resize_bicubic_h_u8": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _p, _p]),

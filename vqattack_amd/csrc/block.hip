@@ -17,6 +17,11 @@
 //                 pass -- plus, optionally, dr = rscale * dx written whole or split: the gradient of the branch that the
 //                 forward prologue added.  Read dy, x, g_a (, g_inj); write dx (, dr) = 20-28 B (eager: LN backward 16 +
 //                 accumulation adds 12-24 + addcmul backward 8 + slice-backward cat 8 = 44-56 B).
+//   vqa_ln_bwd_post : ds = LN'(dy_a + dy_b + g_inj)  -- the same stage of a POST-LN block, y = LN(s), s = x + f(x) (ALBEF's
+//                 BERT fusion encoder, xbert.py BertSelfOutput / BertOutput): the gradients reaching y are summed BEFORE
+//                 the LayerNorm backward, and ds is the gradient of the residual path and of the branch at once, written
+//                 once.  Read s and one to three summands, write ds = 12-20 B (eager: accumulation adds 12-24 + LN
+//                 backward 16 + the add's two backward outputs).
 //   vqa_gelu_fwd / vqa_gelu_bwd : exact (erf) GELU and its derivative, 8 / 12 B per element.
 //
 // One wavefront owns one row of D <= 1024 floats in registers (NCH 16-byte pieces per lane); mean / variance and the
@@ -119,7 +124,7 @@ __global__ __launch_bounds__(kBlock) void ln_fwd_kernel(LnFwdArgs A) {
 #pragma unroll
         for (int k = 0; k < NCH; ++k) x[k] = x[k] + r[k];
       }
-      store_vec<NCH>(x, A.x_out + static_cast<long>(row) * A.D, lane, A.D);
+      if (A.x_out) store_vec<NCH>(x, A.x_out + static_cast<long>(row) * A.D, lane, A.D);   // optional: forward-only callers
     }
     // statistics of the row centred on its first element: a row far from zero, or nearly constant, keeps its spread
     const float pivot = row_pivot(x[0][0]);
@@ -152,6 +157,42 @@ __global__ __launch_bounds__(kBlock) void ln_fwd_kernel(LnFwdArgs A) {
   }
 }
 
+// g <- dLayerNorm/dx(g) for the row x of a forward y = LN(x) * gamma + beta with frozen gamma / beta (input gradient only);
+// x is overwritten with the normalised row.  Shared by vqa_ln_bwd and vqa_ln_bwd_post: one arithmetic, the same bits.
+template <int NCH>
+__device__ __forceinline__ void ln_input_grad(f32x4 (&g)[NCH], f32x4 (&xh)[NCH], const float* gamma,
+                                              const float* rstd_row, int lane, int D, float inv_d) {
+  {
+    f32x4 w[NCH];
+    load_vec<NCH>(w, gamma, lane, D);
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) g[k] = g[k] * w[k];
+  }
+  // x - mean exactly as the forward formed it (the same pivot, sum and order: bitwise the same values); the saved
+  // mean = pivot + mean_c is rounded, and subtracting it would lose a near-constant row's spread
+  const float rstd = *rstd_row;
+  const float pivot = row_pivot(xh[0][0]);
+  const float mean_c = centre_on_pivot<NCH>(xh, pivot, lane, D) * inv_d;
+  float c1 = 0.0f, c2 = 0.0f;
+#pragma unroll
+  for (int k = 0; k < NCH; ++k) {
+    const int d = (k * kWave + lane) * 4;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float h = d < D ? (xh[k][e] - mean_c) * rstd : 0.0f;
+      xh[k][e] = h;
+      c1 += g[k][e];
+      c2 += g[k][e] * h;
+    }
+  }
+  c1 = wave_sum(c1) * inv_d;
+  c2 = wave_sum(c2) * inv_d;
+#pragma unroll
+  for (int k = 0; k < NCH; ++k)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) g[k][e] = rstd * ((g[k][e] - c1) - xh[k][e] * c2);
+}
+
 struct LnBwdArgs {
   const float *dy0, *dy1, *x, *mean, *rstd, *gamma0, *gamma1, *g_a, *g_inj, *rscale;
   float *dx, *dr0, *dr1;
@@ -171,35 +212,7 @@ __global__ __launch_bounds__(kBlock) void ln_bwd_kernel(LnBwdArgs A) {
     f32x4 xh[NCH], g[NCH];
     load_vec<NCH, NT>(xh, A.x + off, lane, A.D);
     load_vec<NCH, NT>(g, A.dy1 ? (sr.seg ? A.dy1 : A.dy0) + sr.row * A.D : A.dy0 + off, lane, A.D);
-    {
-      f32x4 w[NCH];
-      load_vec<NCH>(w, (A.gamma1 && sr.seg) ? A.gamma1 : A.gamma0, lane, A.D);
-#pragma unroll
-      for (int k = 0; k < NCH; ++k) g[k] = g[k] * w[k];
-    }
-    // x - mean exactly as the forward formed it (the same pivot, sum and order: bitwise the same values); the saved
-    // mean = pivot + mean_c is rounded, and subtracting it would lose a near-constant row's spread
-    const float rstd = A.rstd[row];
-    const float pivot = row_pivot(xh[0][0]);
-    const float mean_c = centre_on_pivot<NCH>(xh, pivot, lane, A.D) * inv_d;
-    float c1 = 0.0f, c2 = 0.0f;
-#pragma unroll
-    for (int k = 0; k < NCH; ++k) {
-      const int d = (k * kWave + lane) * 4;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float h = d < A.D ? (xh[k][e] - mean_c) * rstd : 0.0f;
-        xh[k][e] = h;
-        c1 += g[k][e];
-        c2 += g[k][e] * h;
-      }
-    }
-    c1 = wave_sum(c1) * inv_d;
-    c2 = wave_sum(c2) * inv_d;
-#pragma unroll
-    for (int k = 0; k < NCH; ++k)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) g[k][e] = rstd * ((g[k][e] - c1) - xh[k][e] * c2);
+    ln_input_grad<NCH>(g, xh, (A.gamma1 && sr.seg) ? A.gamma1 : A.gamma0, A.rstd + row, lane, A.D, inv_d);
     if (A.g_a) {                                            // gradient arriving over the residual path
       load_vec<NCH, NT>(xh, A.g_a + off, lane, A.D);
 #pragma unroll
@@ -219,6 +232,40 @@ __global__ __launch_bounds__(kBlock) void ln_bwd_kernel(LnBwdArgs A) {
       }
       store_vec<NCH>(g, A.dr1 ? (sr.seg ? A.dr1 : A.dr0) + sr.row * A.D : A.dr0 + off, lane, A.D);
     }
+  }
+}
+
+// Post-LN: the gradients reaching y = LN(s) are summed first, in the fixed order (dy_a + dy_b) + g_inj, then ds = LN'(sum).
+struct LnBwdPostArgs {
+  const float *dy_a, *dy_b, *g_inj, *s, *rstd, *gamma;
+  float* ds;
+  int rows, D;
+};
+
+template <int NCH, bool NT>
+__global__ __launch_bounds__(kBlock) void ln_bwd_post_kernel(LnBwdPostArgs A) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x / kWave;
+  const float inv_d = 1.0f / static_cast<float>(A.D);
+  for (int row = blockIdx.x * kRowsPerBlock + wave; row < A.rows; row += gridDim.x * kRowsPerBlock) {
+    const long off = static_cast<long>(row) * A.D;
+    f32x4 xh[NCH], g[NCH];
+    load_vec<NCH, NT>(xh, A.s + off, lane, A.D);
+    load_vec<NCH, NT>(g, A.dy_a + off, lane, A.D);
+    if (A.dy_b) {
+      f32x4 t[NCH];
+      load_vec<NCH, NT>(t, A.dy_b + off, lane, A.D);
+#pragma unroll
+      for (int k = 0; k < NCH; ++k) g[k] = g[k] + t[k];
+    }
+    if (A.g_inj) {                                          // the loss kernel's gradient of this feature map
+      f32x4 t[NCH];
+      load_vec<NCH, NT>(t, A.g_inj + off, lane, A.D);
+#pragma unroll
+      for (int k = 0; k < NCH; ++k) g[k] = g[k] + t[k];
+    }
+    ln_input_grad<NCH>(g, xh, A.gamma, A.rstd + row, lane, A.D, inv_d);
+    store_vec<NCH>(g, A.ds + off, lane, A.D);
   }
 }
 
@@ -373,7 +420,7 @@ int vqa_ln_fwd(const float* x, const float* r0, const float* r1, const float* rs
                float* mean, float* rstd, long rows, int D, long period, long split, float eps, vqa_stream_t stream) {
   clear_stale_error();
   if (!x || !gamma0 || !beta0 || !y0 || !mean || !rstd) return VQA_ERR_NULL;
-  if ((r0 && !x_out) || (r1 && !r0) || (rscale && !r0) || (gamma1 && !beta1)) return VQA_ERR_NULL;
+  if ((r1 && !r0) || (rscale && !r0) || (gamma1 && !beta1)) return VQA_ERR_NULL;
   const int rc = check_rows(rows, D, period, split);
   if (rc != VQA_OK) return rc;
   if ((r1 || y1 || gamma1) && period <= 0) return VQA_ERR_SHAPE;        // a split needs the token layout
@@ -438,6 +485,39 @@ int vqa_ln_bwd(const float* dy0, const float* dy1, const float* x, const float* 
     case 2: ln_bwd_kernel<2, true><<<grid, kBlock, 0, st>>>(A); break;
     case 3: ln_bwd_kernel<3, true><<<grid, kBlock, 0, st>>>(A); break;
     default: ln_bwd_kernel<4, true><<<grid, kBlock, 0, st>>>(A); break;
+  }
+  return launch_status();
+}
+
+int vqa_ln_bwd_post(const float* dy_a, const float* dy_b, const float* g_inj, const float* s, const float* rstd,
+                    const float* gamma, float* ds, long rows, int D, vqa_stream_t stream) {
+  clear_stale_error();
+  if (!dy_a || !s || !rstd || !gamma || !ds) return VQA_ERR_NULL;
+  const int rc = check_rows(rows, D, 0, 0);
+  if (rc != VQA_OK) return rc;
+  const void* ptrs[] = {dy_a, dy_b, g_inj, s, gamma, ds};
+  for (const void* p : ptrs)
+    if (p && !aligned16(p)) return VQA_ERR_ALIGN;
+  if (rows == 0) return VQA_OK;
+  LnBwdPostArgs A{dy_a, dy_b, g_inj, s, rstd, gamma, ds, static_cast<int>(rows), D};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int grid = row_grid(rows);
+#ifdef VQA_TUNING
+  if (!(g_block_nt & 1)) {
+    switch ((D + 255) / 256) {
+      case 1: ln_bwd_post_kernel<1, false><<<grid, kBlock, 0, st>>>(A); break;
+      case 2: ln_bwd_post_kernel<2, false><<<grid, kBlock, 0, st>>>(A); break;
+      case 3: ln_bwd_post_kernel<3, false><<<grid, kBlock, 0, st>>>(A); break;
+      default: ln_bwd_post_kernel<4, false><<<grid, kBlock, 0, st>>>(A); break;
+    }
+    return launch_status();
+  }
+#endif
+  switch ((D + 255) / 256) {
+    case 1: ln_bwd_post_kernel<1, true><<<grid, kBlock, 0, st>>>(A); break;
+    case 2: ln_bwd_post_kernel<2, true><<<grid, kBlock, 0, st>>>(A); break;
+    case 3: ln_bwd_post_kernel<3, true><<<grid, kBlock, 0, st>>>(A); break;
+    default: ln_bwd_post_kernel<4, true><<<grid, kBlock, 0, st>>>(A); break;
   }
   return launch_status();
 }

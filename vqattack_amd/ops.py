@@ -684,6 +684,22 @@ def ln_bwd(dy0, x, mean, rstd, gamma0, dx, dy1=None, gamma1=None, g_a=None, g_in
                                _p(rscale), _p(dx), _p(dr0), _p(dr1), rows, d, period, split, stream_for(x)), "vqa_ln_bwd")
 
 
+def ln_bwd_post(dy_a, s, rstd, gamma, ds, dy_b=None, g_inj=None):
+    """``vqa_ln_bwd_post``: ``ds = LayerNorm'((dy_a + dy_b) + g_inj)`` at the saved pre-LayerNorm sum ``s`` (rows, D) of a
+    post-LN block ``y = LN(s)``, ``s = x + f(x)``; ``ds`` is the gradient of ``x`` over the residual path and of ``f(x)``."""
+    for name, t in (("s", s), ("dy_a", dy_a), ("ds", ds)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("{} must be a contiguous float32 HIP tensor".format(name))
+    rows, d = s.numel() // s.shape[-1], s.shape[-1]
+    for name, t in (("s", s), ("ds", ds), ("dy_a", dy_a), ("dy_b", dy_b), ("g_inj", g_inj)):
+        _rows_ok(name, t, rows * d)
+    _rows_ok("gamma", gamma, d), _rows_ok("rstd", rstd, rows)
+    same_device(dy_a, dy_b, g_inj, s, rstd, gamma, ds)
+    with _on(s):
+        check(lib().vqa_ln_bwd_post(_p(dy_a), _p(dy_b), _p(g_inj), _p(s), _p(rstd), _p(gamma), _p(ds), rows, d,
+                                    stream_for(s)), "vqa_ln_bwd_post")
+
+
 def gelu_fwd(h, out=None):
     dev_f32(h, "h")
     out = torch.empty_like(h) if out is None else out

@@ -1,4 +1,5 @@
-"""Pre-LN transformer encoder of the frozen white boxes WITHOUT an autograd graph inside: library GEMMs, the hand-written
+"""Transformer encoders of the frozen white boxes (pre-LN: VLMo, ALBEF's ViT; post-LN: ALBEF's BERT fusion encoder, second
+half of this file) WITHOUT an autograd graph inside: library GEMMs, the hand-written
 attention (``csrc/attn.hip``) and the fused block glue of ``csrc/block.hip`` -- forward and input-gradient backward written
 out stage by stage.
 
@@ -355,3 +356,271 @@ def encode(x0, spec, biases, n_text):
         raise ops._hip.HipExtensionError("the fused encoder runs on fp32 HIP tensors")
     outs = _Encoder.apply(x0, _Call(spec, biases, n_text))
     return [x0] + list(outs[:-1]), outs[-1]
+
+
+# ------------------------------------------------------------------------------------ post-LN BERT fusion encoder (ALBEF)
+# Reference computation: ``BertLayer.forward`` of ``ALBEF_attack/models/xbert.py`` -- self-attention, ``BertSelfOutput``
+# (LayerNorm(dense(o) + x)), from ``fusion_layer`` up the same pair with the image states as keys / values, then
+# ``BertIntermediate`` (GELU) and ``BertOutput`` (LayerNorm(dense(a) + x)); restated by ``whitebox/albef.py _BertLayer``.
+# A post-LN stage is ``y = LN(s)``, ``s = x + f(x)``: forward ONE ``vqa_ln_fwd`` (r0 = f(x), x_out = s, kept for the
+# backward as the pre-LN path keeps x1), backward ONE ``vqa_ln_bwd_post`` that sums the gradients reaching y first; its
+# result ds is the residual-path gradient and the branch gradient at once.
+#
+# Cross-attention keys / values: the K and V weights of ALL fusion layers are stacked into one [2 D n_fusion, D] weight, so
+# every layer's K / V come from ONE GEMM over the image states (N = 9216 at base size; the attention kernels read the
+# layer's slice of that buffer through strides), and the gradient of the image states is ONE input-gradient GEMM over the
+# stacked dK / dV (K = 9216) instead of twelve GEMMs and eleven accumulation passes: deterministic, fixed order.  Cost:
+# two (B M, 2 D n_fusion) buffers live across the call, 2 x 5.4 GB at batch 256 x 577 tokens.
+class BertLayerSpec:
+    """Frozen parameters of one post-LN BERT layer as plain fp32 device tensors + every weight the text rows multiply
+    packed by ``_pack``: "qkv" (packed self-attention projection), "o", "fc1", "fc2" and, in fusion layers, "q_c" / "o_c"
+    (the cross-attention's query and output projections; its K / V weights live stacked in ``FusionSpec``).  ``cross``:
+    index of this layer among the fusion layers, or None."""
+    __slots__ = ("wqkv", "bqkv", "wo", "bo", "ln_attn", "cross", "wq_c", "bq_c", "wo_c", "bo_c", "ln_cross", "w1", "b1",
+                 "w2", "b2", "ln_out", "packed")
+
+    def __init__(self, layer, cross):
+        a = layer.attn
+        self.wqkv = torch.cat([a.q.weight.detach(), a.k.weight.detach(), a.v.weight.detach()], dim=0).contiguous()
+        self.bqkv = torch.cat([a.q.bias.detach(), a.k.bias.detach(), a.v.bias.detach()], dim=0).contiguous()
+        self.wo, self.bo, self.ln_attn = _c(a.o.weight), _c(a.o.bias), _ln(layer.ln_attn)
+        self.w1, self.b1, self.w2, self.b2 = _mlp(layer.mlp)
+        self.ln_out = _ln(layer.ln_out)
+        self.packed = dict(qkv=_pack(self.wqkv), o=_pack(self.wo), fc1=_pack(self.w1), fc2=_pack(self.w2))
+        self.cross = cross
+        if cross is not None:
+            c = layer.cross
+            self.wq_c, self.bq_c, self.wo_c, self.bo_c = _c(c.q.weight), _c(c.q.bias), _c(c.o.weight), _c(c.o.bias)
+            self.ln_cross = _ln(layer.ln_cross)
+            self.packed["q_c"], self.packed["o_c"] = _pack(self.wq_c), _pack(self.wo_c)
+
+
+class FusionSpec:
+    """``layers``: one BertLayerSpec per layer; ``wkv`` [2 D n_fusion, D] / ``bkv``: rows ``[2 D j, 2 D j + D)`` are the
+    K weight of fusion layer j, the next D rows its V weight."""
+
+    def __init__(self, layers, heads, eps, wkv, bkv):
+        self.layers, self.heads, self.eps, self.wkv, self.bkv = layers, heads, eps, wkv, bkv
+        self.n_fusion = sum(lay.cross is not None for lay in layers)
+        self.first_fusion = next((i for i, lay in enumerate(layers) if lay.cross is not None), len(layers))
+        self.packed_kv = _pack(wkv) if wkv is not None else (None, None)
+
+
+def bert_spec(layers, heads, eps):
+    """ALBEF's BERT layers (``_BertLayer`` modules) -> FusionSpec: the post-LN counterpart of ``vit_spec``."""
+    specs, wkv, bkv = [], [], []
+    for layer in layers:
+        cross = None
+        if layer.cross is not None:
+            cross = len(wkv) // 2
+            wkv += [layer.cross.k.weight.detach(), layer.cross.v.weight.detach()]
+            bkv += [layer.cross.k.bias.detach(), layer.cross.v.bias.detach()]
+        specs.append(BertLayerSpec(layer, cross))
+    return FusionSpec(specs, heads, eps, torch.cat(wkv, dim=0).contiguous() if wkv else None,
+                      torch.cat(bkv, dim=0).contiguous() if bkv else None)
+
+
+class _FusionCall:
+    """Per-call context: the spec, the key-padding bias of the text batch (tensor kept alive, strides) and the caller's
+    grad mode (``Function.forward`` runs with it off and ``needs_input_grad`` only reflects ``requires_grad``)."""
+
+    def __init__(self, spec, bias_t, bstr, grad):
+        self.spec, self.bias_t, self.bstr, self.grad = spec, bias_t, bstr, grad
+
+
+def _kv_slices(buf, j, b, m, heads):
+    """(K, V) of fusion layer j inside a stacked (B M, 2 D n_fusion) buffer, each as a strided (B, M, H, 64) view."""
+    kv = buf.view(b, m, -1, 2, heads, _attn.HEAD_DIM)
+    return kv[:, :, j, 0], kv[:, :, j, 1]
+
+
+def _post_ln(x, branch, ln, eps, save):
+    """y = LN(x + branch); returns (y, (s, rstd) or None).  The sum s is written out only where the backward will read it."""
+    rows, d = x.shape
+    y, s = torch.empty_like(x), (torch.empty_like(x) if save else None)
+    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+    ops.ln_fwd(x, ln[0], ln[1], y, mean, rstd, eps, r0=branch, x_out=s)
+    return y, ((s, rstd) if save else None)
+
+
+def _fusion_forward(x0, img, call, full_from, partial):
+    """Layers ``>= full_from`` keep everything their backward needs; layer ``partial`` (or None) keeps what the path from
+    its output to its cross-attention K / V needs (FFN and cross-attention, not the self-attention)."""
+    spec = call.spec
+    b, t, d = x0.shape
+    rows = b * t
+    heads = spec.heads
+    scale = _attn.HEAD_DIM ** -0.5
+    x = (x0 if x0.is_contiguous() else x0.contiguous()).view(rows, d)
+    kv, m = None, 0
+    if spec.n_fusion:
+        if img is None or img.dim() != 3 or img.shape[0] != b or img.shape[2] != d:
+            raise ValueError("the fusion layers need image states (B = {}, M, D = {}), got {}".format(
+                b, d, None if img is None else tuple(img.shape)))
+        m = img.shape[1]
+        img2 = (img if img.is_contiguous() else img.contiguous()).view(b * m, d)
+        kv = _linear(img2, spec.wkv, spec.bkv, spec.packed_kv)             # K / V of every fusion layer: one GEMM
+    feats, saved = [], []
+    for li, lay in enumerate(spec.layers):
+        full = li >= full_from
+        part = full or li == partial
+        sv = {}
+        qkv = _linear(x, lay.wqkv, lay.bqkv, lay.packed["qkv"])
+        qkv5 = qkv.view(b, t, 3, heads, _attn.HEAD_DIM)
+        o, lse, scores = _attn._forward(qkv5[:, :, 0], qkv5[:, :, 1], qkv5[:, :, 2], call.bias_t, call.bstr, scale,
+                                        save_scores=full)
+        p = _linear(o.view(rows, d), lay.wo, lay.bo, lay.packed["o"])
+        x, st = _post_ln(x, p, lay.ln_attn, spec.eps, full)
+        del p
+        if full:
+            sv.update(qkv=qkv, o=o, lse=lse, scores=scores, ln_attn=st)
+        del qkv, qkv5, o, lse, scores
+        if lay.cross is not None:
+            q = _linear(x, lay.wq_c, lay.bq_c, lay.packed["q_c"]).view(b, t, heads, _attn.HEAD_DIM)
+            k, v = _kv_slices(kv, lay.cross, b, m, heads)
+            o, lse, scores = _attn._forward(q, k, v, None, None, scale, save_scores=part)
+            p = _linear(o.view(rows, d), lay.wo_c, lay.bo_c, lay.packed["o_c"])
+            x, st = _post_ln(x, p, lay.ln_cross, spec.eps, part)
+            del p
+            if part:
+                sv.update(q_c=q, o_c=o, lse_c=lse, scores_c=scores, ln_cross=st)
+            del q, o, lse, scores
+        h = _linear(x, lay.w1, lay.b1, lay.packed["fc1"])
+        a = ops.gelu_fwd(h)
+        f = _linear(a, lay.w2, lay.b2, lay.packed["fc2"])
+        del a
+        x, st = _post_ln(x, f, lay.ln_out, spec.eps, part)
+        del f
+        if part:
+            sv.update(h=h, ln_out=st)
+        del h
+        feats.append(x.view(b, t, d))
+        saved.append(sv if part else None)
+    return feats, saved, kv
+
+
+def _ln_post_grad(summands, st, gamma):
+    """ds = LN'(sum of the one to three gradients reaching y = LN(s)), one kernel."""
+    s, rstd = st
+    ds = torch.empty_like(s)
+    sm = [_dense(g, s) for g in summands if g is not None]
+    ops.ln_bwd_post(sm[0].view(s.shape), s, rstd, gamma, ds, dy_b=sm[1].view(s.shape) if len(sm) > 1 else None,
+                    g_inj=sm[2].view(s.shape) if len(sm) > 2 else None)
+    return ds
+
+
+def _fusion_backward(saved, kv, call, g_feats, g_states, shape, m, need_t, need_i):
+    """``g_feats[l]``: gradient of feature map l + 1 (the output of layer l), ``g_states``: gradient of the final states
+    (the same values as the last feature map); None = no loss on it.  Returns (gradient of the text embeddings or None,
+    gradient of the image states or None)."""
+    spec = call.spec
+    b, t, d = shape
+    rows, heads = b * t, spec.heads
+    scale = _attn.HEAD_DIM ** -0.5
+    n = len(spec.layers)
+    stop = 0 if need_t else spec.first_fusion        # the lowest layer that is back-propagated (only partly unless need_t)
+    if stop >= n:
+        return None, None
+    dev = call.bias_t.device
+    dkv = None
+    if spec.n_fusion:
+        # every fusion layer's dK / dV side by side (one input-gradient GEMM afterwards) when the image states need a
+        # gradient; otherwise one layer's worth of room the attention backward writes and nobody reads
+        dkv = torch.empty(b * m, 2 * d * (spec.n_fusion if need_i else 1), dtype=torch.float32, device=dev)
+    inc = [g_states, None, g_feats[n - 1]]           # the gradients reaching the output of the layer at hand
+    for li in range(n - 1, stop - 1, -1):
+        lay, sv = spec.layers[li], saved[li]
+        if not any(g is not None for g in inc):      # no loss above this layer: nothing flows, its dK / dV are zero
+            if lay.cross is not None and need_i:
+                dk, dv = _kv_slices(dkv, lay.cross, b, m, heads)
+                dk.zero_(), dv.zero_()
+            inc = [None, None, g_feats[li - 1] if li > 0 else None]
+            saved[li] = None
+            continue
+        ds = _ln_post_grad(inc, sv["ln_out"], lay.ln_out[0])              # d(x + ffn(x)): residual path and branch
+        da = _linear_grad(ds, lay.w2, lay.packed["fc2"])
+        ops.gelu_bwd(sv["h"], da)                                        # in place: dh
+        dx = _linear_grad(da, lay.w1, lay.packed["fc1"])
+        del da
+        inc = [ds, dx, None]
+        if lay.cross is not None:
+            ds = _ln_post_grad(inc, sv["ln_cross"], lay.ln_cross[0])
+            do = _linear_grad(ds, lay.wo_c, lay.packed["o_c"])
+            k, v = _kv_slices(kv, lay.cross, b, m, heads)
+            dk, dv = _kv_slices(dkv, lay.cross if need_i else 0, b, m, heads)
+            dq = torch.empty(b, t, heads, _attn.HEAD_DIM, dtype=torch.float32, device=dev)
+            _attn._backward(sv["q_c"], k, v, None, None, sv["o_c"], sv["lse_c"], do.view(b, t, heads, _attn.HEAD_DIM),
+                            dq, dk, dv, scale, scores=sv["scores_c"])
+            del do
+            if li == stop and not need_t:            # the image states are reached; nothing below needs a gradient
+                saved[li] = None
+                break
+            dx = _linear_grad(dq.view(rows, d), lay.wq_c, lay.packed["q_c"])
+            del dq
+            inc = [ds, dx, None]
+        ds = _ln_post_grad(inc, sv["ln_attn"], lay.ln_attn[0])
+        do = _linear_grad(ds, lay.wo, lay.packed["o"])
+        dqkv = torch.empty_like(sv["qkv"])
+        qkv5, dqkv5 = sv["qkv"].view(b, t, 3, heads, _attn.HEAD_DIM), dqkv.view(b, t, 3, heads, _attn.HEAD_DIM)
+        _attn._backward(qkv5[:, :, 0], qkv5[:, :, 1], qkv5[:, :, 2], call.bias_t, call.bstr, sv["o"], sv["lse"],
+                        do.view(b, t, heads, _attn.HEAD_DIM), dqkv5[:, :, 0], dqkv5[:, :, 1], dqkv5[:, :, 2], scale,
+                        scores=sv["scores"])
+        del do
+        dx = _linear_grad(dqkv, lay.wqkv, lay.packed["qkv"])
+        del dqkv, qkv5, dqkv5
+        inc = [ds, dx, g_feats[li - 1] if li > 0 else None]
+        saved[li] = None                              # this layer's activations are dead
+    g_text = g_img = None
+    if need_t:
+        g_text = torch.add(inc[0], inc[1]).view(b, t, d) if inc[0] is not None else \
+            torch.zeros(b, t, d, dtype=torch.float32, device=dev)
+    if need_i and spec.n_fusion:
+        g_img = _linear_grad(dkv, spec.wkv, spec.packed_kv).view(b, m, d)   # one GEMM over the stacked dK / dV
+    return g_text, g_img
+
+
+class _FusionEncoder(torch.autograd.Function):
+    """(text embeddings (B, T, D), image states (B, M, D), call) -> (feature map 1, ..., feature map L, final states).
+    The backward needs none of the Function's inputs or outputs (a post-LN stage keeps its pre-LayerNorm sum instead of
+    the layer input), so everything it keeps is private to the call and is freed layer by layer."""
+
+    @staticmethod
+    def forward(ctx, text_embeds, image_states, call):
+        ctx.set_materialize_grads(False)
+        need_t = call.grad and ctx.needs_input_grad[0]
+        need_i = call.grad and ctx.needs_input_grad[1] and call.spec.n_fusion > 0
+        n = len(call.spec.layers)
+        full_from = 0 if need_t else (call.spec.first_fusion + 1 if need_i else n)
+        partial = call.spec.first_fusion if (need_i and not need_t) else None
+        feats, saved, kv = _fusion_forward(text_embeds.detach(), None if image_states is None else image_states.detach(),
+                                           call, full_from, partial)
+        ctx.call, ctx.saved, ctx.kv, ctx.need = call, saved, (kv if need_t or need_i else None), (need_t, need_i)
+        ctx.shape, ctx.m = tuple(text_embeds.shape), 0 if image_states is None else image_states.shape[1]
+        return tuple(feats) + (feats[-1].view_as(feats[-1]),)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        saved, kv, ctx.saved, ctx.kv = ctx.saved, ctx.kv, None, None
+        if saved is None:
+            raise RuntimeError("the fused encoder's backward ran twice (its activations are freed by the first run)")
+        g_text, g_img = _fusion_backward(saved, kv, ctx.call, grads[:-1], grads[-1], ctx.shape, ctx.m, *ctx.need)
+        return g_text, g_img, None
+
+
+def encode_fusion(text_embeds, text_masks, image_states, spec):
+    """ALBEF's BERT fusion encoder on the text embeddings (B, T, D) with cross-attention into ``image_states`` (B, M, D)
+    from the first fusion layer up; ``text_masks`` (B, T): 0 = padding (masked as a key of the self-attention; the
+    cross-attention has no mask).  Returns ``([text_embeds, feature maps 1..L], final states)`` like the eager layer
+    loop.  No host read or synchronisation: a graph capture of the attack step records it."""
+    for name, ten in (("text_embeds", text_embeds), ("image_states", image_states)):
+        if ten is not None and (not ten.is_cuda or ten.dtype != torch.float32 or ten.device != text_embeds.device):
+            raise ops._hip.HipExtensionError("the fused encoder runs on fp32 HIP tensors of one device ({})".format(name))
+    if text_masks.device != text_embeds.device:
+        raise ops._hip.HipExtensionError("the fused encoder runs on fp32 HIP tensors of one device (text_masks)")
+    b, t, _ = text_embeds.shape
+    pad = torch.zeros(b, 1, 1, t, device=text_embeds.device)
+    pad = pad.masked_fill(~text_masks.bool()[:, None, None, :], float("-inf"))
+    bias_t, bstr = _attn._bias_view(pad, b, spec.heads, t, t)
+    outs = _FusionEncoder.apply(text_embeds, image_states, _FusionCall(spec, bias_t, bstr, torch.is_grad_enabled()))
+    return [text_embeds] + list(outs[:-1]), outs[-1]

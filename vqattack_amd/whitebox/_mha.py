@@ -42,6 +42,8 @@ def mha(q, k, v, bias=None):
         return _attn.attention(_pad(q), _pad(k), _pad(v), bias, scale=d ** -0.5)[..., :d]
     if isinstance(bias, _attn.KeyHoleBias):
         bias = bias.dense()
+    if bias is not None and bias.dtype != q.dtype:      # the library attention misreads an fp32 bias beside fp64 operands
+        bias = bias.to(q.dtype)
     o = F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), attn_mask=bias)
     return o.transpose(1, 2)
 

@@ -166,9 +166,13 @@ class FrozenAlbef(nn.Module):
         # the ViT (577 of the <= 617 tokens of a pair) runs on whitebox/_fused.py on the GPU; see FrozenVlmo
         self.fused_blocks = os.environ.get("VQA_FUSED_BLOCKS", "1") != "0"
         self._fused_spec = None
+        # the BERT fusion encoder (text_encoder) has the same path (_fused.encode_fusion), switched on its own:
+        # VQA_FUSED_TEXT=1 or fused_text = True.  Off by default: DESIGN section 5 gives the rule for switching it on
+        self.fused_text = os.environ.get("VQA_FUSED_TEXT", "0") == "1"
+        self._fused_text_spec = None
 
     def _apply(self, fn, *args, **kwargs):
-        self._fused_spec = None
+        self._fused_spec = self._fused_text_spec = None
         return super()._apply(fn, *args, **kwargs)
 
     def _init(self, seed):
@@ -215,7 +219,7 @@ class FrozenAlbef(nn.Module):
     def invalidate_fused(self):
         """Drop the cached fused-encoder spec: the next pass rebuilds it from the current weights.  Needed only after
         weight updates ``_fused.weights_key`` cannot see (writes through ``p.data``)."""
-        self._fused_spec = None
+        self._fused_spec = self._fused_text_spec = None
 
     # ---- reference checkpoints ------------------------------------------------------------------------------
     def load_reference_state_dict(self, state_dict, strict=True):
@@ -301,6 +305,13 @@ class FrozenAlbef(nn.Module):
         return ids_cpu.to(ids.device)
 
     def text_encoder(self, text_embeds, text_masks, image_states):
+        if self.fused_text and text_embeds.is_cuda and text_embeds.dtype == torch.float32 and \
+                _fused.supported(self.cfg.dim, self.cfg.heads):
+            key = _fused.weights_key(self.bert_layers)
+            if self._fused_text_spec is None or self._fused_text_spec[0] != key:   # the spec holds packed COPIES
+                self._fused_text_spec = (key, _fused.bert_spec(self.bert_layers, self.cfg.heads, self.cfg.bert_ln_eps))
+            feats, states = _fused.encode_fusion(text_embeds, text_masks, image_states, self._fused_text_spec[1])
+            return states, feats
         pad = torch.zeros(text_masks.shape[0], 1, 1, text_masks.shape[1], device=text_embeds.device)
         pad = pad.masked_fill(~text_masks.bool()[:, None, None, :], float("-inf"))
         x = text_embeds
