@@ -404,6 +404,16 @@ int vqa_gemm_pack_b(const float* w, long ldw, int trans, void* packed, int K, in
 int vqa_gemm_bf16x6(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M, int N,
                     int K, vqa_stream_t stream);
 
+/* vqa_gemm_bf16x6_tile: vqa_gemm_bf16x6 with the output tile of a workgroup chosen by the caller; argument rules and
+ *   return codes of vqa_gemm_bf16x6, any other tile value VQA_ERR_SHAPE.  VQA_GEMM_TILE_256X128 is vqa_gemm_bf16x6
+ *   itself.  VQA_GEMM_TILE_128X256 splits half as much of A per product (every A value is split by N / 256 workgroups
+ *   instead of N / 128) and needs N % 256 == 0; for every other N it runs the 256 x 128 tile.  Same packed operand, same
+ *   product and k-step order: both tiles give every output the same bits. */
+#define VQA_GEMM_TILE_256X128 0
+#define VQA_GEMM_TILE_128X256 1
+int vqa_gemm_bf16x6_tile(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M,
+                         int N, int K, int tile, vqa_stream_t stream);
+
 /* vqa_gemm_bf16x6_small: the same product from the same packed operand on 64 x 128 output tiles, for row counts whose
  *   256 x 128 tiles cannot fill the device, with an optional deterministic split over K.  Argument rules and return
  *   codes of vqa_gemm_bf16x6; 1 <= ksplit <= min(K / 32, 16), else VQA_ERR_SHAPE.  With nk = K / 32 k-steps, part p covers

@@ -1,6 +1,7 @@
-"""Per-shape A/B of the encoder GEMMs: the bf16x6 kernel (``csrc/gemm.hip``) and its small-tile variant (one record per
-``--ksplit`` value, plus the split ``ops.gemm_small_plan`` picks) against the library fp32 GEMM that ``torch.addmm`` /
-``torch.mm`` run (with the recorded TunableOp solutions active, as in bench.py).
+"""Per-shape A/B of the encoder GEMMs: the bf16x6 kernel (``csrc/gemm.hip``) on its 256 x 128 tile ("kernel"), on its
+128 x 256 tile ("wide", where N % 256 == 0) and its small-tile variant (one record per ``--ksplit`` value, plus the split
+``ops.gemm_small_plan`` picks) against the library fp32 GEMM that ``torch.addmm`` / ``torch.mm`` run (with the recorded
+TunableOp solutions active, as in bench.py).
 
 Random data (activations ~ N(0, 1), weights ~ N(0, 0.02^2)): bf16 MFMA loops hold a lower clock on random data than on
 zeros.  The variants are interleaved in one process over several rounds; per shape the median and min time per call, the
@@ -23,7 +24,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vqattack_amd import ops  # noqa: E402
-from vqattack_amd.whitebox import tuned_gemms  # noqa: E402
+from vqattack_amd.whitebox import _fused, tuned_gemms  # noqa: E402
 
 # (dim, ffn, rows per sample, text rows per sample (0 = one modality), batch)
 MODELS = {"vlmo_base": (768, 3072, 591, 40, 64), "albef_base": (768, 3072, 577, 0, 256),
@@ -81,7 +82,7 @@ def main():
         out_l = torch.empty(M, N, device=dev)
 
         def run_kernel():
-            ops.gemm(a, packed, bias, out=out_k)
+            ops.gemm(a, packed, bias, out=out_k, tile="large")
 
         def run_library():
             if bias is not None:
@@ -90,14 +91,18 @@ def main():
                 torch.mm(a, bt, out=out_l)
 
         variants = [("kernel", run_kernel), ("library", run_library)]
+        out_w = torch.empty(M, N, device=dev)
+        if N % 256 == 0:
+            variants.append(("wide", lambda: ops.gemm(a, packed, bias, out=out_w, tile="wide")))
         planned = ops.gemm_small_plan(M, N, K)
         small = sorted({k for k in ksplits + [planned] if 1 <= k <= min(K // 32, 16)}) if ksplits else []
         out_s = torch.empty(M, N, device=dev)
         for k in small:
             variants.append(("small%d" % k, lambda k=k: ops.gemm_small(a, packed, bias, out=out_s, ksplit=k)))
         times = {key: [] for key, _ in variants}
-        for _, fn in variants:                      # warm-up
-            fn()
+        for _ in range(3):                          # warm-up: code objects, then the clock the timed rounds run at
+            for _, fn in variants:
+                fn()
         torch.cuda.synchronize()
         graphs = {}
         if args.graph:
@@ -134,6 +139,15 @@ def main():
             small_rows.append(dict(ksplit=k, planned=k == planned, ms_median=statistics.median(ts), ms_min=min(ts),
                                    ms_spread=max(ts) - min(ts), err_max=es[0], err_rms=es[1],
                                    speedup_vs_library_median=statistics.median(times["library"]) / statistics.median(ts)))
+        wide = None
+        if "wide" in times:
+            ops.gemm(a, packed, bias, out=out_w, tile="wide")
+            torch.cuda.synchronize()
+            ew, tw = err(out_w, ref), times["wide"]
+            wide = dict(ms_median=statistics.median(tw), ms_min=min(tw), ms_spread=max(tw) - min(tw), err_max=ew[0],
+                        err_rms=ew[1], same_bits_as_kernel=bool(torch.equal(out_w, out_k)),
+                        speedup_vs_kernel_median=statistics.median(times["kernel"]) / statistics.median(tw),
+                        bf16_mfma_tflops=12.0 * M * N * K / statistics.median(tw) / 1e9)
         del ref, graphs
         med_k, med_l = statistics.median(times["kernel"]), statistics.median(times["library"])
         flop = 2.0 * M * N * K
@@ -146,10 +160,11 @@ def main():
                    kernel_ms_spread=max(times["kernel"]) - min(times["kernel"]),
                    library_ms_spread=max(times["library"]) - min(times["library"]),
                    big_workgroups=ops.gemm_workgroups(M, N), small_tiles=ops.gemm_small_workgroups(M, N), small=small_rows,
+                   wide=wide, policy_tile=_fused.gemm_tile(M, N, K),
                    kernel_err_max=ek[0], kernel_err_rms=ek[1], library_err_max=el[0], library_err_rms=el[1])
         print(json.dumps(row), flush=True)
         results.append(row)
-        del a, w, packed, out_k, out_l, out_s
+        del a, w, packed, out_k, out_l, out_s, out_w
         torch.cuda.empty_cache()
     summary = dict(model=args.model, batch=args.batch or MODELS[args.model][4], tuned_gemms=tuned, device=torch.cuda.get_device_name(),
                    rounds=args.rounds, reps=args.reps, graph=args.graph, shapes=results)
@@ -162,6 +177,12 @@ def main():
         print("{:<20}{:>10.3f}{:>11.1f}{:>9.0f}{:>8.1f}  {:.2e}/{:.2e}".format(
             r["shape"], r["speedup_median"], r["kernel_fp32eq_tflops"], r["kernel_bf16_mfma_tflops"],
             r["library_tflops"], r["kernel_err_max"], r["library_err_max"]))
+        if r["wide"]:
+            wd = r["wide"]
+            print("  wide tile {}   {:>8.3f}x kernel   {:.4f} ms (spread {:.4f}; kernel {:.4f} spread {:.4f})  bf16 {:.0f} TF  "
+                  "bits {}".format("*" if r["policy_tile"] == "wide" else " ", wd["speedup_vs_kernel_median"],
+                                   wd["ms_median"], wd["ms_spread"], r["kernel_ms_median"], r["kernel_ms_spread"],
+                                   wd["bf16_mfma_tflops"], "equal" if wd["same_bits_as_kernel"] else "DIFFER"))
         for sm in r["small"]:
             print("  small ksplit {:<2}{} {:>8.3f}x library  {:.4f} ms (spread {:.4f}; library {:.4f} spread {:.4f})  err {:.2e}"
                   .format(sm["ksplit"], "*" if sm["planned"] else " ", sm["speedup_vs_library_median"], sm["ms_median"],

@@ -180,6 +180,126 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_kernel(GemmArgs g) {
   }
 }
 
+// ---- wide-tile variant: 128 x 256 outputs per workgroup, half the in-loop split work per MFMA ---------------------
+// A workgroup splits BM x 32 values of A per k-step for BM x BN outputs, so every A value is split by N / BN
+// workgroups; the split is most of the loop's non-MFMA vector work.  With the tile turned on its side (8 waves as 2 along
+// M x 4 along N, 64 x 64 each as above) a thread splits ONE (row, 8-k) piece of A per k-step instead of two and copies
+// 6 x 16 B of packed B instead of 3.  Same LDS footprint (A 8 m-tiles x 3 planes + B 16 n-tiles x 3 planes = 72 KiB per
+// stage), same 24 fragment reads and 96 MFMAs per wave and k-step, same grid size, same packed B (the 16 n-tiles x 3
+// planes of a k-step are one contiguous 48 KiB run), same split, same product and k-step order: every output has the
+// bits of gemm_bf16x6_kernel.  Needs N % 256 == 0.
+constexpr int kWideBM = 128, kWideBN = 256;
+constexpr int kWideMT = kWideBM / 16, kWideNT = kWideBN / 16;          // 8 m-tiles, 16 n-tiles per workgroup
+constexpr int kWideABytes = kWideMT * 3 * kTileBytes;                  // 24 KiB
+constexpr int kWideBBytes = kWideNT * 3 * kTileBytes;                  // 48 KiB
+constexpr int kWideStage = kWideABytes + kWideBBytes;                  // 72 KiB
+constexpr int kWideBPieces = kWideBBytes / 16 / kGemmThreads;          // 6 x 16 B of B per thread and k-step
+constexpr int kWideLoadPair = 12;                                      // MFMAs behind each pair of global loads of the next step
+
+__global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_kernel(GemmArgs g) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * kWideStage];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 2, wn = wave & 3;                 // this wave's 64 x 64 output block
+  const int ntb = g.N / kWideBN;
+  const int mtb = static_cast<int>((g.M + kWideBM - 1) / kWideBM);
+  // XCD remap as above
+  const int nwg = mtb * ntb, orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, rem = nwg & 7;
+  const int wg = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (orig >> 3);
+  const int mb = wg / ntb, nb = wg - mb * ntb;
+  const long m0 = static_cast<long>(mb) * kWideBM;
+  const int n0 = nb * kWideBN;
+  const int nk = g.K / kGemmBK;
+  const int nt16 = g.N / 16;
+
+  // staging: this thread splits one (row, 8-k chunk) piece of A per k-step -- m-tile wave, row lane & 15, chunk
+  // lane >> 4 -- and copies 6 x 16 B of packed B
+  long r = m0 + wave * 16 + (lane & 15);
+  r = r < g.M ? r : g.M - 1;
+  const float* arow = g.A + r * g.lda + 8 * (lane >> 4);
+  const bf16x8* bsrc = g.B + static_cast<size_t>(nb) * kWideNT * 3 * 64;
+  const size_t bstep = static_cast<size_t>(nt16) * 3 * 64;            // bf16x8 per k-step of packed B
+
+  f32x4 ra[2];
+  bf16x8 rb[kWideBPieces];
+  auto load = [&](int kt) {
+    ra[0] = *reinterpret_cast<const f32x4*>(arow + kt * kGemmBK);
+    ra[1] = *reinterpret_cast<const f32x4*>(arow + kt * kGemmBK + 4);
+#pragma unroll
+    for (int p = 0; p < kWideBPieces; ++p) rb[p] = bsrc[kt * bstep + p * kGemmThreads + tid];
+  };
+  auto store = [&](int s) {
+    char* base = smem + s * kWideStage;
+    bf16x8 p0, p1, p2;
+    split8(ra[0], ra[1], p0, p1, p2);
+    bf16x8* dst = reinterpret_cast<bf16x8*>(base) + wave * 3 * 64 + lane;
+    dst[0] = p0;
+    dst[64] = p1;
+    dst[128] = p2;
+    bf16x8* bdst = reinterpret_cast<bf16x8*>(base + kWideABytes);
+#pragma unroll
+    for (int p = 0; p < kWideBPieces; ++p) bdst[p * kGemmThreads + tid] = rb[p];
+  };
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+  load(0);
+  store(0);
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const int cur = kt & 1;
+    load(kt + 1 < nk ? kt + 1 : kt);          // the last step reloads its own tile into the idle buffer: no branch
+    const bf16x8* sa = reinterpret_cast<const bf16x8*>(smem + cur * kWideStage) + wm * 4 * 3 * 64 + lane;
+    const bf16x8* sb = reinterpret_cast<const bf16x8*>(smem + cur * kWideStage + kWideABytes) + wn * 4 * 3 * 64 + lane;
+    bf16x8 fa[3][4], fb[3][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int p = 0; p < 3; ++p) {
+        fa[p][i] = sa[(i * 3 + p) * 64];
+        fb[p][i] = sb[(i * 3 + p) * 64];
+      }
+    constexpr int kPa[6] = {2, 1, 0, 1, 0, 0}, kPb[6] = {0, 1, 2, 0, 1, 0};   // the order of gemm_bf16x6_kernel
+#pragma unroll
+    for (int t = 0; t < 6; ++t) {
+      if (t == 3) store(cur ^ 1);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kPa[t]][i], fb[kPb[t]][j], acc[i][j], 0, 0, 0);
+    }
+    // placement of the 8 global loads: a pair per kWideLoadPair MFMAs over the first half of the step (the A pair
+    // first; the split needs it at t == 3).  Measured 5.7-7.6 % faster than all eight ahead of the first MFMA, as
+    // gemm_bf16x6_kernel has them (profiles/r10/README.md); that is consistent with every wave of the workgroup waiting
+    // in the vector-memory issue queue right after the barrier before any of them reaches its MFMAs, which was not
+    // measured directly.  The group barriers are hints: tests/test_gemm_wide.py checks where the loads land
+#pragma unroll
+    for (int n = 0; n < (2 + kWideBPieces) / 2; ++n) {
+      __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);                  // two vector-memory reads
+      __builtin_amdgcn_sched_group_barrier(0x008, kWideLoadPair, 0);      // kWideLoadPair MFMAs
+    }
+    __syncthreads();
+  }
+
+  // epilogue: accumulator register r of tile (i, j) is row (lane >> 4) * 4 + r, column lane & 15
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int col = n0 + wn * 64 + j * 16 + (lane & 15);
+    const float bv = g.bias ? g.bias[col] : 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        const long row = m0 + wm * 64 + i * 16 + (lane >> 4) * 4 + rr;
+        if (row < g.M) g.C[row * g.ldc + col] = g.bias ? acc[i][j][rr] + bv : acc[i][j][rr];
+      }
+  }
+}
+
 // ---- small-tile variant for grids the 256 x 128 tile cannot fill (a few hundred rows, or a narrow N) ---------------
 // Same packed B, same split, same product and k-step order, so with ksplit == 1 every output has the bits of
 // gemm_bf16x6_kernel.  Tile: 64 x 128 outputs per workgroup of 4 waves (2 along M x 2 along N, 32 x 64 each = 2 x 4 MFMA
@@ -377,6 +497,26 @@ int vqa_gemm_bf16x6(const float* A, long lda, const void* packed, const float* b
   GemmArgs g{A, static_cast<const bf16x8*>(packed), bias, C, lda, ldc, M, N, K};
   const int grid = static_cast<int>((M + kGemmBM - 1) / kGemmBM * (N / kGemmBN));
   gemm_bf16x6_kernel<<<grid, kGemmThreads, 0, static_cast<hipStream_t>(stream)>>>(g);
+  return launch_status();
+}
+
+int vqa_gemm_bf16x6_tile(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M,
+                         int N, int K, int tile, vqa_stream_t stream) {
+  if (tile != VQA_GEMM_TILE_256X128 && tile != VQA_GEMM_TILE_128X256) {
+    clear_stale_error();
+    return VQA_ERR_SHAPE;
+  }
+  // the wide tile stages 16 n-tiles per workgroup: every other N runs the 256 x 128 kernel (same bits)
+  if (tile == VQA_GEMM_TILE_256X128 || N <= 0 || N % kWideBN) return vqa_gemm_bf16x6(A, lda, packed, bias, C, ldc, M, N, K, stream);
+  clear_stale_error();
+  if (!A || !packed || !C) return VQA_ERR_NULL;
+  if (M < 0 || K <= 0 || K % kGemmBK || lda < K || lda % 4 || ldc < N) return VQA_ERR_SHAPE;
+  if ((M + kWideBM - 1) / kWideBM * (N / kWideBN) > 0x7fffffffL) return VQA_ERR_SHAPE;
+  if (!aligned16(A) || !aligned16(packed) || !aligned4(C) || (bias && !aligned4(bias))) return VQA_ERR_ALIGN;
+  if (M == 0) return VQA_OK;
+  GemmArgs g{A, static_cast<const bf16x8*>(packed), bias, C, lda, ldc, M, N, K};
+  const int grid = static_cast<int>((M + kWideBM - 1) / kWideBM * (N / kWideBN));
+  gemm_bf16x6_wide_kernel<<<grid, kGemmThreads, 0, static_cast<hipStream_t>(stream)>>>(g);
   return launch_status();
 }
 

@@ -756,9 +756,23 @@ def gemm_pack(w, trans):
     return PackedWeight(data, K, N)
 
 
-def gemm(a, packed, bias=None, out=None):
+GEMM_TILES = {"large": 0, "wide": 1}      # VQA_GEMM_TILE_256X128, VQA_GEMM_TILE_128X256 of include/vqattack_hip.h
+
+
+def gemm(a, packed, bias=None, out=None, tile=None):
     """``out = a @ B (+ bias)`` on the bf16 matrix pipe (bf16x6, fp32-grade), B a ``PackedWeight``.  ``a``: fp32 (M, K)
-    with unit column stride and a row stride that is a multiple of 4 floats."""
+    with unit column stride and a row stride that is a multiple of 4 floats.  ``tile``: the output tile of a workgroup,
+    "large" (256 x 128) or "wide" (128 x 256: half the in-loop split work; N % 256 == 0, any other N runs "large");
+    both give the same bits.  None = what ``whitebox/_fused.py`` records for the shape (``gemm_tile``)."""
+    if tile is None:
+        from .whitebox import _fused
+        tile = _fused.gemm_tile(a.shape[0], packed.N, packed.K)
+    if tile not in GEMM_TILES:
+        raise ValueError("tile must be one of {}, got {!r}".format(sorted(GEMM_TILES), tile))
+    return _gemm_tiled(a, packed, bias, out, tile)
+
+
+def _gemm_tiled(a, packed, bias, out, tile):
     dev_f32(a, "a", contiguous=False)
     if a.dim() != 2 or a.shape[1] != packed.K or a.stride(1) != 1 or a.stride(0) % 4:
         raise ValueError("a must be (M, {}) with unit column stride and a row stride % 4 == 0, got shape {} strides {}"
@@ -774,8 +788,8 @@ def gemm(a, packed, bias=None, out=None):
     same_device(a, packed.data, bias, out)
     if M:
         with _on(a):
-            check(lib().vqa_gemm_bf16x6(_p(a), a.stride(0), _p(packed.data), ptr(bias), _p(out), packed.N, M, packed.N,
-                                        packed.K, stream_for(a)), "vqa_gemm_bf16x6")
+            check(lib().vqa_gemm_bf16x6_tile(_p(a), a.stride(0), _p(packed.data), ptr(bias), _p(out), packed.N, M, packed.N,
+                                             packed.K, GEMM_TILES[tile], stream_for(a)), "vqa_gemm_bf16x6_tile")
     return out
 
 

@@ -42,12 +42,36 @@ MIN_WORKGROUPS = 192
 # taken, so it is not dispatched: the policy is empty and the unset VQA_GEMM behaves as "large".
 SMALL_POLICY = {}
 
+# From MIN_WORKGROUPS up, ops.gemm runs one of two output tiles with the same bits: 256 x 128, or 128 x 256 ("wide":
+# half the in-loop split work per product, N % 256 == 0).  A shape class (N, K) -> (fewest rows, most rows), both
+# inclusive, is listed here only by the rule of SMALL_POLICY: the wide tile's median in tools/gemm_bench.py beat the
+# 256 x 128 tile's by more than the round-to-round spread of either in the same record (profiles/r10/README.md), and
+# the benchmark with the entries in place beat the one without.  VQA_GEMM=large / VQA_GEMM=wide force one tile everywhere.
+# Recorded at 35264 and 37824 rows (VLMO-base, batch 64; (768, 768) at 37824 only): 1.07-1.10x.  The range spans the two
+# measured row counts; the benchmark's own row counts (text trimmed to its longest question) lie between them.  Not
+# listed: the qkv classes (2304, 768) and (768, 2304) -- 1.08-1.10x at the median in both gemm_bench records, but the
+# 256 x 128 kernel's own max - min (0.07-0.09 ms) exceeds the margin (0.06-0.07 ms), so they fail the rule; the text
+# expert's 2560 x 3072 x 768 (240 workgroups; one of its two shapes fails the margin); ALBEF-base's 147712 rows (not
+# measured).
+_WIDE_ROWS = (35264, 37824)
+WIDE_POLICY = {(768, 768): _WIDE_ROWS, (3072, 768): _WIDE_ROWS, (768, 3072): _WIDE_ROWS}
+
 
 def _mode():
-    """VQA_GEMM: "library" = the library everywhere, "large" = the big kernel from MIN_WORKGROUPS up and the library below,
-    "small" = as "large" plus the small kernel for every covered shape below, anything else = the measured policy."""
+    """VQA_GEMM: "library" = the library everywhere, "large" = the 256 x 128 kernel from MIN_WORKGROUPS up and the library
+    below, "wide" = as "large" on the 128 x 256 tile (where N % 256 == 0), "small" = as "large" plus the small kernel for
+    every covered shape below, anything else = the measured policies."""
     mode = os.environ.get("VQA_GEMM", "")
-    return mode if mode in ("library", "large", "small") else ""
+    return mode if mode in ("library", "large", "wide", "small") else ""
+
+
+def gemm_tile(rows, n, k):
+    """The output tile ops.gemm runs (rows, n, k) with where the caller names none: "wide" or "large"."""
+    mode = _mode()
+    if mode == "wide":
+        return "wide"
+    lo, hi = WIDE_POLICY.get((n, k), (1, 0))
+    return "wide" if mode == "" and lo <= rows <= hi else "large"
 
 
 def _kernel_gemms():
