@@ -427,6 +427,28 @@ size_t vqa_gemm_small_ws_bytes(long M, int N, int ksplit);
 int vqa_gemm_bf16x6_small(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M,
                           int N, int K, int ksplit, void* ws, vqa_stream_t stream);
 
+/* vqa_gemm_bf16x6_epi: vqa_gemm_bf16x6_tile with the FFN's GELU, or the product with its derivative, applied to the
+ *   accumulators in the GEMM's epilogue -- the activation of the reference's Mlp.forward (x = self.act(self.fc1(x)),
+ *   VLMO_VQAttack/vlmo/modules/multiway_transformer.py:36-55; ALBEF_attack/models/vit.py Mlp) and of BertIntermediate
+ *   (ALBEF_attack/models/xbert.py: intermediate_act_fn(dense(hidden_states))) without the pass over the pre-activation
+ *   that vqa_gelu_fwd / vqa_gelu_bwd make.  Same prologue, k-loop, packed operand and product order as the unfused
+ *   kernels; the GELU arithmetic is vqa_gelu_fwd's / vqa_gelu_bwd's, so every output has the bits of the two-step form.
+ *   VQA_GEMM_EPI_NONE: vqa_gemm_bf16x6_tile itself (aux, ldaux ignored).
+ *   VQA_GEMM_EPI_GELU: h = acc (+ bias);  aux[row * ldaux + col] = h where aux != NULL;  C = gelu(h).
+ *   VQA_GEMM_EPI_GELU_GRAD: C = (acc (+ bias)) * gelu'(aux[row * ldaux + col]);  aux (the forward's h, read only) is
+ *     required: NULL -> VQA_ERR_NULL.
+ *   Argument rules and return codes of vqa_gemm_bf16x6_tile (VQA_GEMM_TILE_128X256 with N % 256 != 0 runs the fused
+ *   256 x 128 kernel), and: any other epilogue VQA_ERR_SHAPE; aux given with ldaux < N VQA_ERR_SHAPE; aux not 4-byte
+ *   aligned VQA_ERR_ALIGN; M == 0 VQA_OK.  aux must not overlap C or A: rows >= M of aux are neither read nor written,
+ *   but nothing orders one workgroup's stores against another's loads.  Only pointer equality is detected: aux == C
+ *   or aux == A returns VQA_ERR_SHAPE (a return code of this entry point alone; vqa_gemm_bf16x6_tile has no such
+ *   operand).  Never allocates, never synchronises. */
+#define VQA_GEMM_EPI_NONE 0
+#define VQA_GEMM_EPI_GELU 1
+#define VQA_GEMM_EPI_GELU_GRAD 2
+int vqa_gemm_bf16x6_epi(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M,
+                        int N, int K, int tile, int epilogue, float* aux, long ldaux, vqa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,10 @@
 """Per-shape A/B of the encoder GEMMs: the bf16x6 kernel (``csrc/gemm.hip``) on its 256 x 128 tile ("kernel"), on its
 128 x 256 tile ("wide", where N % 256 == 0) and its small-tile variant (one record per ``--ksplit`` value, plus the split
 ``ops.gemm_small_plan`` picks) against the library fp32 GEMM that ``torch.addmm`` / ``torch.mm`` run (with the recorded
-TunableOp solutions active, as in bench.py).
+TunableOp solutions active, as in bench.py).  For the shapes whose N is the FFN width (fc1 forward, fc2 input gradient) the
+GELU epilogues of ``ops.gemm(..., epilogue=)`` are timed as further interleaved variants against the two-step form they
+replace, on the tile the policy picks for the shape: "fused_gelu" (h stored) and "fused_gelu_nosave" against
+"pair_gelu" (GEMM + ``vqa_gelu_fwd``), "fused_gelu_grad" against "pair_gelu_grad" (GEMM + ``vqa_gelu_bwd`` in place).
 
 Random data (activations ~ N(0, 1), weights ~ N(0, 0.02^2)): bf16 MFMA loops hold a lower clock on random data than on
 zeros.  The variants are interleaved in one process over several rounds; per shape the median and min time per call, the
@@ -45,6 +48,11 @@ def shapes(model, batch=0):
         out += [("fc1_fwd_" + tag, m, f, d, True), ("fc1_bwd_" + tag, m, d, f, False),
                 ("fc2_fwd_" + tag, m, d, f, True), ("fc2_bwd_" + tag, m, f, d, False)]
     return out
+
+
+# (fused variant, the two-step form it replaces, the epilogue whose policy decides it)
+EPILOGUE_AB = (("fused_gelu", "pair_gelu", "gelu"), ("fused_gelu_nosave", "pair_gelu", "gelu"),
+               ("fused_gelu_grad", "pair_gelu_grad", "gelu_grad"))
 
 
 def err(c, ref):
@@ -99,6 +107,24 @@ def main():
         out_s = torch.empty(M, N, device=dev)
         for k in small:
             variants.append(("small%d" % k, lambda k=k: ops.gemm_small(a, packed, bias, out=out_s, ksplit=k)))
+        epi_tile = _fused.gemm_tile(M, N, K)
+        if N == MODELS[args.model][1]:
+            h_e, act_e, dh_e = (torch.empty(M, N, device=dev) for _ in range(3))
+            h_p, act_p, dh_p = (torch.empty(M, N, device=dev) for _ in range(3))
+            h_in = torch.randn(M, N, device=dev, generator=gen)          # the pre-activation the backward reads
+
+            def pair_gelu():
+                ops.gelu_fwd(ops.gemm(a, packed, bias, out=h_p, tile=epi_tile), out=act_p)
+
+            def pair_gelu_grad():
+                ops.gelu_bwd(h_in, ops.gemm(a, packed, bias, out=dh_p, tile=epi_tile))
+
+            variants += [("pair_gelu", pair_gelu),
+                         ("fused_gelu", lambda: ops.gemm(a, packed, bias, out=act_e, tile=epi_tile, epilogue="gelu", aux=h_e)),
+                         ("fused_gelu_nosave", lambda: ops.gemm(a, packed, bias, out=act_e, tile=epi_tile, epilogue="gelu")),
+                         ("pair_gelu_grad", pair_gelu_grad),
+                         ("fused_gelu_grad",
+                          lambda: ops.gemm(a, packed, bias, out=dh_e, tile=epi_tile, epilogue="gelu_grad", aux=h_in))]
         times = {key: [] for key, _ in variants}
         for _ in range(3):                          # warm-up: code objects, then the clock the timed rounds run at
             for _, fn in variants:
@@ -148,6 +174,29 @@ def main():
                         err_rms=ew[1], same_bits_as_kernel=bool(torch.equal(out_w, out_k)),
                         speedup_vs_kernel_median=statistics.median(times["kernel"]) / statistics.median(tw),
                         bf16_mfma_tflops=12.0 * M * N * K / statistics.median(tw) / 1e9)
+        epilogue = None
+        if "fused_gelu" in times:
+            def stats(key):
+                ts = times[key]
+                return dict(ms_median=statistics.median(ts), ms_min=min(ts), ms_spread=max(ts) - min(ts))
+            pair_gelu()
+            pair_gelu_grad()
+            ops.gemm(a, packed, bias, out=act_e, tile=epi_tile, epilogue="gelu", aux=h_e)
+            ops.gemm(a, packed, bias, out=dh_e, tile=epi_tile, epilogue="gelu_grad", aux=h_in)
+            torch.cuda.synchronize()
+            same = torch.equal(h_e, h_p) and torch.equal(act_e, act_p) and torch.equal(dh_e, dh_p)
+            fuses = {epi: _fused.gelu_epilogue(M, N, K, epi) for epi in ("gelu", "gelu_grad")}
+            epilogue = dict(tile=epi_tile, policy_fuses=fuses, same_bits=bool(same))
+            for key in ("pair_gelu", "fused_gelu", "fused_gelu_nosave", "pair_gelu_grad", "fused_gelu_grad"):
+                epilogue[key] = stats(key)
+            for fused, pair, _epi in EPILOGUE_AB:
+                f, q = epilogue[fused], epilogue[pair]
+                f["speedup_vs_pair_median"] = q["ms_median"] / f["ms_median"]
+                # the policy's rule: the medians' difference against the larger round-to-round spread of the two
+                f["margin_ms"] = q["ms_median"] - f["ms_median"]
+                f["larger_spread_ms"] = max(f["ms_spread"], q["ms_spread"])
+                f["passes_rule"] = f["margin_ms"] > f["larger_spread_ms"]
+            del h_e, act_e, dh_e, h_p, act_p, dh_p, h_in
         del ref, graphs
         med_k, med_l = statistics.median(times["kernel"]), statistics.median(times["library"])
         flop = 2.0 * M * N * K
@@ -160,7 +209,7 @@ def main():
                    kernel_ms_spread=max(times["kernel"]) - min(times["kernel"]),
                    library_ms_spread=max(times["library"]) - min(times["library"]),
                    big_workgroups=ops.gemm_workgroups(M, N), small_tiles=ops.gemm_small_workgroups(M, N), small=small_rows,
-                   wide=wide, policy_tile=_fused.gemm_tile(M, N, K),
+                   wide=wide, policy_tile=_fused.gemm_tile(M, N, K), epilogue=epilogue,
                    kernel_err_max=ek[0], kernel_err_rms=ek[1], library_err_max=el[0], library_err_rms=el[1])
         print(json.dumps(row), flush=True)
         results.append(row)
@@ -183,6 +232,15 @@ def main():
                   "bits {}".format("*" if r["policy_tile"] == "wide" else " ", wd["speedup_vs_kernel_median"],
                                    wd["ms_median"], wd["ms_spread"], r["kernel_ms_median"], r["kernel_ms_spread"],
                                    wd["bf16_mfma_tflops"], "equal" if wd["same_bits_as_kernel"] else "DIFFER"))
+        if r["epilogue"]:
+            ep = r["epilogue"]
+            for fused, pair, epi in EPILOGUE_AB:
+                f, q = ep[fused], ep[pair]
+                print("  {:<18}{} {:>7.3f}x pair   {:.4f} ms (spread {:.4f}; pair {:.4f} spread {:.4f})  margin {:+.4f} {}  "
+                      "tile {}  bits {}".format(fused, "*" if ep["policy_fuses"][epi] else " ",
+                                                f["speedup_vs_pair_median"], f["ms_median"], f["ms_spread"], q["ms_median"],
+                                                q["ms_spread"], f["margin_ms"], "passes" if f["passes_rule"] else "fails",
+                                                ep["tile"], "equal" if ep["same_bits"] else "DIFFER"))
         for sm in r["small"]:
             print("  small ksplit {:<2}{} {:>8.3f}x library  {:.4f} ms (spread {:.4f}; library {:.4f} spread {:.4f})  err {:.2e}"
                   .format(sm["ksplit"], "*" if sm["planned"] else " ", sm["speedup_vs_library_median"], sm["ms_median"],

@@ -78,6 +78,7 @@ SIGNATURES = {
     "vqa_gemm_bf16x6_tile": (_i, [_p, _l, _p, _p, _p, _l, _l, _i, _i, _i, _p]),
     "vqa_gemm_small_ws_bytes": (_sz, [_l, _i, _i]),
     "vqa_gemm_bf16x6_small": (_i, [_p, _l, _p, _p, _p, _l, _l, _i, _i, _i, _p, _p]),
+    "vqa_gemm_bf16x6_epi": (_i, [_p, _l, _p, _p, _p, _l, _l, _i, _i, _i, _i, _p, _l, _p]),
 }
 
 _lib = None

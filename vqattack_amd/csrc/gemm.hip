@@ -24,13 +24,13 @@
 // Deterministic: fixed summation order (per k-step the products a2b0, a1b1, a0b2, a1b0, a0b1, a0b0 in turn, k-steps in
 // order), no split-K, no atomics.  Rows >= M are read clamped to row M-1 and never stored.
 #include "common.hpp"
+#include "gelu.hpp"
 
 namespace vqa {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kGemmBM = 256, kGemmBN = 128, kGemmBK = 32;
 constexpr int kGemmThreads = 512;
@@ -72,6 +72,8 @@ struct GemmArgs {
   int N, K;
 };
 
+// gemm_bf16x6_epi_kernel<EPI> below is a COPY of this prologue and k-loop (only the epilogue differs): a change here
+// goes there too.
 __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) char smem[2 * kGemmStage];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -196,6 +198,8 @@ constexpr int kWideStage = kWideABytes + kWideBBytes;                  // 72 KiB
 constexpr int kWideBPieces = kWideBBytes / 16 / kGemmThreads;          // 6 x 16 B of B per thread and k-step
 constexpr int kWideLoadPair = 12;                                      // MFMAs behind each pair of global loads of the next step
 
+// gemm_bf16x6_wide_epi_kernel<EPI> below is a COPY of this prologue and k-loop (only the epilogue differs): a change
+// here goes there too.
 __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) char smem[2 * kWideStage];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -298,6 +302,288 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_kernel(GemmArgs
         if (row < g.M) g.C[row * g.ldc + col] = g.bias ? acc[i][j][rr] + bv : acc[i][j][rr];
       }
   }
+}
+
+// ---- GELU in the epilogue: the FFN's activation, or the product with its derivative, on the accumulators --------------
+// gemm_bf16x6_epi_kernel<EPI> / gemm_bf16x6_wide_epi_kernel<EPI> are gemm_bf16x6_kernel / gemm_bf16x6_wide_kernel up to
+// the epilogue, as copies: the prologue and the k-loop are the same text, so the same split, packed B, product and
+// k-step order and (wide) load placement, and the unfused kernels' code objects do not change by a single instruction
+// (a shared __device__ body changed their prologue scheduling and LDS addressing).  tests/test_gemm_epilogue.py holds
+// the copies to the originals' loop budgets and to the bits of the unfused pair.
+struct GemmEpiArgs : GemmArgs {
+  float* aux;          // GELU: where the pre-activation goes (nullable); GELU_GRAD: the pre-activation (read only)
+  long ldaux;
+};
+
+// What a wave does with its 64 x 64 block of accumulators at (row0, col0): register r of tile (i, j) is row
+// i * 16 + (lane >> 4) * 4 + r, column j * 16 + (lane & 15).  Rows >= M are neither stored nor loaded from aux.
+//   VQA_GEMM_EPI_GELU       h = acc (+ bias);  aux = h where aux is given;  C = gelu(h)
+//   VQA_GEMM_EPI_GELU_GRAD  C = (acc (+ bias)) * gelu'(aux)
+// GELU and its derivative are gelu.hpp's, on the pairs (r, r + 1) of a tile's registers: the bits of vqa_gelu_fwd /
+// vqa_gelu_bwd applied to the plain epilogue's output.  FULL: all 64 rows are below M, so nothing is guarded and the
+// code is one basic block (behind a per-row branch the compiler waits for EVERY outstanding load, which serialises
+// the h loads of GELU_GRAD with the arithmetic).
+template <int EPI, bool FULL>
+__device__ __forceinline__ void gemm_epilogue_rows(const f32x4 (&acc)[4][4], const GemmEpiArgs& g, long row0, int col0,
+                                                   int lane) {
+  float bv[4] = {0.0f, 0.0f, 0.0f, 0.0f};                 // ahead of the h loads: a load behind them would wait for them
+  if (g.bias) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bv[j] = g.bias[col0 + j * 16 + (lane & 15)];
+  }
+  if constexpr (EPI == VQA_GEMM_EPI_GELU) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int col = col0 + j * 16 + (lane & 15);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; r += 2) {
+          const long row = row0 + i * 16 + (lane >> 4) * 4 + r;
+          const f32x2 v = {acc[i][j][r], acc[i][j][r + 1]};
+          const f32x2 h = g.bias ? v + pk(bv[j]) : v;
+          const f32x2 a = gelu2(h);
+#pragma unroll
+          for (int e = 0; e < 2; ++e)
+            if (FULL || row + e < g.M) {
+              if (g.aux) g.aux[(row + e) * g.ldaux + col] = h[e];
+              g.C[(row + e) * g.ldc + col] = a[e];
+            }
+        }
+    }
+  } else {
+    // the loads of column tile j + 1 are issued ahead of the arithmetic of tile j (the loop's prefetch and fragment
+    // registers are dead here: 2 x 16 registers of h fit)
+    float hv[2][4][4];
+    auto fetch = [&](int j, float (&dst)[4][4]) {
+      const int col = col0 + j * 16 + (lane & 15);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const long row = row0 + i * 16 + (lane >> 4) * 4 + r;
+          dst[i][r] = (FULL || row < g.M) ? g.aux[row * g.ldaux + col] : 0.0f;
+        }
+    };
+    fetch(0, hv[0]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (j + 1 < 4) fetch(j + 1, hv[(j + 1) & 1]);
+      const int col = col0 + j * 16 + (lane & 15);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; r += 2) {
+          const long row = row0 + i * 16 + (lane >> 4) * 4 + r;
+          const f32x2 v = {acc[i][j][r], acc[i][j][r + 1]};
+          const f32x2 d = g.bias ? v + pk(bv[j]) : v;
+          const f32x2 dh = d * gelu_grad2(f32x2{hv[j & 1][i][r], hv[j & 1][i][r + 1]});
+#pragma unroll
+          for (int e = 0; e < 2; ++e)
+            if (FULL || row + e < g.M) g.C[(row + e) * g.ldc + col] = dh[e];
+        }
+    }
+  }
+}
+
+template <int EPI>
+__device__ __forceinline__ void gemm_epilogue(const f32x4 (&acc)[4][4], const GemmEpiArgs& g, long row0, int col0,
+                                              int lane) {
+  if (__builtin_amdgcn_readfirstlane(row0 + 64 <= g.M)) {       // row0 is the wave's: uniform
+    gemm_epilogue_rows<EPI, true>(acc, g, row0, col0, lane);
+  } else {
+    gemm_epilogue_rows<EPI, false>(acc, g, row0, col0, lane);
+  }
+}
+
+template <int EPI>
+__global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_epi_kernel(GemmEpiArgs g) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * kGemmStage];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;                 // this wave's 64 x 64 output block
+  const int ntb = g.N / kGemmBN;
+  const int mtb = static_cast<int>((g.M + kGemmBM - 1) / kGemmBM);
+  // XCD remap (bijective for any grid): consecutive tiles -- the same A row band -- share an XCD's L2
+  const int nwg = mtb * ntb, orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, rem = nwg & 7;
+  const int wg = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (orig >> 3);
+  const int mb = wg / ntb, nb = wg - mb * ntb;
+  const long m0 = static_cast<long>(mb) * kGemmBM;
+  const int n0 = nb * kGemmBN;
+  const int nk = g.K / kGemmBK;
+  const int nt16 = g.N / 16;
+
+  // staging: this thread splits 2 (row, 8-k chunk) pieces of A per k-step -- m-tiles 2*wave, 2*wave+1, row lane & 15,
+  // chunk lane >> 4 -- and copies 3 x 16 B of packed B
+  const float* arow[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    long r = m0 + (2 * wave + j) * 16 + (lane & 15);
+    r = r < g.M ? r : g.M - 1;
+    arow[j] = g.A + r * g.lda + 8 * (lane >> 4);
+  }
+  const bf16x8* bsrc = g.B + static_cast<size_t>(nb) * kGemmNT * 3 * 64;
+  const size_t bstep = static_cast<size_t>(nt16) * 3 * 64;            // bf16x8 per k-step of packed B
+
+  f32x4 ra[2][2];
+  bf16x8 rb[kGemmBPieces];
+  auto load = [&](int kt) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      ra[j][0] = *reinterpret_cast<const f32x4*>(arow[j] + kt * kGemmBK);
+      ra[j][1] = *reinterpret_cast<const f32x4*>(arow[j] + kt * kGemmBK + 4);
+    }
+#pragma unroll
+    for (int p = 0; p < kGemmBPieces; ++p) rb[p] = bsrc[kt * bstep + p * kGemmThreads + tid];
+  };
+  auto store = [&](int s) {
+    char* base = smem + s * kGemmStage;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      bf16x8 p0, p1, p2;
+      split8(ra[j][0], ra[j][1], p0, p1, p2);
+      bf16x8* dst = reinterpret_cast<bf16x8*>(base) + (2 * wave + j) * 3 * 64 + lane;
+      dst[0] = p0;
+      dst[64] = p1;
+      dst[128] = p2;
+    }
+    bf16x8* bdst = reinterpret_cast<bf16x8*>(base + kGemmABytes);
+#pragma unroll
+    for (int p = 0; p < kGemmBPieces; ++p) bdst[p * kGemmThreads + tid] = rb[p];
+  };
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+  load(0);
+  store(0);
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const int cur = kt & 1;
+    load(kt + 1 < nk ? kt + 1 : kt);          // the last step reloads its own tile into the idle buffer: no branch
+    __builtin_amdgcn_sched_barrier(0);        // keep the loads ahead of the MFMAs (the scheduler sinks them otherwise)
+    const bf16x8* sa = reinterpret_cast<const bf16x8*>(smem + cur * kGemmStage) + wm * 4 * 3 * 64 + lane;
+    const bf16x8* sb = reinterpret_cast<const bf16x8*>(smem + cur * kGemmStage + kGemmABytes) + wn * 4 * 3 * 64 + lane;
+    bf16x8 fa[3][4], fb[3][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int p = 0; p < 3; ++p) {
+        fa[p][i] = sa[(i * 3 + p) * 64];
+        fb[p][i] = sb[(i * 3 + p) * 64];
+      }
+    // small terms first; each product sweeps all 16 accumulators (independent MFMAs back to back)
+    constexpr int kPa[6] = {2, 1, 0, 1, 0, 0}, kPb[6] = {0, 1, 2, 0, 1, 0};
+    // the split of step k+1 sits between the two halves: half a step of MFMAs covers the loads' latency, and its VALU
+    // work fills the gaps of the second half
+#pragma unroll
+    for (int t = 0; t < 6; ++t) {
+      if (t == 3) store(cur ^ 1);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kPa[t]][i], fb[kPb[t]][j], acc[i][j], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+
+  gemm_epilogue<EPI>(acc, g, m0 + wm * 64, n0 + wn * 64, lane);
+}
+
+template <int EPI>
+__global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_epi_kernel(GemmEpiArgs g) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * kWideStage];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 2, wn = wave & 3;                 // this wave's 64 x 64 output block
+  const int ntb = g.N / kWideBN;
+  const int mtb = static_cast<int>((g.M + kWideBM - 1) / kWideBM);
+  // XCD remap as above
+  const int nwg = mtb * ntb, orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, rem = nwg & 7;
+  const int wg = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (orig >> 3);
+  const int mb = wg / ntb, nb = wg - mb * ntb;
+  const long m0 = static_cast<long>(mb) * kWideBM;
+  const int n0 = nb * kWideBN;
+  const int nk = g.K / kGemmBK;
+  const int nt16 = g.N / 16;
+
+  // staging: this thread splits one (row, 8-k chunk) piece of A per k-step -- m-tile wave, row lane & 15, chunk
+  // lane >> 4 -- and copies 6 x 16 B of packed B
+  long r = m0 + wave * 16 + (lane & 15);
+  r = r < g.M ? r : g.M - 1;
+  const float* arow = g.A + r * g.lda + 8 * (lane >> 4);
+  const bf16x8* bsrc = g.B + static_cast<size_t>(nb) * kWideNT * 3 * 64;
+  const size_t bstep = static_cast<size_t>(nt16) * 3 * 64;            // bf16x8 per k-step of packed B
+
+  f32x4 ra[2];
+  bf16x8 rb[kWideBPieces];
+  auto load = [&](int kt) {
+    ra[0] = *reinterpret_cast<const f32x4*>(arow + kt * kGemmBK);
+    ra[1] = *reinterpret_cast<const f32x4*>(arow + kt * kGemmBK + 4);
+#pragma unroll
+    for (int p = 0; p < kWideBPieces; ++p) rb[p] = bsrc[kt * bstep + p * kGemmThreads + tid];
+  };
+  auto store = [&](int s) {
+    char* base = smem + s * kWideStage;
+    bf16x8 p0, p1, p2;
+    split8(ra[0], ra[1], p0, p1, p2);
+    bf16x8* dst = reinterpret_cast<bf16x8*>(base) + wave * 3 * 64 + lane;
+    dst[0] = p0;
+    dst[64] = p1;
+    dst[128] = p2;
+    bf16x8* bdst = reinterpret_cast<bf16x8*>(base + kWideABytes);
+#pragma unroll
+    for (int p = 0; p < kWideBPieces; ++p) bdst[p * kGemmThreads + tid] = rb[p];
+  };
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+  load(0);
+  store(0);
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const int cur = kt & 1;
+    load(kt + 1 < nk ? kt + 1 : kt);          // the last step reloads its own tile into the idle buffer: no branch
+    const bf16x8* sa = reinterpret_cast<const bf16x8*>(smem + cur * kWideStage) + wm * 4 * 3 * 64 + lane;
+    const bf16x8* sb = reinterpret_cast<const bf16x8*>(smem + cur * kWideStage + kWideABytes) + wn * 4 * 3 * 64 + lane;
+    bf16x8 fa[3][4], fb[3][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int p = 0; p < 3; ++p) {
+        fa[p][i] = sa[(i * 3 + p) * 64];
+        fb[p][i] = sb[(i * 3 + p) * 64];
+      }
+    constexpr int kPa[6] = {2, 1, 0, 1, 0, 0}, kPb[6] = {0, 1, 2, 0, 1, 0};   // the order of gemm_bf16x6_kernel
+#pragma unroll
+    for (int t = 0; t < 6; ++t) {
+      if (t == 3) store(cur ^ 1);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kPa[t]][i], fb[kPb[t]][j], acc[i][j], 0, 0, 0);
+    }
+    // placement of the 8 global loads: a pair per kWideLoadPair MFMAs over the first half of the step (the A pair
+    // first; the split needs it at t == 3).  Measured 5.7-7.6 % faster than all eight ahead of the first MFMA, as
+    // gemm_bf16x6_kernel has them (profiles/r10/README.md); that is consistent with every wave of the workgroup waiting
+    // in the vector-memory issue queue right after the barrier before any of them reaches its MFMAs, which was not
+    // measured directly.  The group barriers are hints: tests/test_gemm_wide.py checks where the loads land
+#pragma unroll
+    for (int n = 0; n < (2 + kWideBPieces) / 2; ++n) {
+      __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);                  // two vector-memory reads
+      __builtin_amdgcn_sched_group_barrier(0x008, kWideLoadPair, 0);      // kWideLoadPair MFMAs
+    }
+    __syncthreads();
+  }
+
+  gemm_epilogue<EPI>(acc, g, m0 + wm * 64, n0 + wn * 64, lane);
 }
 
 // ---- small-tile variant for grids the 256 x 128 tile cannot fill (a few hundred rows, or a narrow N) ---------------
@@ -517,6 +803,35 @@ int vqa_gemm_bf16x6_tile(const float* A, long lda, const void* packed, const flo
   GemmArgs g{A, static_cast<const bf16x8*>(packed), bias, C, lda, ldc, M, N, K};
   const int grid = static_cast<int>((M + kWideBM - 1) / kWideBM * (N / kWideBN));
   gemm_bf16x6_wide_kernel<<<grid, kGemmThreads, 0, static_cast<hipStream_t>(stream)>>>(g);
+  return launch_status();
+}
+
+int vqa_gemm_bf16x6_epi(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M,
+                        int N, int K, int tile, int epilogue, float* aux, long ldaux, vqa_stream_t stream) {
+  if (epilogue == VQA_GEMM_EPI_NONE) return vqa_gemm_bf16x6_tile(A, lda, packed, bias, C, ldc, M, N, K, tile, stream);
+  clear_stale_error();
+  if (tile != VQA_GEMM_TILE_256X128 && tile != VQA_GEMM_TILE_128X256) return VQA_ERR_SHAPE;
+  if (epilogue != VQA_GEMM_EPI_GELU && epilogue != VQA_GEMM_EPI_GELU_GRAD) return VQA_ERR_SHAPE;
+  if (!A || !packed || !C || (epilogue == VQA_GEMM_EPI_GELU_GRAD && !aux)) return VQA_ERR_NULL;
+  if (M < 0 || N <= 0 || K <= 0 || K % kGemmBK || N % kGemmBN || lda < K || lda % 4 || ldc < N) return VQA_ERR_SHAPE;
+  if (aux && ldaux < N) return VQA_ERR_SHAPE;
+  const bool wide = tile == VQA_GEMM_TILE_128X256 && N % kWideBN == 0;     // every other N runs the 256 x 128 tile
+  const long grid = wide ? (M + kWideBM - 1) / kWideBM * (N / kWideBN) : (M + kGemmBM - 1) / kGemmBM * (N / kGemmBN);
+  if (grid > 0x7fffffffL) return VQA_ERR_SHAPE;
+  if (!aligned16(A) || !aligned16(packed) || !aligned4(C) || (bias && !aligned4(bias)) || (aux && !aligned4(aux)))
+    return VQA_ERR_ALIGN;
+  if (aux && (aux == C || aux == A)) return VQA_ERR_SHAPE;
+  if (M == 0) return VQA_OK;
+  GemmEpiArgs e{{A, static_cast<const bf16x8*>(packed), bias, C, lda, ldc, M, N, K}, aux, ldaux};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int nwg = static_cast<int>(grid);
+  if (wide) {
+    if (epilogue == VQA_GEMM_EPI_GELU) gemm_bf16x6_wide_epi_kernel<VQA_GEMM_EPI_GELU><<<nwg, kGemmThreads, 0, st>>>(e);
+    else gemm_bf16x6_wide_epi_kernel<VQA_GEMM_EPI_GELU_GRAD><<<nwg, kGemmThreads, 0, st>>>(e);
+  } else {
+    if (epilogue == VQA_GEMM_EPI_GELU) gemm_bf16x6_epi_kernel<VQA_GEMM_EPI_GELU><<<nwg, kGemmThreads, 0, st>>>(e);
+    else gemm_bf16x6_epi_kernel<VQA_GEMM_EPI_GELU_GRAD><<<nwg, kGemmThreads, 0, st>>>(e);
+  }
   return launch_status();
 }
 

@@ -759,16 +759,43 @@ def gemm_pack(w, trans):
 GEMM_TILES = {"large": 0, "wide": 1}      # VQA_GEMM_TILE_256X128, VQA_GEMM_TILE_128X256 of include/vqattack_hip.h
 
 
-def gemm(a, packed, bias=None, out=None, tile=None):
+GEMM_EPILOGUES = {"gelu": 1, "gelu_grad": 2}   # VQA_GEMM_EPI_GELU, VQA_GEMM_EPI_GELU_GRAD of include/vqattack_hip.h
+
+
+def gemm(a, packed, bias=None, out=None, tile=None, epilogue=None, aux=None):
     """``out = a @ B (+ bias)`` on the bf16 matrix pipe (bf16x6, fp32-grade), B a ``PackedWeight``.  ``a``: fp32 (M, K)
     with unit column stride and a row stride that is a multiple of 4 floats.  ``tile``: the output tile of a workgroup,
     "large" (256 x 128) or "wide" (128 x 256: half the in-loop split work; N % 256 == 0, any other N runs "large");
-    both give the same bits.  None = what ``whitebox/_fused.py`` records for the shape (``gemm_tile``)."""
+    both give the same bits.  None = what ``whitebox/_fused.py`` records for the shape (``gemm_tile``).
+
+    ``epilogue``: None, or the FFN's activation applied to the accumulators inside the GEMM (``vqa_gemm_bf16x6_epi``),
+    with the bits of the two-step form.  "gelu": ``out = gelu(h)`` with ``h = a @ B (+ bias)``; ``aux``, if given, is
+    filled with ``h`` (``aux=None``: ``h`` is not stored at all).  "gelu_grad": ``out = (a @ B (+ bias)) * gelu'(aux)``,
+    ``aux`` = the forward's ``h``.  ``aux``: fp32 (M, N) on ``a``'s device, unit column stride, any row stride >= N; it
+    must not overlap ``out`` or ``a`` (the C entry point refuses ``aux == out`` / ``aux == a`` with VQA_ERR_SHAPE; the
+    wrapper raises ValueError first).  Layout of ``out``: contiguous without an epilogue (``vqa_gemm_bf16x6_tile`` is
+    called with ldc = N), unit column stride and any row stride >= N with one (``vqa_gemm_bf16x6_epi`` takes ldc)."""
+    if epilogue is not None and epilogue not in GEMM_EPILOGUES:
+        raise ValueError("epilogue must be None or one of {}, got {!r}".format(sorted(GEMM_EPILOGUES), epilogue))
+    if epilogue is None and aux is not None:
+        raise ValueError("aux goes with an epilogue")
+    if epilogue == "gelu_grad" and aux is None:
+        raise ValueError("epilogue 'gelu_grad' needs aux = the pre-activation h")
+    if aux is not None:
+        if aux is out:
+            raise ValueError("aux must not be out")
+        M = a.shape[0]
+        if not isinstance(aux, torch.Tensor) or tuple(aux.shape) != (M, packed.N) or aux.stride(1) != 1 or \
+                (M > 1 and aux.stride(0) < packed.N):
+            raise ValueError("aux must be a ({}, {}) tensor with unit column stride, got {}".format(
+                M, packed.N, (tuple(aux.shape), aux.stride()) if isinstance(aux, torch.Tensor) else type(aux)))
     if tile is None:
         from .whitebox import _fused
         tile = _fused.gemm_tile(a.shape[0], packed.N, packed.K)
     if tile not in GEMM_TILES:
         raise ValueError("tile must be one of {}, got {!r}".format(sorted(GEMM_TILES), tile))
+    if epilogue is not None:
+        return _gemm_epilogue(a, packed, bias, out, tile, epilogue, aux)
     return _gemm_tiled(a, packed, bias, out, tile)
 
 
@@ -790,6 +817,35 @@ def _gemm_tiled(a, packed, bias, out, tile):
         with _on(a):
             check(lib().vqa_gemm_bf16x6_tile(_p(a), a.stride(0), _p(packed.data), ptr(bias), _p(out), packed.N, M, packed.N,
                                              packed.K, GEMM_TILES[tile], stream_for(a)), "vqa_gemm_bf16x6_tile")
+    return out
+
+
+def _gemm_epilogue(a, packed, bias, out, tile, epilogue, aux):
+    """``vqa_gemm_bf16x6_epi``; ``gemm`` has checked the epilogue's name and the shape of ``aux``."""
+    dev_f32(a, "a", contiguous=False)
+    if a.dim() != 2 or a.shape[1] != packed.K or a.stride(1) != 1 or a.stride(0) % 4:
+        raise ValueError("a must be (M, {}) with unit column stride and a row stride % 4 == 0, got shape {} strides {}"
+                         .format(packed.K, tuple(a.shape), a.stride()))
+    M, N = a.shape[0], packed.N
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float32, device=a.device)
+    dev_f32(out, "out", contiguous=False)
+    if tuple(out.shape) != (M, N) or out.stride(1) != 1 or (M > 1 and out.stride(0) < N):
+        raise ValueError("out must be ({}, {}) with unit column stride, got {} strides {}".format(
+            M, N, tuple(out.shape), out.stride()))
+    if bias is not None:
+        dev_f32(bias, "bias"), _rows_ok("bias", bias, N)
+    if aux is not None:
+        dev_f32(aux, "aux", contiguous=False)
+        if aux.data_ptr() in (out.data_ptr(), a.data_ptr()):
+            raise ValueError("aux must not alias out or a")
+    same_device(a, packed.data, bias, out, aux)
+    if M:
+        with _on(a):
+            check(lib().vqa_gemm_bf16x6_epi(_p(a), a.stride(0), _p(packed.data), ptr(bias), _p(out), max(out.stride(0), N), M,
+                                            N, packed.K, GEMM_TILES[tile], GEMM_EPILOGUES[epilogue], ptr(aux),
+                                            max(aux.stride(0), N) if aux is not None else 0, stream_for(a)),
+                  "vqa_gemm_bf16x6_epi")
     return out
 
 

@@ -56,6 +56,25 @@ SMALL_POLICY = {}
 _WIDE_ROWS = (35264, 37824)
 WIDE_POLICY = {(768, 768): _WIDE_ROWS, (3072, 768): _WIDE_ROWS, (768, 3072): _WIDE_ROWS}
 
+# The FFN's GELU (forward) and the product with its derivative (backward) can run in the epilogue of the GEMM that
+# produces their input (ops.gemm(..., epilogue=): vqa_gemm_bf16x6_epi, the bits of the two-step form), which saves one
+# pass over the (rows, 4D) pre-activation per direction.  Whether that is faster is a measurement, not a given: the tiles
+# run one workgroup per CU, so the epilogue's erf arithmetic is not hidden behind another workgroup's MFMAs.  Per
+# epilogue, a shape class (N, K) -> (fewest rows, most rows), both inclusive, is listed only by the rule of WIDE_POLICY:
+# the fused call's median in tools/gemm_bench.py beat the median of GEMM + GELU kernel by more than the round-to-round
+# spread of either in BOTH records of the shape (profiles/r11/README.md), and the benchmark with the entries in place
+# beat the one without.  Listed shapes are fused wherever the 256 x 128 or 128 x 256 kernel runs the GEMM (from
+# MIN_WORKGROUPS up, VQA_GEMM != library).  VQA_GEMM_EPILOGUE=1 fuses every such GEMM + GELU pair, =0 none.
+# Recorded per shape at 35264 and 37824 rows (VLMO-base, batch 64; profiles/r11/README.md): "gelu_grad" is 1.18-1.22x of
+# the pair, its margin 3-12 times the larger spread in every record, and the benchmark with its entry in place read
+# 15.68-15.71 examples/s against the previous commit's 15.45-15.48 in three alternating rounds (1.015x, outputs bitwise
+# equal): listed, on the row range of WIDE_POLICY.  "gelu" with h stored is 1.06-1.10x, but its margin (0.06-0.10 ms) is
+# of the size of the spreads and falls below the fused call's own max - min in one of four records at 35264 rows: not
+# listed (without the store of h, as under no_grad, it is 1.14-1.17x and passes).  Passing per shape but not listed,
+# the table holding one row range per class and no end-to-end run taken with them: "gelu_grad" at the text expert's
+# 2560 rows (1.25-1.29x) and at ALBEF-base's 147712 rows (1.21-1.22x).
+EPILOGUE_POLICY = {"gelu": {}, "gelu_grad": {(3072, 768): _WIDE_ROWS}}
+
 
 def _mode():
     """VQA_GEMM: "library" = the library everywhere, "large" = the 256 x 128 kernel from MIN_WORKGROUPS up and the library
@@ -86,6 +105,18 @@ def _small_gemm(rows, n, k):
     return mode == "" and lo <= rows <= hi
 
 
+def gelu_epilogue(rows, n, k, epilogue="gelu"):
+    """Whether a GEMM (rows, n, k) that feeds a GELU ("gelu"), or the derivative's product ("gelu_grad"), takes the
+    fused epilogue."""
+    if not _kernel_gemms() or ops.gemm_workgroups(rows, n) < MIN_WORKGROUPS:
+        return False
+    switch = os.environ.get("VQA_GEMM_EPILOGUE", "")
+    if switch in ("0", "1"):
+        return switch == "1"
+    lo, hi = EPILOGUE_POLICY[epilogue].get((n, k), (1, 0))
+    return lo <= rows <= hi
+
+
 def _pack(w):
     """(forward operand w.t(), input-gradient operand w) of a Linear weight w [out, in], packed once for both kernels;
     None where they do not cover the shape or VQA_GEMM=library."""
@@ -114,6 +145,25 @@ def _linear_grad(g, w, packed):
         if g.shape[0] and _small_gemm(g.shape[0], pk.N, pk.K):
             return ops.gemm_small(g, pk, ksplit=ops.gemm_small_plan(g.shape[0], pk.N, pk.K))
     return torch.mm(g, w)
+
+
+def _linear_gelu(a, w, bias, packed, save):
+    """(h or None, gelu(h)) with h = a @ w.t() + bias: an FFN's first layer and its activation.  ``h`` is returned for
+    the backward only if ``save``; the fused form then neither allocates nor writes it."""
+    pk = packed[0]
+    if pk is not None and gelu_epilogue(a.shape[0], pk.N, pk.K):
+        h = torch.empty(a.shape[0], pk.N, dtype=torch.float32, device=a.device) if save else None
+        return h, ops.gemm(a, pk, bias, epilogue="gelu", aux=h)
+    h = _linear(a, w, bias, packed)
+    return (h if save else None), ops.gelu_fwd(h)
+
+
+def _linear_grad_gelu(g, w, packed, h):
+    """(g @ w) * gelu'(h): the gradient of the pre-activation ``h`` from the gradient of the FFN's second layer's output."""
+    pk = packed[1]
+    if pk is not None and gelu_epilogue(g.shape[0], pk.N, pk.K, "gelu_grad"):
+        return ops.gemm(g, pk, epilogue="gelu_grad", aux=h)
+    return ops.gelu_bwd(h, _linear_grad(g, w, packed))                  # in place on the GEMM's output
 
 
 class LayerSpec:
@@ -248,8 +298,7 @@ def _forward(x0, call, save):
         del p
         hs, ms = [], []
         for e, (ye, (w1, b1, w2, b2)) in enumerate(zip(ys, lay.mlp)):
-            h = _linear(ye, w1, b1, lay.packed["fc1_%d" % e])
-            a = ops.gelu_fwd(h)
+            h, a = _linear_gelu(ye, w1, b1, lay.packed["fc1_%d" % e], save)
             ms.append(_linear(a, w2, b2, lay.packed["fc2_%d" % e]))
             hs.append(h)
             del a
@@ -308,8 +357,7 @@ def _backward(saved, call, g_feats, g_states, shape):
         two = len(lay.mlp) == 2
         dys = []
         for e, (dme, h, (w1, _b1, w2, _b2)) in enumerate(zip(dm, sv["hs"], lay.mlp)):
-            da = _linear_grad(dme, w2, lay.packed["fc2_%d" % e])      # (rows_e, 4D)
-            ops.gelu_bwd(h, da)                   # in place: dh
+            da = _linear_grad_gelu(dme, w2, lay.packed["fc2_%d" % e], h)      # (rows_e, 4D): dh
             dys.append(_linear_grad(da, w1, lay.packed["fc1_%d" % e]))
             del da
         del dm
@@ -510,8 +558,7 @@ def _fusion_forward(x0, img, call, full_from, partial):
             if part:
                 sv.update(q_c=q, o_c=o, lse_c=lse, scores_c=scores, ln_cross=st)
             del q, o, lse, scores
-        h = _linear(x, lay.w1, lay.b1, lay.packed["fc1"])
-        a = ops.gelu_fwd(h)
+        h, a = _linear_gelu(x, lay.w1, lay.b1, lay.packed["fc1"], part)
         f = _linear(a, lay.w2, lay.b2, lay.packed["fc2"])
         del a
         x, st = _post_ln(x, f, lay.ln_out, spec.eps, part)
@@ -563,8 +610,7 @@ def _fusion_backward(saved, kv, call, g_feats, g_states, shape, m, need_t, need_
             saved[li] = None
             continue
         ds = _ln_post_grad(inc, sv["ln_out"], lay.ln_out[0])              # d(x + ffn(x)): residual path and branch
-        da = _linear_grad(ds, lay.w2, lay.packed["fc2"])
-        ops.gelu_bwd(sv["h"], da)                                        # in place: dh
+        da = _linear_grad_gelu(ds, lay.w2, lay.packed["fc2"], sv["h"])      # dh
         dx = _linear_grad(da, lay.w1, lay.packed["fc1"])
         del da
         inc = [ds, dx, None]
