@@ -15,7 +15,17 @@
 // = 72 KiB, double-buffered = 144 KiB (one workgroup per CU, 2 waves per SIMD).  Every LDS image is "fragment order":
 // 1 KiB per (tile, plane), lane l's 16 bytes at l * 16, so every ds_read_b128 / ds_write_b128 of a wave is one linear,
 // conflict-free KiB.  Per k-step a wave issues 24 fragment reads and 96 MFMAs.  The k-loop is: issue the global loads of
-// step k+1 into registers, run the MFMAs of step k, split + write step k+1 into the other buffer, one barrier.
+// step k+1 (A into registers, B straight into the other LDS buffer), run the MFMAs of step k, split + write A of step
+// k+1 into the other buffer, wait for the B loads, one barrier.
+//
+// Staging of B: vqa_gemm_pack_b wrote B in fragment order, so the LDS image of a k-step is a plain copy of its run of
+// packed B, and thread tid's 16-byte piece p goes to (p * 512 + tid) * 16 = a wave-uniform base + lane * 16.  That is
+// the form a direct-to-LDS load writes (stage_b16: global_load_lds_dwordx4), so the 256 x 128 and 128 x 256 kernels
+// and their _epi copies move B without a register or a ds_write (3 / 6 pieces per thread and k-step; measured
+// 1.03-1.09x per kernel over staging through registers, profiles/r12/README.md).  Such a load is a pending LDS write
+// on the vector-memory counter: every wave waits for its own (stage_b_wait) ahead of the barrier that ends the step,
+// and the buffer it targets was last read before the barrier that began the step.  All LDS is ONE __shared__ array.
+// gemm_bf16x6_small_kernel keeps the register staging (rb[]): it is what the tests compare the bits against.
 //
 // Packed B ("vqa_gemm_pack_b"): bf16 [K/32][N/16][3 planes][64 lanes][8]; element (k, n) sits in plane tile
 // (k / 32, n / 16) at lane (n % 16) + 16 * ((k % 32) / 8), slot k % 8 -- the B-operand map of the 16x16x32 MFMA.  The
@@ -40,6 +50,7 @@ constexpr int kGemmABytes = kGemmMT * 3 * kTileBytes;                  // 48 KiB
 constexpr int kGemmBBytes = kGemmNT * 3 * kTileBytes;                  // 24 KiB
 constexpr int kGemmStage = kGemmABytes + kGemmBBytes;                  // 72 KiB
 constexpr int kGemmBPieces = kGemmBBytes / 16 / kGemmThreads;          // 3 x 16 B of B per thread and k-step
+constexpr int kWideLoadPair = 12;                                      // MFMAs behind each pair of global loads of the next step
 
 // a -> (a0, a1, a2), exact for finite a whose bf16 rounding is finite.  Plain RNE casts (v_cvt_pk_bf16_f32).
 __device__ __forceinline__ void split2(f32x2 a, bf16x2& h0, bf16x2& h1, bf16x2& h2) {
@@ -63,6 +74,16 @@ __device__ __forceinline__ void split8(const f32x4& lo, const f32x4& hi, bf16x8&
   p2 = bf16x8{c[0].x, c[0].y, c[1].x, c[1].y, c[2].x, c[2].y, c[3].x, c[3].y};
 }
 
+// 16 bytes per lane from global memory straight into LDS (global_load_lds_dwordx4): the wave's 64 pieces land at
+// lds + lane * 16, lds wave-uniform.  A pending LDS write on the vector-memory counter until stage_b_wait().
+__device__ __forceinline__ void stage_b16(const bf16x8* src, char* lds) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,   // address-space casts are C casts
+                                   (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
+}
+// Every vector-memory operation of this wave has completed (s_waitcnt vmcnt(0)): ahead of the barrier behind which the
+// other waves read what stage_b16 wrote.
+__device__ __forceinline__ void stage_b_wait() { __builtin_amdgcn_s_waitcnt(0x0f70); }
+
 struct GemmArgs {
   const float* A;
   const bf16x8* B;     // packed planes
@@ -77,6 +98,7 @@ struct GemmArgs {
 __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) char smem[2 * kGemmStage];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);   // the same value, known to be uniform
   const int wm = wave >> 1, wn = wave & 1;                 // this wave's 64 x 64 output block
   const int ntb = g.N / kGemmBN;
   const int mtb = static_cast<int>((g.M + kGemmBM - 1) / kGemmBM);
@@ -90,7 +112,7 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_kernel(GemmArgs g) {
   const int nt16 = g.N / 16;
 
   // staging: this thread splits 2 (row, 8-k chunk) pieces of A per k-step -- m-tiles 2*wave, 2*wave+1, row lane & 15,
-  // chunk lane >> 4 -- and copies 3 x 16 B of packed B
+  // chunk lane >> 4 -- and stages 3 x 16 B of packed B
   const float* arow[2];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
@@ -102,15 +124,18 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_kernel(GemmArgs g) {
   const size_t bstep = static_cast<size_t>(nt16) * 3 * 64;            // bf16x8 per k-step of packed B
 
   f32x4 ra[2][2];
-  bf16x8 rb[kGemmBPieces];
   auto load = [&](int kt) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       ra[j][0] = *reinterpret_cast<const f32x4*>(arow[j] + kt * kGemmBK);
       ra[j][1] = *reinterpret_cast<const f32x4*>(arow[j] + kt * kGemmBK + 4);
     }
-#pragma unroll
-    for (int p = 0; p < kGemmBPieces; ++p) rb[p] = bsrc[kt * bstep + p * kGemmThreads + tid];
+  };
+  // piece p of step kt's packed B into stage s, with no register in between: the wave's KiB lands at the base given
+  // here + lane * 16, which is where bdst[p * kGemmThreads + tid] = bsrc[...] used to put it
+  char* const bwave = smem + kGemmABytes + wave_u * kTileBytes;
+  auto load_b = [&](int kt, int s, int p) {
+    stage_b16(bsrc + kt * bstep + p * kGemmThreads + tid, bwave + s * kGemmStage + p * kGemmThreads * 16);
   };
   auto store = [&](int s) {
     char* base = smem + s * kGemmStage;
@@ -123,9 +148,6 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_kernel(GemmArgs g) {
       dst[64] = p1;
       dst[128] = p2;
     }
-    bf16x8* bdst = reinterpret_cast<bf16x8*>(base + kGemmABytes);
-#pragma unroll
-    for (int p = 0; p < kGemmBPieces; ++p) bdst[p * kGemmThreads + tid] = rb[p];
   };
 
   f32x4 acc[4][4];
@@ -135,12 +157,15 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_kernel(GemmArgs g) {
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 
   load(0);
+#pragma unroll
+  for (int p = 0; p < kGemmBPieces; ++p) load_b(0, 0, p);
   store(0);
+  stage_b_wait();
   __syncthreads();
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
-    load(kt + 1 < nk ? kt + 1 : kt);          // the last step reloads its own tile into the idle buffer: no branch
-    __builtin_amdgcn_sched_barrier(0);        // keep the loads ahead of the MFMAs (the scheduler sinks them otherwise)
+    const int nxt = kt + 1 < nk ? kt + 1 : kt;   // the last step reloads its own tile into the idle buffer: no branch
+    load(nxt);
     const bf16x8* sa = reinterpret_cast<const bf16x8*>(smem + cur * kGemmStage) + wm * 4 * 3 * 64 + lane;
     const bf16x8* sb = reinterpret_cast<const bf16x8*>(smem + cur * kGemmStage + kGemmABytes) + wn * 4 * 3 * 64 + lane;
     bf16x8 fa[3][4], fb[3][4];
@@ -161,9 +186,25 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_kernel(GemmArgs g) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < 4; ++j) {
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kPa[t]][i], fb[kPb[t]][j], acc[i][j], 0, 0, 0);
+          // B pieces 0, 1 behind the 24th MFMA and piece 2 behind the 36th.  Stage cur ^ 1 was last read in the step
+          // that the barrier above this one ended
+          if (t * 16 + i * 4 + j + 1 == 2 * kWideLoadPair) {
+            load_b(nxt, cur ^ 1, 0);
+            load_b(nxt, cur ^ 1, 1);
+          }
+          if (t * 16 + i * 4 + j + 1 == 3 * kWideLoadPair) load_b(nxt, cur ^ 1, 2);
+        }
     }
+    // placement of the 7 global loads, as in the wide kernel: the two A pairs ahead of the first and behind the 12th MFMA
+    // (group barriers: hints), B where the source has it; tests/test_gemm_lds_staging.py checks where they land
+#pragma unroll
+    for (int n = 0; n < (4 + kGemmBPieces + 1) / 2; ++n) {
+      __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);                  // two vector-memory reads
+      __builtin_amdgcn_sched_group_barrier(0x008, kWideLoadPair, 0);      // kWideLoadPair MFMAs
+    }
+    stage_b_wait();
     __syncthreads();
   }
 
@@ -185,7 +226,7 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_kernel(GemmArgs g) {
 // ---- wide-tile variant: 128 x 256 outputs per workgroup, half the in-loop split work per MFMA ---------------------
 // A workgroup splits BM x 32 values of A per k-step for BM x BN outputs, so every A value is split by N / BN
 // workgroups; the split is most of the loop's non-MFMA vector work.  With the tile turned on its side (8 waves as 2 along
-// M x 4 along N, 64 x 64 each as above) a thread splits ONE (row, 8-k) piece of A per k-step instead of two and copies
+// M x 4 along N, 64 x 64 each as above) a thread splits ONE (row, 8-k) piece of A per k-step instead of two and stages
 // 6 x 16 B of packed B instead of 3.  Same LDS footprint (A 8 m-tiles x 3 planes + B 16 n-tiles x 3 planes = 72 KiB per
 // stage), same 24 fragment reads and 96 MFMAs per wave and k-step, same grid size, same packed B (the 16 n-tiles x 3
 // planes of a k-step are one contiguous 48 KiB run), same split, same product and k-step order: every output has the
@@ -196,13 +237,13 @@ constexpr int kWideABytes = kWideMT * 3 * kTileBytes;                  // 24 KiB
 constexpr int kWideBBytes = kWideNT * 3 * kTileBytes;                  // 48 KiB
 constexpr int kWideStage = kWideABytes + kWideBBytes;                  // 72 KiB
 constexpr int kWideBPieces = kWideBBytes / 16 / kGemmThreads;          // 6 x 16 B of B per thread and k-step
-constexpr int kWideLoadPair = 12;                                      // MFMAs behind each pair of global loads of the next step
 
 // gemm_bf16x6_wide_epi_kernel<EPI> below is a COPY of this prologue and k-loop (only the epilogue differs): a change
 // here goes there too.
 __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) char smem[2 * kWideStage];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);   // the same value, known to be uniform
   const int wm = wave >> 2, wn = wave & 3;                 // this wave's 64 x 64 output block
   const int ntb = g.N / kWideBN;
   const int mtb = static_cast<int>((g.M + kWideBM - 1) / kWideBM);
@@ -216,7 +257,7 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_kernel(GemmArgs
   const int nt16 = g.N / 16;
 
   // staging: this thread splits one (row, 8-k chunk) piece of A per k-step -- m-tile wave, row lane & 15, chunk
-  // lane >> 4 -- and copies 6 x 16 B of packed B
+  // lane >> 4 -- and stages 6 x 16 B of packed B
   long r = m0 + wave * 16 + (lane & 15);
   r = r < g.M ? r : g.M - 1;
   const float* arow = g.A + r * g.lda + 8 * (lane >> 4);
@@ -224,12 +265,15 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_kernel(GemmArgs
   const size_t bstep = static_cast<size_t>(nt16) * 3 * 64;            // bf16x8 per k-step of packed B
 
   f32x4 ra[2];
-  bf16x8 rb[kWideBPieces];
   auto load = [&](int kt) {
     ra[0] = *reinterpret_cast<const f32x4*>(arow + kt * kGemmBK);
     ra[1] = *reinterpret_cast<const f32x4*>(arow + kt * kGemmBK + 4);
-#pragma unroll
-    for (int p = 0; p < kWideBPieces; ++p) rb[p] = bsrc[kt * bstep + p * kGemmThreads + tid];
+  };
+  // piece p of step kt's packed B into stage s, with no register in between: the wave's KiB lands at the base given
+  // here + lane * 16, which is where bdst[p * kGemmThreads + tid] = bsrc[...] used to put it
+  char* const bwave = smem + kWideABytes + wave_u * kTileBytes;
+  auto load_b = [&](int kt, int s, int p) {
+    stage_b16(bsrc + kt * bstep + p * kGemmThreads + tid, bwave + s * kWideStage + p * kGemmThreads * 16);
   };
   auto store = [&](int s) {
     char* base = smem + s * kWideStage;
@@ -239,9 +283,6 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_kernel(GemmArgs
     dst[0] = p0;
     dst[64] = p1;
     dst[128] = p2;
-    bf16x8* bdst = reinterpret_cast<bf16x8*>(base + kWideABytes);
-#pragma unroll
-    for (int p = 0; p < kWideBPieces; ++p) bdst[p * kGemmThreads + tid] = rb[p];
   };
 
   f32x4 acc[4][4];
@@ -251,11 +292,15 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_kernel(GemmArgs
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 
   load(0);
+#pragma unroll
+  for (int p = 0; p < kWideBPieces; ++p) load_b(0, 0, p);
   store(0);
+  stage_b_wait();
   __syncthreads();
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
-    load(kt + 1 < nk ? kt + 1 : kt);          // the last step reloads its own tile into the idle buffer: no branch
+    const int nxt = kt + 1 < nk ? kt + 1 : kt;   // the last step reloads its own tile into the idle buffer: no branch
+    load(nxt);
     const bf16x8* sa = reinterpret_cast<const bf16x8*>(smem + cur * kWideStage) + wm * 4 * 3 * 64 + lane;
     const bf16x8* sb = reinterpret_cast<const bf16x8*>(smem + cur * kWideStage + kWideABytes) + wn * 4 * 3 * 64 + lane;
     bf16x8 fa[3][4], fb[3][4];
@@ -273,19 +318,30 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_kernel(GemmArgs
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < 4; ++j) {
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kPa[t]][i], fb[kPb[t]][j], acc[i][j], 0, 0, 0);
+          // a pair of B pieces behind every kWideLoadPair MFMAs of the first half.  Stage cur ^ 1 was last read in
+          // the step that the barrier above this one ended
+          if ((t * 16 + i * 4 + j + 1) % kWideLoadPair == 0 && (t * 16 + i * 4 + j + 1) / kWideLoadPair <= kWideBPieces / 2) {
+            const int pair = (t * 16 + i * 4 + j + 1) / kWideLoadPair - 1;
+            load_b(nxt, cur ^ 1, 2 * pair);
+            load_b(nxt, cur ^ 1, 2 * pair + 1);
+          }
+        }
     }
     // placement of the 8 global loads: a pair per kWideLoadPair MFMAs over the first half of the step (the A pair
-    // first; the split needs it at t == 3).  Measured 5.7-7.6 % faster than all eight ahead of the first MFMA, as
-    // gemm_bf16x6_kernel has them (profiles/r10/README.md); that is consistent with every wave of the workgroup waiting
-    // in the vector-memory issue queue right after the barrier before any of them reaches its MFMAs, which was not
-    // measured directly.  The group barriers are hints: tests/test_gemm_wide.py checks where the loads land
+    // first; the split needs it).  Measured 5.7-7.6 % faster than all eight ahead of the first MFMA
+    // (profiles/r10/README.md); that is consistent with every wave of the workgroup waiting in the vector-memory issue
+    // queue right after the barrier before any of them reaches its MFMAs, which was not measured directly.  The direct
+    // loads of B stay where the source has them (behind the 12th, 24th and 36th MFMA); the group barriers place the A
+    // pair and keep the MFMAs from moving across the others.  They are hints: tests/test_gemm_wide.py and
+    // tests/test_gemm_lds_staging.py check where the loads land
 #pragma unroll
     for (int n = 0; n < (2 + kWideBPieces) / 2; ++n) {
       __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);                  // two vector-memory reads
       __builtin_amdgcn_sched_group_barrier(0x008, kWideLoadPair, 0);      // kWideLoadPair MFMAs
     }
+    stage_b_wait();
     __syncthreads();
   }
 
@@ -400,6 +456,7 @@ template <int EPI>
 __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_epi_kernel(GemmEpiArgs g) {
   __shared__ __attribute__((aligned(16))) char smem[2 * kGemmStage];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);   // the same value, known to be uniform
   const int wm = wave >> 1, wn = wave & 1;                 // this wave's 64 x 64 output block
   const int ntb = g.N / kGemmBN;
   const int mtb = static_cast<int>((g.M + kGemmBM - 1) / kGemmBM);
@@ -413,7 +470,7 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_epi_kernel(GemmEpiAr
   const int nt16 = g.N / 16;
 
   // staging: this thread splits 2 (row, 8-k chunk) pieces of A per k-step -- m-tiles 2*wave, 2*wave+1, row lane & 15,
-  // chunk lane >> 4 -- and copies 3 x 16 B of packed B
+  // chunk lane >> 4 -- and stages 3 x 16 B of packed B
   const float* arow[2];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
@@ -425,15 +482,18 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_epi_kernel(GemmEpiAr
   const size_t bstep = static_cast<size_t>(nt16) * 3 * 64;            // bf16x8 per k-step of packed B
 
   f32x4 ra[2][2];
-  bf16x8 rb[kGemmBPieces];
   auto load = [&](int kt) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       ra[j][0] = *reinterpret_cast<const f32x4*>(arow[j] + kt * kGemmBK);
       ra[j][1] = *reinterpret_cast<const f32x4*>(arow[j] + kt * kGemmBK + 4);
     }
-#pragma unroll
-    for (int p = 0; p < kGemmBPieces; ++p) rb[p] = bsrc[kt * bstep + p * kGemmThreads + tid];
+  };
+  // piece p of step kt's packed B into stage s, with no register in between: the wave's KiB lands at the base given
+  // here + lane * 16, which is where bdst[p * kGemmThreads + tid] = bsrc[...] used to put it
+  char* const bwave = smem + kGemmABytes + wave_u * kTileBytes;
+  auto load_b = [&](int kt, int s, int p) {
+    stage_b16(bsrc + kt * bstep + p * kGemmThreads + tid, bwave + s * kGemmStage + p * kGemmThreads * 16);
   };
   auto store = [&](int s) {
     char* base = smem + s * kGemmStage;
@@ -446,9 +506,6 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_epi_kernel(GemmEpiAr
       dst[64] = p1;
       dst[128] = p2;
     }
-    bf16x8* bdst = reinterpret_cast<bf16x8*>(base + kGemmABytes);
-#pragma unroll
-    for (int p = 0; p < kGemmBPieces; ++p) bdst[p * kGemmThreads + tid] = rb[p];
   };
 
   f32x4 acc[4][4];
@@ -458,12 +515,15 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_epi_kernel(GemmEpiAr
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 
   load(0);
+#pragma unroll
+  for (int p = 0; p < kGemmBPieces; ++p) load_b(0, 0, p);
   store(0);
+  stage_b_wait();
   __syncthreads();
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
-    load(kt + 1 < nk ? kt + 1 : kt);          // the last step reloads its own tile into the idle buffer: no branch
-    __builtin_amdgcn_sched_barrier(0);        // keep the loads ahead of the MFMAs (the scheduler sinks them otherwise)
+    const int nxt = kt + 1 < nk ? kt + 1 : kt;   // the last step reloads its own tile into the idle buffer: no branch
+    load(nxt);
     const bf16x8* sa = reinterpret_cast<const bf16x8*>(smem + cur * kGemmStage) + wm * 4 * 3 * 64 + lane;
     const bf16x8* sb = reinterpret_cast<const bf16x8*>(smem + cur * kGemmStage + kGemmABytes) + wn * 4 * 3 * 64 + lane;
     bf16x8 fa[3][4], fb[3][4];
@@ -484,9 +544,25 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_epi_kernel(GemmEpiAr
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < 4; ++j) {
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kPa[t]][i], fb[kPb[t]][j], acc[i][j], 0, 0, 0);
+          // B pieces 0, 1 behind the 24th MFMA and piece 2 behind the 36th.  Stage cur ^ 1 was last read in the step
+          // that the barrier above this one ended
+          if (t * 16 + i * 4 + j + 1 == 2 * kWideLoadPair) {
+            load_b(nxt, cur ^ 1, 0);
+            load_b(nxt, cur ^ 1, 1);
+          }
+          if (t * 16 + i * 4 + j + 1 == 3 * kWideLoadPair) load_b(nxt, cur ^ 1, 2);
+        }
     }
+    // placement of the 7 global loads, as in the wide kernel: the two A pairs ahead of the first and behind the 12th MFMA
+    // (group barriers: hints), B where the source has it; tests/test_gemm_lds_staging.py checks where they land
+#pragma unroll
+    for (int n = 0; n < (4 + kGemmBPieces + 1) / 2; ++n) {
+      __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);                  // two vector-memory reads
+      __builtin_amdgcn_sched_group_barrier(0x008, kWideLoadPair, 0);      // kWideLoadPair MFMAs
+    }
+    stage_b_wait();
     __syncthreads();
   }
 
@@ -497,6 +573,7 @@ template <int EPI>
 __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_epi_kernel(GemmEpiArgs g) {
   __shared__ __attribute__((aligned(16))) char smem[2 * kWideStage];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);   // the same value, known to be uniform
   const int wm = wave >> 2, wn = wave & 3;                 // this wave's 64 x 64 output block
   const int ntb = g.N / kWideBN;
   const int mtb = static_cast<int>((g.M + kWideBM - 1) / kWideBM);
@@ -510,7 +587,7 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_epi_kernel(Gemm
   const int nt16 = g.N / 16;
 
   // staging: this thread splits one (row, 8-k chunk) piece of A per k-step -- m-tile wave, row lane & 15, chunk
-  // lane >> 4 -- and copies 6 x 16 B of packed B
+  // lane >> 4 -- and stages 6 x 16 B of packed B
   long r = m0 + wave * 16 + (lane & 15);
   r = r < g.M ? r : g.M - 1;
   const float* arow = g.A + r * g.lda + 8 * (lane >> 4);
@@ -518,12 +595,15 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_epi_kernel(Gemm
   const size_t bstep = static_cast<size_t>(nt16) * 3 * 64;            // bf16x8 per k-step of packed B
 
   f32x4 ra[2];
-  bf16x8 rb[kWideBPieces];
   auto load = [&](int kt) {
     ra[0] = *reinterpret_cast<const f32x4*>(arow + kt * kGemmBK);
     ra[1] = *reinterpret_cast<const f32x4*>(arow + kt * kGemmBK + 4);
-#pragma unroll
-    for (int p = 0; p < kWideBPieces; ++p) rb[p] = bsrc[kt * bstep + p * kGemmThreads + tid];
+  };
+  // piece p of step kt's packed B into stage s, with no register in between: the wave's KiB lands at the base given
+  // here + lane * 16, which is where bdst[p * kGemmThreads + tid] = bsrc[...] used to put it
+  char* const bwave = smem + kWideABytes + wave_u * kTileBytes;
+  auto load_b = [&](int kt, int s, int p) {
+    stage_b16(bsrc + kt * bstep + p * kGemmThreads + tid, bwave + s * kWideStage + p * kGemmThreads * 16);
   };
   auto store = [&](int s) {
     char* base = smem + s * kWideStage;
@@ -533,9 +613,6 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_epi_kernel(Gemm
     dst[0] = p0;
     dst[64] = p1;
     dst[128] = p2;
-    bf16x8* bdst = reinterpret_cast<bf16x8*>(base + kWideABytes);
-#pragma unroll
-    for (int p = 0; p < kWideBPieces; ++p) bdst[p * kGemmThreads + tid] = rb[p];
   };
 
   f32x4 acc[4][4];
@@ -545,11 +622,15 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_epi_kernel(Gemm
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 
   load(0);
+#pragma unroll
+  for (int p = 0; p < kWideBPieces; ++p) load_b(0, 0, p);
   store(0);
+  stage_b_wait();
   __syncthreads();
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
-    load(kt + 1 < nk ? kt + 1 : kt);          // the last step reloads its own tile into the idle buffer: no branch
+    const int nxt = kt + 1 < nk ? kt + 1 : kt;   // the last step reloads its own tile into the idle buffer: no branch
+    load(nxt);
     const bf16x8* sa = reinterpret_cast<const bf16x8*>(smem + cur * kWideStage) + wm * 4 * 3 * 64 + lane;
     const bf16x8* sb = reinterpret_cast<const bf16x8*>(smem + cur * kWideStage + kWideABytes) + wn * 4 * 3 * 64 + lane;
     bf16x8 fa[3][4], fb[3][4];
@@ -567,19 +648,30 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_epi_kernel(Gemm
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < 4; ++j) {
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kPa[t]][i], fb[kPb[t]][j], acc[i][j], 0, 0, 0);
+          // a pair of B pieces behind every kWideLoadPair MFMAs of the first half.  Stage cur ^ 1 was last read in
+          // the step that the barrier above this one ended
+          if ((t * 16 + i * 4 + j + 1) % kWideLoadPair == 0 && (t * 16 + i * 4 + j + 1) / kWideLoadPair <= kWideBPieces / 2) {
+            const int pair = (t * 16 + i * 4 + j + 1) / kWideLoadPair - 1;
+            load_b(nxt, cur ^ 1, 2 * pair);
+            load_b(nxt, cur ^ 1, 2 * pair + 1);
+          }
+        }
     }
     // placement of the 8 global loads: a pair per kWideLoadPair MFMAs over the first half of the step (the A pair
-    // first; the split needs it at t == 3).  Measured 5.7-7.6 % faster than all eight ahead of the first MFMA, as
-    // gemm_bf16x6_kernel has them (profiles/r10/README.md); that is consistent with every wave of the workgroup waiting
-    // in the vector-memory issue queue right after the barrier before any of them reaches its MFMAs, which was not
-    // measured directly.  The group barriers are hints: tests/test_gemm_wide.py checks where the loads land
+    // first; the split needs it).  Measured 5.7-7.6 % faster than all eight ahead of the first MFMA
+    // (profiles/r10/README.md); that is consistent with every wave of the workgroup waiting in the vector-memory issue
+    // queue right after the barrier before any of them reaches its MFMAs, which was not measured directly.  The direct
+    // loads of B stay where the source has them (behind the 12th, 24th and 36th MFMA); the group barriers place the A
+    // pair and keep the MFMAs from moving across the others.  They are hints: tests/test_gemm_wide.py and
+    // tests/test_gemm_lds_staging.py check where the loads land
 #pragma unroll
     for (int n = 0; n < (2 + kWideBPieces) / 2; ++n) {
       __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);                  // two vector-memory reads
       __builtin_amdgcn_sched_group_barrier(0x008, kWideLoadPair, 0);      // kWideLoadPair MFMAs
     }
+    stage_b_wait();
     __syncthreads();
   }
 

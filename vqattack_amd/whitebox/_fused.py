@@ -52,7 +52,11 @@ SMALL_POLICY = {}
 # listed: the qkv classes (2304, 768) and (768, 2304) -- 1.08-1.10x at the median in both gemm_bench records, but the
 # 256 x 128 kernel's own max - min (0.07-0.09 ms) exceeds the margin (0.06-0.07 ms), so they fail the rule; the text
 # expert's 2560 x 3072 x 768 (240 workgroups; one of its two shapes fails the margin); ALBEF-base's 147712 rows (not
-# measured).
+# measured).  Re-taken with packed B staged straight into LDS in both tiles (profiles/r12/README.md, two records):
+# the listed classes 1.07-1.12x, margins 1.4-4.3 times the larger spread; (768, 2304) fails again in both records
+# (margin 0.05-0.06 ms against the 256 x 128 kernel's max - min of 0.07-0.08 ms) and (2304, 768) passes by 0.0001 ms
+# in one of them, so the qkv classes stay unlisted (the benchmark with both listed read 16.51-16.54 examples/s against
+# 16.32-16.34 without).
 _WIDE_ROWS = (35264, 37824)
 WIDE_POLICY = {(768, 768): _WIDE_ROWS, (3072, 768): _WIDE_ROWS, (768, 3072): _WIDE_ROWS}
 
