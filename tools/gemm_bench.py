@@ -15,7 +15,8 @@ error of each against an fp64 product are reported, plus the speed-up and, per v
 graphs of ``--reps`` calls, as that path is replayed.
 
     python tools/gemm_bench.py [--model vlmo_base|albef_base|vlmo_large] [--batch B] [--ksplit 1,2,4,8] [--graph]
-                               [--rounds 5] [--reps 10] [--only NAMES] [--out FILE]
+                               [--rounds 5] [--reps 10] [--warmup 3] [--only NAMES] [--out FILE]
+(the per-kernel records since round 13 use --warmup 10 --rounds 7 --reps 50).
 """
 import argparse
 import json
@@ -65,6 +66,7 @@ def main():
     ap.add_argument("--model", default="vlmo_base", choices=sorted(MODELS))
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3, help="untimed passes over all variants ahead of the timed rounds")
     ap.add_argument("--only", default="", help="comma-separated shape names")
     ap.add_argument("--batch", type=int, default=0, help="samples per encoder pass (default: the model's benchmark batch)")
     ap.add_argument("--ksplit", default="1,2,4,8", help="comma-separated K splits of the small-tile kernel ('' = none)")
@@ -126,7 +128,7 @@ def main():
                          ("fused_gelu_grad",
                           lambda: ops.gemm(a, packed, bias, out=dh_e, tile=epi_tile, epilogue="gelu_grad", aux=h_in))]
         times = {key: [] for key, _ in variants}
-        for _ in range(3):                          # warm-up: code objects, then the clock the timed rounds run at
+        for _ in range(args.warmup):                # warm-up: code objects, then the clock the timed rounds run at
             for _, fn in variants:
                 fn()
         torch.cuda.synchronize()
@@ -216,7 +218,7 @@ def main():
         del a, w, packed, out_k, out_l, out_s, out_w
         torch.cuda.empty_cache()
     summary = dict(model=args.model, batch=args.batch or MODELS[args.model][4], tuned_gemms=tuned, device=torch.cuda.get_device_name(),
-                   rounds=args.rounds, reps=args.reps, graph=args.graph, shapes=results)
+                   rounds=args.rounds, reps=args.reps, warmup=args.warmup, graph=args.graph, shapes=results)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as fh:

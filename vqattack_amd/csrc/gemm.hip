@@ -31,6 +31,15 @@
 // (k / 32, n / 16) at lane (n % 16) + 16 * ((k % 32) / 8), slot k % 8 -- the B-operand map of the 16x16x32 MFMA.  The
 // 8 n-tiles x 3 planes a workgroup stages per k-step are therefore one contiguous 24 KiB run.
 //
+// Epilogue of the large tiles: the A and B operand maps of the 16x16x32 MFMA are the same map (row or column on
+// lane & 15, k-chunk on lane >> 4), so the six large-tile kernels hand the instruction (B fragment, A fragment) and get
+// the transposed tile: a lane's four accumulator registers are four consecutive COLUMNS of one row.  Each of a lane's 16
+// tiles is then one 16-byte store (and, in the GELU' kernel, one 16-byte load of h) instead of four dword accesses that
+// each cover 4 rows x 64 bytes, and a row's four tiles are issued back to back (whole 128-byte lines); the same products are summed in the same order per element, so the bits are those of
+// gemm_bf16x6_small_kernel, which keeps the instruction's own order and dword stores.  The 16-byte form needs C, bias
+// and aux on 16-byte boundaries and ldc, ldaux % 4 == 0 (GemmArgs::vec, worked out by the wrappers); the entry points
+// still take 4-byte-aligned pointers and any stride >= N, which run the same lane map with dword accesses.
+//
 // Deterministic: fixed summation order (per k-step the products a2b0, a1b1, a0b2, a1b0, a0b1, a0b0 in turn, k-steps in
 // order), no split-K, no atomics.  Rows >= M are read clamped to row M-1 and never stored.
 #include "common.hpp"
@@ -91,7 +100,73 @@ struct GemmArgs {
   float* C;
   long lda, ldc, M;
   int N, K;
+  int vec;             // large-tile kernels: C, bias (and aux) are 16-byte aligned and ldc (ldaux) % 4 == 0 (gemm_vec_ok)
 };
+
+// Four consecutive floats of a row: one 16-byte access where the wrapper found everything aligned (VEC), four dwords
+// where it did not.
+template <bool VEC>
+__device__ __forceinline__ f32x4 load4(const float* p) {
+  if constexpr (VEC) return *reinterpret_cast<const f32x4*>(p);
+  return f32x4{p[0], p[1], p[2], p[3]};
+}
+template <bool VEC>
+__device__ __forceinline__ void store4(float* p, const f32x4& v) {
+  if constexpr (VEC) {
+    *reinterpret_cast<f32x4*>(p) = v;
+  } else {
+    p[0] = v.x, p[1] = v.y, p[2] = v.z, p[3] = v.w;
+  }
+}
+
+// Plain epilogue of a wave's 64 x 64 block at (row0, col0).  The large-tile kernels pass the MFMA its operands in the
+// order (B fragment, A fragment), so an accumulator tile is the transpose of the instruction's own layout: register r
+// of tile (i, j) is row i * 16 + (lane & 15), column j * 16 + (lane >> 4) * 4 + r -- four consecutive columns, one
+// 16-byte store per tile (16 per lane) instead of four dword stores down a column.  Same products in the same order
+// per element: the bits do not change.  Fully unrolled, rows >= M are not stored.  Order: i outer, j inner, see
+// gemm_epilogue_rows.
+template <bool VEC, bool FULL>
+__device__ __forceinline__ void gemm_store_rows(const f32x4 (&acc)[4][4], const GemmArgs& g, long row0, int col0, int lane) {
+  const int colq = col0 + (lane >> 4) * 4;
+  // the bias is added to all 16 tiles ahead of the first store: the memory counter is one for loads and stores, in order,
+  // so a bias load consumed behind a store (or behind a row guard, where the compiler no longer knows what is
+  // outstanding) waits for that store to be acknowledged
+  f32x4 v[4][4];
+  if (g.bias) {
+    f32x4 bv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bv[j] = load4<VEC>(g.bias + colq + j * 16);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[i][j] = acc[i][j] + bv[j];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[i][j] = acc[i][j];
+  }
+  // a row's four tiles back to back: its 256 bytes -- two whole 128-byte lines -- leave in consecutive stores
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const long row = row0 + i * 16 + (lane & 15);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (FULL || row < g.M) store4<VEC>(g.C + row * g.ldc + colq + j * 16, v[i][j]);
+  }
+}
+
+// FULL: all 64 rows of the wave's block are below M (row0 is the wave's: uniform), so nothing is guarded and the 16
+// stores are one basic block.  The scalar path (a misaligned pointer or an odd stride) has the guarded form only.
+__device__ __forceinline__ void gemm_store(const f32x4 (&acc)[4][4], const GemmArgs& g, long row0, int col0, int lane) {
+  if (!g.vec) {
+    gemm_store_rows<false, false>(acc, g, row0, col0, lane);
+  } else if (__builtin_amdgcn_readfirstlane(row0 + 64 <= g.M)) {
+    gemm_store_rows<true, true>(acc, g, row0, col0, lane);
+  } else {
+    gemm_store_rows<true, false>(acc, g, row0, col0, lane);
+  }
+}
 
 // gemm_bf16x6_epi_kernel<EPI> below is a COPY of this prologue and k-loop (only the epilogue differs): a change here
 // goes there too.
@@ -187,7 +262,7 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_kernel(GemmArgs g) {
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kPa[t]][i], fb[kPb[t]][j], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[kPb[t]][j], fa[kPa[t]][i], acc[i][j], 0, 0, 0);   // transposed
           // B pieces 0, 1 behind the 24th MFMA and piece 2 behind the 36th.  Stage cur ^ 1 was last read in the step
           // that the barrier above this one ended
           if (t * 16 + i * 4 + j + 1 == 2 * kWideLoadPair) {
@@ -208,19 +283,8 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_kernel(GemmArgs g) {
     __syncthreads();
   }
 
-  // epilogue: accumulator register r of tile (i, j) is row (lane >> 4) * 4 + r, column lane & 15
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int col = n0 + wn * 64 + j * 16 + (lane & 15);
-    const float bv = g.bias ? g.bias[col] : 0.0f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const long row = m0 + wm * 64 + i * 16 + (lane >> 4) * 4 + r;
-        if (row < g.M) g.C[row * g.ldc + col] = g.bias ? acc[i][j][r] + bv : acc[i][j][r];
-      }
-  }
+  // epilogue: accumulator register r of tile (i, j) is row lane & 15, column (lane >> 4) * 4 + r (operands swapped)
+  gemm_store(acc, g, m0 + wm * 64, n0 + wn * 64, lane);
 }
 
 // ---- wide-tile variant: 128 x 256 outputs per workgroup, half the in-loop split work per MFMA ---------------------
@@ -319,7 +383,7 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_kernel(GemmArgs
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kPa[t]][i], fb[kPb[t]][j], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[kPb[t]][j], fa[kPa[t]][i], acc[i][j], 0, 0, 0);   // transposed
           // a pair of B pieces behind every kWideLoadPair MFMAs of the first half.  Stage cur ^ 1 was last read in
           // the step that the barrier above this one ended
           if ((t * 16 + i * 4 + j + 1) % kWideLoadPair == 0 && (t * 16 + i * 4 + j + 1) / kWideLoadPair <= kWideBPieces / 2) {
@@ -345,19 +409,8 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_kernel(GemmArgs
     __syncthreads();
   }
 
-  // epilogue: accumulator register r of tile (i, j) is row (lane >> 4) * 4 + r, column lane & 15
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int col = n0 + wn * 64 + j * 16 + (lane & 15);
-    const float bv = g.bias ? g.bias[col] : 0.0f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const long row = m0 + wm * 64 + i * 16 + (lane >> 4) * 4 + rr;
-        if (row < g.M) g.C[row * g.ldc + col] = g.bias ? acc[i][j][rr] + bv : acc[i][j][rr];
-      }
-  }
+  // epilogue: accumulator register r of tile (i, j) is row lane & 15, column (lane >> 4) * 4 + r (operands swapped)
+  gemm_store(acc, g, m0 + wm * 64, n0 + wn * 64, lane);
 }
 
 // ---- GELU in the epilogue: the FFN's activation, or the product with its derivative, on the accumulators --------------
@@ -371,84 +424,92 @@ struct GemmEpiArgs : GemmArgs {
   long ldaux;
 };
 
-// What a wave does with its 64 x 64 block of accumulators at (row0, col0): register r of tile (i, j) is row
-// i * 16 + (lane >> 4) * 4 + r, column j * 16 + (lane & 15).  Rows >= M are neither stored nor loaded from aux.
+// What a wave does with its 64 x 64 block of accumulators at (row0, col0), on the transposed map of gemm_store_rows:
+// register r of tile (i, j) is row i * 16 + (lane & 15), column j * 16 + (lane >> 4) * 4 + r.  Rows >= M are neither
+// stored nor loaded from aux.
 //   VQA_GEMM_EPI_GELU       h = acc (+ bias);  aux = h where aux is given;  C = gelu(h)
 //   VQA_GEMM_EPI_GELU_GRAD  C = (acc (+ bias)) * gelu'(aux)
-// GELU and its derivative are gelu.hpp's, on the pairs (r, r + 1) of a tile's registers: the bits of vqa_gelu_fwd /
-// vqa_gelu_bwd applied to the plain epilogue's output.  FULL: all 64 rows are below M, so nothing is guarded and the
-// code is one basic block (behind a per-row branch the compiler waits for EVERY outstanding load, which serialises
-// the h loads of GELU_GRAD with the arithmetic).
-template <int EPI, bool FULL>
+// GELU and its derivative are gelu.hpp's, on the pairs (0, 1) and (2, 3) of a tile's registers -- neighbouring columns;
+// both are elementwise, so these are the bits of vqa_gelu_fwd / vqa_gelu_bwd applied to the plain epilogue's output.
+// A tile's four values of h, aux and C are one 16-byte access each (VEC) or four dwords, and the tiles go row group by
+// row group (i outer, j inner), so the four accesses of a row cover its 256 bytes -- two whole 128-byte lines -- back to
+// back.  Column tile by column tile, where the other half of a line follows four (GELU with h stored: eight) stores
+// later, the 16-byte form measured 1-2 % SLOWER than the dword stores it replaces in the GELU kernel and no faster in
+// the GELU' kernel; row by row it is 2-3 % and 1-2 % faster (profiles/r13/README.md).  FULL: all 64 rows are below
+// M, so nothing is guarded and the code is one basic block (behind a per-row branch the compiler waits for EVERY
+// outstanding load, which serialises the h loads of GELU_GRAD with the arithmetic).
+template <int EPI, bool FULL, bool VEC>
 __device__ __forceinline__ void gemm_epilogue_rows(const f32x4 (&acc)[4][4], const GemmEpiArgs& g, long row0, int col0,
                                                    int lane) {
-  float bv[4] = {0.0f, 0.0f, 0.0f, 0.0f};                 // ahead of the h loads: a load behind them would wait for them
+  const int colq = col0 + (lane >> 4) * 4;
+  // acc (+ bias) of all 16 tiles ahead of the first store and the first h load, as in gemm_store_rows
+  f32x4 v[4][4];
   if (g.bias) {
+    f32x4 bv[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) bv[j] = g.bias[col0 + j * 16 + (lane & 15)];
+    for (int j = 0; j < 4; ++j) bv[j] = load4<VEC>(g.bias + colq + j * 16);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[i][j] = acc[i][j] + bv[j];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[i][j] = acc[i][j];
   }
   if constexpr (EPI == VQA_GEMM_EPI_GELU) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int col = col0 + j * 16 + (lane & 15);
+    for (int i = 0; i < 4; ++i) {
+      const long row = row0 + i * 16 + (lane & 15);
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; r += 2) {
-          const long row = row0 + i * 16 + (lane >> 4) * 4 + r;
-          const f32x2 v = {acc[i][j][r], acc[i][j][r + 1]};
-          const f32x2 h = g.bias ? v + pk(bv[j]) : v;
-          const f32x2 a = gelu2(h);
-#pragma unroll
-          for (int e = 0; e < 2; ++e)
-            if (FULL || row + e < g.M) {
-              if (g.aux) g.aux[(row + e) * g.ldaux + col] = h[e];
-              g.C[(row + e) * g.ldc + col] = a[e];
-            }
+      for (int j = 0; j < 4; ++j) {
+        const int col = colq + j * 16;
+        const f32x4 h = v[i][j];
+        const f32x2 lo = gelu2(f32x2{h.x, h.y}), hi = gelu2(f32x2{h.z, h.w});
+        if (FULL || row < g.M) {
+          if (g.aux) store4<VEC>(g.aux + row * g.ldaux + col, h);
+          store4<VEC>(g.C + row * g.ldc + col, f32x4{lo.x, lo.y, hi.x, hi.y});
         }
+      }
     }
   } else {
-    // the loads of column tile j + 1 are issued ahead of the arithmetic of tile j (the loop's prefetch and fragment
-    // registers are dead here: 2 x 16 registers of h fit)
-    float hv[2][4][4];
-    auto fetch = [&](int j, float (&dst)[4][4]) {
-      const int col = col0 + j * 16 + (lane & 15);
+    // row group by row group, as above; the loads of row group i + 1 -- whole 128-byte lines of h -- are issued ahead
+    // of the arithmetic of group i (the loop's prefetch and fragment registers are dead here: 2 x 16 registers of h fit)
+    f32x4 hv[2][4];
+    auto fetch = [&](int i, f32x4 (&dst)[4]) {
+      const long row = row0 + i * 16 + (lane & 15);
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const long row = row0 + i * 16 + (lane >> 4) * 4 + r;
-          dst[i][r] = (FULL || row < g.M) ? g.aux[row * g.ldaux + col] : 0.0f;
-        }
+      for (int j = 0; j < 4; ++j)
+        dst[j] = (FULL || row < g.M) ? load4<VEC>(g.aux + row * g.ldaux + colq + j * 16) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     };
     fetch(0, hv[0]);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (j + 1 < 4) fetch(j + 1, hv[(j + 1) & 1]);
-      const int col = col0 + j * 16 + (lane & 15);
+    for (int i = 0; i < 4; ++i) {
+      if (i + 1 < 4) fetch(i + 1, hv[(i + 1) & 1]);
+      const long row = row0 + i * 16 + (lane & 15);
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; r += 2) {
-          const long row = row0 + i * 16 + (lane >> 4) * 4 + r;
-          const f32x2 v = {acc[i][j][r], acc[i][j][r + 1]};
-          const f32x2 d = g.bias ? v + pk(bv[j]) : v;
-          const f32x2 dh = d * gelu_grad2(f32x2{hv[j & 1][i][r], hv[j & 1][i][r + 1]});
-#pragma unroll
-          for (int e = 0; e < 2; ++e)
-            if (FULL || row + e < g.M) g.C[(row + e) * g.ldc + col] = dh[e];
-        }
+      for (int j = 0; j < 4; ++j) {
+        const f32x4 d = v[i][j];
+        const f32x4 h = hv[i & 1][j];
+        const f32x2 lo = f32x2{d.x, d.y} * gelu_grad2(f32x2{h.x, h.y});
+        const f32x2 hi = f32x2{d.z, d.w} * gelu_grad2(f32x2{h.z, h.w});
+        if (FULL || row < g.M) store4<VEC>(g.C + row * g.ldc + colq + j * 16, f32x4{lo.x, lo.y, hi.x, hi.y});
+      }
     }
   }
 }
 
+// The scalar path (a misaligned pointer or an odd stride) need not be fast: it has the guarded form only.
 template <int EPI>
 __device__ __forceinline__ void gemm_epilogue(const f32x4 (&acc)[4][4], const GemmEpiArgs& g, long row0, int col0,
                                               int lane) {
-  if (__builtin_amdgcn_readfirstlane(row0 + 64 <= g.M)) {       // row0 is the wave's: uniform
-    gemm_epilogue_rows<EPI, true>(acc, g, row0, col0, lane);
+  if (!g.vec) {
+    gemm_epilogue_rows<EPI, false, false>(acc, g, row0, col0, lane);
+  } else if (__builtin_amdgcn_readfirstlane(row0 + 64 <= g.M)) {       // row0 is the wave's: uniform
+    gemm_epilogue_rows<EPI, true, true>(acc, g, row0, col0, lane);
   } else {
-    gemm_epilogue_rows<EPI, false>(acc, g, row0, col0, lane);
+    gemm_epilogue_rows<EPI, false, true>(acc, g, row0, col0, lane);
   }
 }
 
@@ -545,7 +606,7 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_epi_kernel(GemmEpiAr
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kPa[t]][i], fb[kPb[t]][j], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[kPb[t]][j], fa[kPa[t]][i], acc[i][j], 0, 0, 0);   // transposed
           // B pieces 0, 1 behind the 24th MFMA and piece 2 behind the 36th.  Stage cur ^ 1 was last read in the step
           // that the barrier above this one ended
           if (t * 16 + i * 4 + j + 1 == 2 * kWideLoadPair) {
@@ -649,7 +710,7 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_epi_kernel(Gemm
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kPa[t]][i], fb[kPb[t]][j], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[kPb[t]][j], fa[kPa[t]][i], acc[i][j], 0, 0, 0);   // transposed
           // a pair of B pieces behind every kWideLoadPair MFMAs of the first half.  Stage cur ^ 1 was last read in
           // the step that the barrier above this one ended
           if ((t * 16 + i * 4 + j + 1) % kWideLoadPair == 0 && (t * 16 + i * 4 + j + 1) / kWideLoadPair <= kWideBPieces / 2) {
@@ -845,6 +906,12 @@ __global__ __launch_bounds__(kBlock) void gemm_pack_b_kernel(const float* __rest
 
 using namespace vqa;
 
+// The large-tile kernels' vector epilogue: every pointer it touches on a 16-byte boundary, every row stride it steps by a
+// multiple of 4 floats (columns start at multiples of 4).  Anything else runs the same lane map with dword accesses.
+static int gemm_vec_ok(const float* C, long ldc, const float* bias, const float* aux = nullptr, long ldaux = 0) {
+  return aligned16(C) && ldc % 4 == 0 && (!bias || aligned16(bias)) && (!aux || (aligned16(aux) && ldaux % 4 == 0));
+}
+
 extern "C" {
 
 size_t vqa_gemm_packed_bytes(int K, int N) {
@@ -872,7 +939,7 @@ int vqa_gemm_bf16x6(const float* A, long lda, const void* packed, const float* b
   if ((M + kGemmBM - 1) / kGemmBM * (N / kGemmBN) > 0x7fffffffL) return VQA_ERR_SHAPE;
   if (!aligned16(A) || !aligned16(packed) || !aligned4(C) || (bias && !aligned4(bias))) return VQA_ERR_ALIGN;
   if (M == 0) return VQA_OK;
-  GemmArgs g{A, static_cast<const bf16x8*>(packed), bias, C, lda, ldc, M, N, K};
+  GemmArgs g{A, static_cast<const bf16x8*>(packed), bias, C, lda, ldc, M, N, K, gemm_vec_ok(C, ldc, bias)};
   const int grid = static_cast<int>((M + kGemmBM - 1) / kGemmBM * (N / kGemmBN));
   gemm_bf16x6_kernel<<<grid, kGemmThreads, 0, static_cast<hipStream_t>(stream)>>>(g);
   return launch_status();
@@ -892,7 +959,7 @@ int vqa_gemm_bf16x6_tile(const float* A, long lda, const void* packed, const flo
   if ((M + kWideBM - 1) / kWideBM * (N / kWideBN) > 0x7fffffffL) return VQA_ERR_SHAPE;
   if (!aligned16(A) || !aligned16(packed) || !aligned4(C) || (bias && !aligned4(bias))) return VQA_ERR_ALIGN;
   if (M == 0) return VQA_OK;
-  GemmArgs g{A, static_cast<const bf16x8*>(packed), bias, C, lda, ldc, M, N, K};
+  GemmArgs g{A, static_cast<const bf16x8*>(packed), bias, C, lda, ldc, M, N, K, gemm_vec_ok(C, ldc, bias)};
   const int grid = static_cast<int>((M + kWideBM - 1) / kWideBM * (N / kWideBN));
   gemm_bf16x6_wide_kernel<<<grid, kGemmThreads, 0, static_cast<hipStream_t>(stream)>>>(g);
   return launch_status();
@@ -914,7 +981,8 @@ int vqa_gemm_bf16x6_epi(const float* A, long lda, const void* packed, const floa
     return VQA_ERR_ALIGN;
   if (aux && (aux == C || aux == A)) return VQA_ERR_SHAPE;
   if (M == 0) return VQA_OK;
-  GemmEpiArgs e{{A, static_cast<const bf16x8*>(packed), bias, C, lda, ldc, M, N, K}, aux, ldaux};
+  GemmEpiArgs e{{A, static_cast<const bf16x8*>(packed), bias, C, lda, ldc, M, N, K, gemm_vec_ok(C, ldc, bias, aux, ldaux)},
+                aux, ldaux};
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int nwg = static_cast<int>(grid);
   if (wide) {
