@@ -449,6 +449,34 @@ int vqa_gemm_bf16x6_small(const float* A, long lda, const void* packed, const fl
 int vqa_gemm_bf16x6_epi(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M,
                         int N, int K, int tile, int epilogue, float* aux, long ldaux, vqa_stream_t stream);
 
+/* vqa_gemm_bf16x6_lse: the cross entropy of an LM head without its logits -- row_loss[row] = logsumexp_c(x[row, c]) -
+ *   x[row, targets[row]] over c < n_valid, with x = A . B + bias the product vqa_gemm_bf16x6_tile would have stored.
+ *   It replaces the vocabulary logits and F.cross_entropy(reduction='none') of the reference's answer ranking
+ *   (ALBEF_attack/models/model_vqa.py:149-203 with the LM loss of ALBEF_attack/models/xbert.py:1265-1271), which
+ *   materialise [rows, vocabulary] twice to obtain one number per row.
+ *   The same prologue, k-loop, packed operand and product order as vqa_gemm_bf16x6_epi, with a third epilogue
+ *   (VQA_GEMM_EPI_LSE of csrc/gemm.hip; it has operands of its own, so it is no value of vqa_gemm_bf16x6_epi's
+ *   `epilogue` and is not defined here): no C is stored.  Every
+ *   wave reduces its 64 x 64 block of x, columns >= n_valid masked to -inf, to one (max, sum exp(x - max)) pair per row
+ *   and stores it to ws; the lane that holds column targets[row] stores that x (the bits of C[row, target]).  A second
+ *   kernel on the same stream folds a row's N / 64 pairs in block order and writes
+ *     lse[row] (nullable) = max + log(sum);
+ *     row_loss[row] = lse - x[row, target];  exactly 0 where targets[row] == ignore_index;  NaN, with
+ *     VQA_FLAG_BAD_LABEL ORed into *flag (nullable), where it is neither ignore_index nor in [0, n_valid).
+ *   exp is the hardware v_exp_f32, as in vqa_ce_rows: 1e-4 relative against torch.  No atomics on the values, fixed
+ *   order: bitwise reproducible, and both tiles give the same bits (a wave's block is 64 x 64 in both).  A NaN in a row
+ *   of A makes that row NaN and no other; a block of 64 columns that is all -inf or all padding contributes (-inf, 0).
+ *   B is packed from a weight padded to N columns (what the pad columns hold does not matter: they are masked);
+ *   bias (nullable) has N entries.  N % 128 == 0, K % 32 == 0, 0 < n_valid <= N, else VQA_ERR_SHAPE; lda rules and
+ *   the tile argument of vqa_gemm_bf16x6_tile.  ws: vqa_gemm_lse_ws_floats(M, N) floats, 16-byte aligned (else
+ *   VQA_ERR_ALIGN): [N / 64][M] pairs, then the M target logits.  targets: int64 [M].  M == 0 VQA_OK.  Never
+ *   allocates, never synchronises.
+ * vqa_gemm_lse_ws_floats: floats of that workspace; 0 for an unsupported shape. */
+long vqa_gemm_lse_ws_floats(long M, int N);
+int vqa_gemm_bf16x6_lse(const float* A, long lda, const void* packed, const float* bias, long M, int N, int K,
+                        int n_valid, const int64_t* targets, long ignore_index, float* ws, float* row_loss, float* lse,
+                        int* flag, int tile, vqa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

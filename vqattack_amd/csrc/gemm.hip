@@ -32,7 +32,7 @@
 // 8 n-tiles x 3 planes a workgroup stages per k-step are therefore one contiguous 24 KiB run.
 //
 // Epilogue of the large tiles: the A and B operand maps of the 16x16x32 MFMA are the same map (row or column on
-// lane & 15, k-chunk on lane >> 4), so the six large-tile kernels hand the instruction (B fragment, A fragment) and get
+// lane & 15, k-chunk on lane >> 4), so the eight large-tile kernels hand the instruction (B fragment, A fragment) and get
 // the transposed tile: a lane's four accumulator registers are four consecutive COLUMNS of one row.  Each of a lane's 16
 // tiles is then one 16-byte store (and, in the GELU' kernel, one 16-byte load of h) instead of four dword accesses that
 // each cover 4 rows x 64 bytes, and a row's four tiles are issued back to back (whole 128-byte lines); the same products are summed in the same order per element, so the bits are those of
@@ -419,9 +419,19 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_kernel(GemmArgs
 // k-step order and (wide) load placement, and the unfused kernels' code objects do not change by a single instruction
 // (a shared __device__ body changed their prologue scheduling and LDS addressing).  tests/test_gemm_epilogue.py holds
 // the copies to the originals' loop budgets and to the bits of the unfused pair.
+
+// The third epilogue of the two kernels below, behind an entry point of its own (vqa_gemm_bf16x6_lse): not a value of
+// vqa_gemm_bf16x6_epi's `epilogue` argument, so the header does not define it.
+#define VQA_GEMM_EPI_LSE 3
+
 struct GemmEpiArgs : GemmArgs {
   float* aux;          // GELU: where the pre-activation goes (nullable); GELU_GRAD: the pre-activation (read only)
   long ldaux;
+  // VQA_GEMM_EPI_LSE only (C, aux unused; vec = the bias may be read 16 bytes at a time)
+  const int64_t* targets;   // [M]
+  f32x2* part;              // [N / 64][M] (max, sum exp(x - max)) of a row's 64 columns
+  float* tgt;               // [M] the logit at targets[row]
+  int n_valid;              // columns >= n_valid are padding: masked to -inf
 };
 
 // What a wave does with its 64 x 64 block of accumulators at (row0, col0), on the transposed map of gemm_store_rows:
@@ -500,11 +510,113 @@ __device__ __forceinline__ void gemm_epilogue_rows(const f32x4 (&acc)[4][4], con
   }
 }
 
+// ---- row log-sum-exp in the epilogue: an LM head's cross entropy without its [M, V] logits ------------------------------
+// VQA_GEMM_EPI_LSE stores no C.  With x = acc (+ bias) on the map above and columns >= n_valid masked to -inf, a wave
+// reduces each of its 64 rows over its 64 columns to (m, s) = (max x, sum exp(x - m)) and stores the pair to
+// part[col0 / 64][row]; lse_combine_kernel folds a row's N / 64 pairs in block order.  A lane holds 16 of a row's values
+// (4 tiles x 4 registers); the other 48 sit in the lanes with the same lane & 15, which v_permlane16_swap and
+// v_permlane32_swap reach in two steps: with both operands the same register, the swap leaves (even 16-lane rows, odd
+// rows) resp. (lower half, upper half) duplicated in its two results, and max / + of the two is the same value in the
+// same order in every lane.  The maximum is reduced first and the exponentials are taken against the row's maximum of
+// the block: 64 v_exp_f32 per lane and no rescaling.  Lane l then keeps row l (row group l >> 4), so the pairs leave as
+// one 512-byte run of 8-byte stores per wave.  A block without a finite value (all -inf, or all padding) gives
+// (-inf, 0): exp is taken against 0 there, not against -inf.  A NaN among a row's values makes s NaN; m skips it.
+// The lane that holds column targets[row] stores that x -- the bits the plain epilogue would have put at
+// C[row, target] -- to tgt[row]: one writer per row over the whole grid.  Both large tiles give a wave a 64 x 64 block
+// at a multiple of 64, so they write the same pairs.
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+// The two results are read as .x / .y of a non-const vector: through __builtin_bit_cast(float, r[1]) of a const one the
+// compiler handed out element 0 twice (profiles/r14/README.md).
+__device__ __forceinline__ float lse_swap16(float v, bool is_max) {
+  const unsigned u = __builtin_bit_cast(unsigned, v);
+  u32x2 r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+  const unsigned ua = r.x, ub = r.y;
+  const float a = __builtin_bit_cast(float, ua), b = __builtin_bit_cast(float, ub);
+  return is_max ? fmaxf(a, b) : a + b;
+}
+__device__ __forceinline__ float lse_swap32(float v, bool is_max) {
+  const unsigned u = __builtin_bit_cast(unsigned, v);
+  u32x2 r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+  const unsigned ua = r.x, ub = r.y;
+  const float a = __builtin_bit_cast(float, ua), b = __builtin_bit_cast(float, ub);
+  return is_max ? fmaxf(a, b) : a + b;
+}
+
+__device__ __forceinline__ void gemm_epilogue_lse(const f32x4 (&acc)[4][4], const GemmEpiArgs& g, long row0, int col0,
+                                                  int lane) {
+  const int colq = col0 + (lane >> 4) * 4;
+  // every load -- the bias and the four targets of this lane's rows (clamped like the rows of A) -- ahead of the
+  // first store, as in gemm_store_rows
+  f32x4 bv[4];
+  if (g.bias) {
+    if (g.vec) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bv[j] = load4<true>(g.bias + colq + j * 16);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bv[j] = load4<false>(g.bias + colq + j * 16);
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bv[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  }
+  int tcol[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    long row = row0 + i * 16 + (lane & 15);
+    row = row < g.M ? row : g.M - 1;
+    const long t = g.targets[row];
+    tcol[i] = (t >= 0 && t < g.n_valid) ? static_cast<int>(t) : -1;     // ignore_index / a bad label: nobody writes tgt
+  }
+  const bool add_bias = g.bias != nullptr;
+  const float ninf = -__builtin_inff();
+  float mrow[4], srow[4], tval[4];
+  bool mine[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float x[4][4];
+    float m = ninf;
+    tval[i] = 0.0f, mine[i] = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int col = colq + j * 16 + r;
+        const float v = add_bias ? acc[i][j][r] + bv[j][r] : acc[i][j][r];
+        if (col == tcol[i]) tval[i] = v, mine[i] = true;
+        x[j][r] = col < g.n_valid ? v : ninf;
+        m = fmaxf(m, x[j][r]);
+      }
+    m = lse_swap32(lse_swap16(m, true), true);
+    const float ref = m == ninf ? 0.0f : m;
+    float s = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) s += __expf(x[j][r] - ref);
+    s = lse_swap32(lse_swap16(s, false), false);
+    mrow[i] = m, srow[i] = s;
+  }
+  // the stores behind the last use of a loaded value (one memory counter)
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const long row = row0 + i * 16 + (lane & 15);
+    if (mine[i] && row < g.M) g.tgt[row] = tval[i];
+  }
+  const int grp = lane >> 4;
+  const float mo = grp == 0 ? mrow[0] : grp == 1 ? mrow[1] : grp == 2 ? mrow[2] : mrow[3];
+  const float so = grp == 0 ? srow[0] : grp == 1 ? srow[1] : grp == 2 ? srow[2] : srow[3];
+  const long row = row0 + lane;                         // = row0 + grp * 16 + (lane & 15)
+  if (row < g.M) g.part[static_cast<long>(col0 >> 6) * g.M + row] = f32x2{mo, so};
+}
+
 // The scalar path (a misaligned pointer or an odd stride) need not be fast: it has the guarded form only.
 template <int EPI>
 __device__ __forceinline__ void gemm_epilogue(const f32x4 (&acc)[4][4], const GemmEpiArgs& g, long row0, int col0,
                                               int lane) {
-  if (!g.vec) {
+  if constexpr (EPI == VQA_GEMM_EPI_LSE) {
+    gemm_epilogue_lse(acc, g, row0, col0, lane);
+  } else if (!g.vec) {
     gemm_epilogue_rows<EPI, false, false>(acc, g, row0, col0, lane);
   } else if (__builtin_amdgcn_readfirstlane(row0 + 64 <= g.M)) {       // row0 is the wave's: uniform
     gemm_epilogue_rows<EPI, true, true>(acc, g, row0, col0, lane);
@@ -881,6 +993,44 @@ __global__ __launch_bounds__(kBlock) void gemm_splitk_combine_kernel(const f32x4
   }
 }
 
+// Folds a row's N / 64 (max, sum) pairs in block order, one row per lane (consecutive lanes read consecutive pairs of a
+// block): (mx, sm) <- (max(mx, m), sm * exp(mx - max) + s * exp(m - max)); nothing is rescaled while the running maximum
+// is still -inf (exp(-inf - -inf) would be NaN), and a NaN sum stays NaN.  lse = mx + log(sm);
+// row_loss = log(sm) - (tgt - mx): lse - tgt without rounding at ulp(mx) first (as vqa_ce_rows forms it).
+__global__ __launch_bounds__(kBlock) void lse_combine_kernel(const f32x2* __restrict__ part, const float* __restrict__ tgt,
+                                                             const int64_t* __restrict__ targets, long ignore_index,
+                                                             long M, int nblk, int n_valid, float* __restrict__ row_loss,
+                                                             float* __restrict__ lse, int* __restrict__ flag) {
+  const float ninf = -__builtin_inff();
+  for (long row = static_cast<long>(blockIdx.x) * blockDim.x + threadIdx.x; row < M;
+       row += static_cast<long>(gridDim.x) * blockDim.x) {
+    float mx = ninf, sm = 0.0f;
+    for (int b = 0; b < nblk; ++b) {
+      const f32x2 p = part[static_cast<long>(b) * M + row];
+      const float nm = fmaxf(mx, p.x);
+      if (nm == ninf) {
+        sm += p.y;                                      // 0, or the NaN of a block that met one
+      } else {
+        sm = sm * __expf(mx - nm) + p.y * __expf(p.x - nm);
+        mx = nm;
+      }
+    }
+    const float ls = logf(sm);
+    if (lse) lse[row] = mx + ls;
+    const long t = targets[row];
+    float loss = 0.0f;
+    if (t != ignore_index) {
+      if (t >= 0 && t < n_valid) {
+        loss = ls - (tgt[row] - mx);
+      } else {
+        loss = __builtin_nanf("");
+        if (flag) atomicOr(flag, VQA_FLAG_BAD_LABEL);
+      }
+    }
+    row_loss[row] = loss;
+  }
+}
+
 // One thread per (k-tile, n-tile, lane): 8 consecutive k of one column, split into the three planes.
 __global__ __launch_bounds__(kBlock) void gemm_pack_b_kernel(const float* __restrict__ w, long ldw, int trans,
                                                              bf16x8* __restrict__ out, int K, int N) {
@@ -992,6 +1142,39 @@ int vqa_gemm_bf16x6_epi(const float* A, long lda, const void* packed, const floa
     if (epilogue == VQA_GEMM_EPI_GELU) gemm_bf16x6_epi_kernel<VQA_GEMM_EPI_GELU><<<nwg, kGemmThreads, 0, st>>>(e);
     else gemm_bf16x6_epi_kernel<VQA_GEMM_EPI_GELU_GRAD><<<nwg, kGemmThreads, 0, st>>>(e);
   }
+  return launch_status();
+}
+
+long vqa_gemm_lse_ws_floats(long M, int N) {
+  if (M <= 0 || N <= 0 || N % kGemmBN) return 0;
+  return (static_cast<long>(N / 64) * 2 + 1) * M;        // the pairs, then tgt
+}
+
+int vqa_gemm_bf16x6_lse(const float* A, long lda, const void* packed, const float* bias, long M, int N, int K,
+                        int n_valid, const int64_t* targets, long ignore_index, float* ws, float* row_loss, float* lse,
+                        int* flag, int tile, vqa_stream_t stream) {
+  clear_stale_error();
+  if (tile != VQA_GEMM_TILE_256X128 && tile != VQA_GEMM_TILE_128X256) return VQA_ERR_SHAPE;
+  if (!A || !packed || !targets || !ws || !row_loss) return VQA_ERR_NULL;
+  if (M < 0 || N <= 0 || K <= 0 || K % kGemmBK || N % kGemmBN || lda < K || lda % 4) return VQA_ERR_SHAPE;
+  if (n_valid <= 0 || n_valid > N) return VQA_ERR_SHAPE;
+  const bool wide = tile == VQA_GEMM_TILE_128X256 && N % kWideBN == 0;     // every other N runs the 256 x 128 tile
+  const long grid = wide ? (M + kWideBM - 1) / kWideBM * (N / kWideBN) : (M + kGemmBM - 1) / kGemmBM * (N / kGemmBN);
+  if (grid > 0x7fffffffL) return VQA_ERR_SHAPE;
+  if (!aligned16(A) || !aligned16(packed) || !aligned16(ws) || (bias && !aligned4(bias)) || !aligned4(row_loss) ||
+      (lse && !aligned4(lse)) || (flag && !aligned4(flag)) || (reinterpret_cast<uintptr_t>(targets) & 7u))
+    return VQA_ERR_ALIGN;
+  if (M == 0) return VQA_OK;
+  const int nblk = N / 64;
+  f32x2* part = reinterpret_cast<f32x2*>(ws);
+  float* tgt = ws + static_cast<long>(nblk) * 2 * M;
+  GemmEpiArgs e{{A, static_cast<const bf16x8*>(packed), bias, nullptr, lda, 0, M, N, K, !bias || aligned16(bias)},
+                nullptr, 0, targets, part, tgt, n_valid};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (wide) gemm_bf16x6_wide_epi_kernel<VQA_GEMM_EPI_LSE><<<static_cast<int>(grid), kGemmThreads, 0, st>>>(e);
+  else gemm_bf16x6_epi_kernel<VQA_GEMM_EPI_LSE><<<static_cast<int>(grid), kGemmThreads, 0, st>>>(e);
+  lse_combine_kernel<<<blocks_for(static_cast<size_t>(M), kBlock), kBlock, 0, st>>>(part, tgt, targets, ignore_index, M,
+                                                                                   nblk, n_valid, row_loss, lse, flag);
   return launch_status();
 }
 

@@ -723,11 +723,15 @@ def gelu_bwd(h, da, out=None):
 
 class PackedWeight:
     """A frozen [K, N] GEMM operand packed for ``vqa_gemm_bf16x6``: three bf16 planes in the kernel's fragment order
-    (``include/vqattack_hip.h``), held as raw bytes."""
-    __slots__ = ("data", "K", "N")
+    (``include/vqattack_hip.h``), held as raw bytes.  ``n_valid``: how many of the N columns are real -- N itself, except
+    for an LM head padded by ``gemm_pack_vocab`` (``gemm_lse`` masks the rest)."""
+    __slots__ = ("data", "K", "N", "n_valid")
 
-    def __init__(self, data, K, N):
+    def __init__(self, data, K, N, n_valid=None):
         self.data, self.K, self.N = data, K, N
+        self.n_valid = N if n_valid is None else int(n_valid)
+        if not 0 < self.n_valid <= N:
+            raise ValueError("n_valid must be in (0, {}], got {}".format(N, n_valid))
 
 
 def gemm_shape_ok(N, K):
@@ -754,6 +758,25 @@ def gemm_pack(w, trans):
     with _on(w):
         check(lib().vqa_gemm_pack_b(_p(w), w.shape[1], int(bool(trans)), _p(data), K, N, stream_for(w)), "vqa_gemm_pack_b")
     return PackedWeight(data, K, N)
+
+
+VOCAB_PAD = 256      # both large tiles take N % 256 == 0
+
+
+def gemm_pack_vocab(w):
+    """Pack an LM-head weight ``w`` [V, K] (logits = h @ w.t()) for ``gemm_lse``: V is padded with zero rows to a multiple
+    of 256, so both tiles apply, and the result carries ``n_valid = V``."""
+    dev_f32(w, "w")
+    if w.dim() != 2:
+        raise ValueError("w must be 2-D, got shape {}".format(tuple(w.shape)))
+    V, K = w.shape
+    Vp = -(-V // VOCAB_PAD) * VOCAB_PAD
+    if Vp != V:
+        padded = torch.zeros(Vp, K, dtype=torch.float32, device=w.device)
+        padded[:V] = w
+        w = padded
+    packed = gemm_pack(w.contiguous(), trans=True)
+    return PackedWeight(packed.data, packed.K, packed.N, V)
 
 
 GEMM_TILES = {"large": 0, "wide": 1}      # VQA_GEMM_TILE_256X128, VQA_GEMM_TILE_128X256 of include/vqattack_hip.h
@@ -900,3 +923,45 @@ def gemm_small(a, packed, bias=None, out=None, ksplit=1):
                                               packed.N, packed.K, ksplit, ptr(ws), stream_for(a)),
                   "vqa_gemm_bf16x6_small")
     return out
+
+
+def gemm_lse(a, packed, bias, targets, ignore_index=-100, tile=None, want_lse=False, flag=None, want_target_logit=False):
+    """Per-row cross entropy of ``logits = a @ B (+ bias)`` against ``targets`` without the logits
+    (``vqa_gemm_bf16x6_lse``): ``row_loss`` (M,) = logsumexp over the first ``packed.n_valid`` columns minus the target's
+    logit; exactly 0 where ``targets == ignore_index``; NaN (and VQA_FLAG_BAD_LABEL in ``flag``, an int32[1] word) for a
+    target that is neither.  ``packed``: from ``gemm_pack_vocab``; columns >= ``n_valid`` are masked whatever they hold.
+    ``bias``: None, (n_valid,) or (N,).  ``targets``: int64 (M,).  Returns ``row_loss``, or ``(row_loss, lse)`` with
+    ``want_lse``; ``want_target_logit`` appends the target logits (M,) -- a view of the workspace, defined only where the
+    target is in range: the bits ``gemm`` puts at ``[row, target]``.  Both tiles give the same bits."""
+    dev_f32(a, "a", contiguous=False)
+    if a.dim() != 2 or a.shape[1] != packed.K or a.stride(1) != 1 or a.stride(0) % 4:
+        raise ValueError("a must be (M, {}) with unit column stride and a row stride % 4 == 0, got shape {} strides {}"
+                         .format(packed.K, tuple(a.shape), a.stride()))
+    M, N = a.shape[0], packed.N
+    if not isinstance(targets, torch.Tensor) or not targets.is_cuda or targets.dtype != torch.int64 or \
+            tuple(targets.shape) != (M,) or not targets.is_contiguous():
+        raise TypeError("targets must be a contiguous int64 HIP tensor of shape ({},)".format(M))
+    if bias is not None:
+        dev_f32(bias, "bias")
+        if bias.numel() == packed.n_valid and packed.n_valid != N:
+            bias = torch.cat([bias.reshape(-1), bias.new_zeros(N - packed.n_valid)])
+        _rows_ok("bias", bias, N)
+    if flag is not None and (not isinstance(flag, torch.Tensor) or not flag.is_cuda or flag.dtype != torch.int32 or
+                             flag.numel() != 1):
+        raise TypeError("flag must be an int32[1] HIP tensor (ops.new_flag)")
+    if tile is None:
+        from .whitebox import _fused
+        tile = _fused.gemm_tile(M, N, packed.K)
+    if tile not in GEMM_TILES:
+        raise ValueError("tile must be one of {}, got {!r}".format(sorted(GEMM_TILES), tile))
+    same_device(a, packed.data, bias, targets, flag)
+    row_loss = torch.empty(M, dtype=torch.float32, device=a.device)
+    lse = torch.empty(M, dtype=torch.float32, device=a.device) if want_lse else None
+    ws = torch.empty(max(1, lib().vqa_gemm_lse_ws_floats(M, N)), dtype=torch.float32, device=a.device)
+    if M:
+        with _on(a):
+            check(lib().vqa_gemm_bf16x6_lse(_p(a), a.stride(0), _p(packed.data), ptr(bias), M, N, packed.K, packed.n_valid,
+                                            _p(targets), int(ignore_index), _p(ws), _p(row_loss), ptr(lse), ptr(flag),
+                                            GEMM_TILES[tile], stream_for(a)), "vqa_gemm_bf16x6_lse")
+    res = (row_loss,) + ((lse,) if want_lse else ()) + ((ws[(N // 64) * 2 * M:][:M],) if want_target_logit else ())
+    return res[0] if len(res) == 1 else res

@@ -698,3 +698,74 @@ def encode_fusion(text_embeds, text_masks, image_states, spec):
     bias_t, bstr = _attn._bias_view(pad, b, spec.heads, t, t)
     outs = _FusionEncoder.apply(text_embeds, image_states, _FusionCall(spec, bias_t, bstr, torch.is_grad_enabled()))
     return [text_embeds] + list(outs[:-1]), outs[-1]
+
+
+# ------------------------------------------------------------------------------------ ALBEF's answer decoder (forward only)
+# Reference computation: the second pass of ``rank_answer`` (``ALBEF_attack/models/model_vqa.py:149-203``): the causal
+# ``text_decoder`` on the k candidate answers of every question, with cross-attention into the question states tiled k
+# times (``tile(question_states, 0, k)``).  The candidates of one question share their keys and values, so here nothing is
+# tiled: the cross-attention K / V of all layers come from ONE stacked GEMM over the B T question-state rows (not
+# B k T), and the k candidates are folded into the QUERY axis of the cross-attention -- candidate rows are contiguous by
+# (sample, candidate, position), so the (B k L, D) query projection is a (B, k L, H, 64) view, the keys / values are the
+# (B, T, H, 64) slices of ``_kv_slices`` and the bias is the (B, 1, 1, T) question key padding.  Queries never interact:
+# row by row the arithmetic of the tiled form, on the attention kernel that exists.
+def decode_candidates(x0, self_bias, question_states, question_pad, k, spec):
+    """``x0``: (B k, L, D) decoder embeddings of the candidates, sample-major; ``self_bias``: additive (B k, 1, L, L)
+    causal-and-padding mask; ``question_states``: (B, T, D); ``question_pad``: additive (B, 1, 1, T) key padding;
+    ``spec``: ``bert_spec`` of the decoder layers (every layer has cross-attention).  Returns the final states
+    (B k, L, D).  Forward only (the victim runs under ``no_grad``): nothing is kept.  No host read or synchronisation."""
+    for name, ten in (("x0", x0), ("self_bias", self_bias), ("question_states", question_states),
+                      ("question_pad", question_pad)):
+        if not ten.is_cuda or ten.dtype != torch.float32 or ten.device != x0.device:
+            raise ops._hip.HipExtensionError("the fused decoder runs on fp32 HIP tensors of one device ({})".format(name))
+    n, length, d = x0.shape
+    b, t = question_states.shape[0], question_states.shape[1]
+    if n != b * k or question_states.shape[2] != d or any(lay.cross is None for lay in spec.layers):
+        raise ValueError("decode_candidates: {} candidate rows for {} questions x k = {}, width {} / {}".format(
+            n, b, k, d, question_states.shape[2]))
+    rows, heads = n * length, spec.heads
+    scale = _attn.HEAD_DIM ** -0.5
+    bias_s, bstr_s = _attn._bias_view(self_bias, n, heads, length, length)
+    bias_c, bstr_c = _attn._bias_view(question_pad, b, heads, k * length, t)
+    qs = (question_states if question_states.is_contiguous() else question_states.contiguous()).view(b * t, d)
+    kv = _linear(qs, spec.wkv, spec.bkv, spec.packed_kv)                  # K / V of every layer, once per QUESTION
+    x = (x0 if x0.is_contiguous() else x0.contiguous()).view(rows, d)
+    for lay in spec.layers:
+        qkv5 = _linear(x, lay.wqkv, lay.bqkv, lay.packed["qkv"]).view(n, length, 3, heads, _attn.HEAD_DIM)
+        o, _lse, _ = _attn._forward(qkv5[:, :, 0], qkv5[:, :, 1], qkv5[:, :, 2], bias_s, bstr_s, scale)
+        del qkv5
+        x, _ = _post_ln(x, _linear(o.view(rows, d), lay.wo, lay.bo, lay.packed["o"]), lay.ln_attn, spec.eps, False)
+        q = _linear(x, lay.wq_c, lay.bq_c, lay.packed["q_c"]).view(b, k * length, heads, _attn.HEAD_DIM)
+        kc, vc = _kv_slices(kv, lay.cross, b, t, heads)
+        o, _lse, _ = _attn._forward(q, kc, vc, bias_c, bstr_c, scale)
+        del q
+        x, _ = _post_ln(x, _linear(o.view(rows, d), lay.wo_c, lay.bo_c, lay.packed["o_c"]), lay.ln_cross, spec.eps, False)
+        _h, a = _linear_gelu(x, lay.w1, lay.b1, lay.packed["fc1"], False)
+        x, _ = _post_ln(x, _linear(a, lay.w2, lay.b2, lay.packed["fc2"]), lay.ln_out, spec.eps, False)
+        del a, o
+    return x.view(n, length, d)
+
+
+class LmHeadSpec:
+    """An LM head ``LayerNorm(gelu(dense(x))) @ word.t() + bias`` in the form ``lm_head_row_loss`` consumes: the dense
+    weight packed by ``_pack``, the vocabulary weight packed by ``ops.gemm_pack_vocab`` (padded to a multiple of 256 rows,
+    ``n_valid`` = the vocabulary) and the bias padded with it."""
+
+    def __init__(self, dense, ln, word, bias):
+        self.w, self.b, self.ln, self.eps = _c(dense.weight), _c(dense.bias), _ln(ln), ln.eps
+        self.packed = _pack(self.w)
+        self.vocab = ops.gemm_pack_vocab(_c(word))
+        pad = self.vocab.N - self.vocab.n_valid
+        self.bias = torch.cat([bias.detach().reshape(-1), bias.new_zeros(pad)]).contiguous()
+
+
+def lm_head_row_loss(states, targets, head, ignore_index=-100):
+    """Per-row cross entropy of the LM head on ``states`` (rows, D) against ``targets`` (rows,) int64 WITHOUT the
+    (rows, vocabulary) logits: dense + GELU, LayerNorm, then ``ops.gemm_lse`` (``vqa_gemm_bf16x6_lse``)."""
+    rows, d = states.shape
+    _h, a = _linear_gelu(states, head.w, head.b, head.packed, False)
+    y = torch.empty_like(a)
+    mean = torch.empty(rows, dtype=torch.float32, device=a.device)
+    rstd = torch.empty(rows, dtype=torch.float32, device=a.device)
+    ops.ln_fwd(a, head.ln[0], head.ln[1], y, mean, rstd, head.eps)
+    return ops.gemm_lse(y, head.vocab, head.bias, targets, ignore_index=ignore_index)

@@ -170,9 +170,13 @@ class FrozenAlbef(nn.Module):
         # VQA_FUSED_TEXT=1 or fused_text = True.  Off by default: DESIGN section 5 gives the rule for switching it on
         self.fused_text = os.environ.get("VQA_FUSED_TEXT", "0") == "1"
         self._fused_text_spec = None
+        # the answer ranking's second pass (the decoder on the k candidates + the LM loss) has one too
+        # (_fused.decode_candidates, ops.gemm_lse): VQA_FUSED_RANK=1 or fused_rank = True.  Off by default, same rule
+        self.fused_rank = os.environ.get("VQA_FUSED_RANK", "0") == "1"
+        self._fused_rank_spec = self._fused_rank_head = None
 
     def _apply(self, fn, *args, **kwargs):
-        self._fused_spec = self._fused_text_spec = None
+        self._fused_spec = self._fused_text_spec = self._fused_rank_spec = self._fused_rank_head = None
         return super()._apply(fn, *args, **kwargs)
 
     def _init(self, seed):
@@ -219,7 +223,7 @@ class FrozenAlbef(nn.Module):
     def invalidate_fused(self):
         """Drop the cached fused-encoder spec: the next pass rebuilds it from the current weights.  Needed only after
         weight updates ``_fused.weights_key`` cannot see (writes through ``p.data``)."""
-        self._fused_spec = self._fused_text_spec = None
+        self._fused_spec = self._fused_text_spec = self._fused_rank_spec = self._fused_rank_head = None
 
     # ---- reference checkpoints ------------------------------------------------------------------------------
     def load_reference_state_dict(self, state_dict, strict=True):
@@ -363,10 +367,40 @@ class FrozenAlbef(nn.Module):
         h = self.dec_ln(F.gelu(self.dec_dense(x)))
         return F.linear(h, self.dec_word.weight, self.dec_bias)
 
+    def _answer_loss_fused(self, ids, atts, targets, question_states, question_atts, k):
+        """Summed LM loss (B k, 1) of the candidate rows ``ids`` (B k, L) on the graph-free path: the decoder without the
+        k-fold copy of the question states or their K / V (``_fused.decode_candidates``), the head on positions 0 .. L-2
+        only, and the per-token cross entropy from the vocabulary GEMM's epilogue (``ops.gemm_lse``) -- the
+        (B k, L, vocabulary) logits are never written.  No host read."""
+        cfg = self.cfg
+        n, length = ids.shape
+        key = _fused.weights_key(self.dec_layers)
+        if self._fused_rank_spec is None or self._fused_rank_spec[0] != key:       # the spec holds packed COPIES
+            self._fused_rank_spec = (key, _fused.bert_spec(self.dec_layers, cfg.heads, cfg.bert_ln_eps))
+        key = (_fused.weights_key(self.dec_dense), _fused.weights_key(self.dec_ln), _fused.weights_key(self.dec_word),
+               (self.dec_bias.data_ptr(), self.dec_bias._version))
+        if self._fused_rank_head is None or self._fused_rank_head[0] != key:
+            self._fused_rank_head = (key, _fused.LmHeadSpec(self.dec_dense, self.dec_ln, self.dec_word.weight, self.dec_bias))
+        e = self.dec_word(ids) + self.dec_type.weight[0]
+        e = self.dec_emb_ln(e + self.dec_pos.weight[:length].unsqueeze(0))
+        causal = torch.ones(length, length, dtype=torch.bool, device=ids.device).tril()
+        keep = causal[None, None] & atts.bool()[:, None, None, :]
+        self_mask = torch.zeros(n, 1, length, length, device=ids.device).masked_fill(~keep, float("-inf"))
+        cross_mask = torch.zeros(question_atts.shape[0], 1, 1, question_atts.shape[1], device=ids.device).masked_fill(
+            ~question_atts.bool()[:, None, None, :], float("-inf"))
+        states = _fused.decode_candidates(e, self_mask, question_states, cross_mask, k, self._fused_rank_spec[1])
+        rows = states[:, :-1, :].reshape(n * (length - 1), cfg.dim)                  # the last position predicts nothing
+        tok = _fused.lm_head_row_loss(rows, targets[:, 1:].reshape(-1), self._fused_rank_head[1], ignore_index=-100)
+        return tok.view(n, -1).sum(1, keepdim=True)
+
     @torch.no_grad()
-    def rank_answer(self, question_states, question_atts, k=None):
+    def rank_answer(self, question_states, question_atts, k=None, want_log_probs=False):
         """Top-k answers per question, re-ranked by the full-sequence LM likelihood; returns (topk_ids, topk_probs),
-        both (B, k), sorted by probability.  Batched restatement of model_vqa.py:149-203 (no per-question loop)."""
+        both (B, k), sorted by probability.  Batched restatement of model_vqa.py:149-203 (no per-question loop).
+        ``want_log_probs``: also return the candidates' log-likelihoods (log P(first token) - LM loss) in the same order.
+
+        With ``fused_rank`` the second pass runs ``_answer_loss_fused``; the first pass (B rows, one token) is the same
+        code either way, so the candidate set has the same bits."""
         cfg = self.cfg
         k = min(k or cfg.k_test, cfg.n_answers)
         b = question_states.shape[0]
@@ -378,16 +412,22 @@ class FrozenAlbef(nn.Module):
         ids = ans[topk_ids].reshape(b * k, -1)                                       # (B*k, L)
         atts = ans_atts[topk_ids].reshape(b * k, -1)
         targets = ids.masked_fill(ids == cfg.pad_id, -100)
-        q_states = question_states.repeat_interleave(k, dim=0)
-        q_atts = question_atts.repeat_interleave(k, dim=0)
-        lm = self._decode(ids, atts, q_states, q_atts)
-        # BertLMHeadModel loss with reduction='none' (xbert.py:1265-1271): shift, per-token CE, sum over the sequence
-        tok = F.cross_entropy(lm[:, :-1, :].reshape(-1, cfg.vocab), targets[:, 1:].reshape(-1), reduction="none",
-                              ignore_index=-100)
-        answer_loss = tok.view(b * k, -1).sum(1, keepdim=True)
+        if self.fused_rank and question_states.is_cuda and question_states.dtype == torch.float32 and \
+                _fused.supported(cfg.dim, cfg.heads):
+            answer_loss = self._answer_loss_fused(ids, atts, targets, question_states, question_atts, k)
+        else:
+            q_states = question_states.repeat_interleave(k, dim=0)
+            q_atts = question_atts.repeat_interleave(k, dim=0)
+            lm = self._decode(ids, atts, q_states, q_atts)
+            # BertLMHeadModel loss with reduction='none' (xbert.py:1265-1271): shift, per-token CE, sum over the sequence
+            tok = F.cross_entropy(lm[:, :-1, :].reshape(-1, cfg.vocab), targets[:, 1:].reshape(-1), reduction="none",
+                                  ignore_index=-100)
+            answer_loss = tok.view(b * k, -1).sum(1, keepdim=True)
         log_probs = torch.cat([topk_probs.view(-1, 1).log(), -answer_loss], dim=1).sum(1).view(b, k)
         probs = F.softmax(log_probs, dim=-1)
         probs, rerank = probs.topk(k, dim=1)
+        if want_log_probs:
+            return torch.gather(topk_ids, 1, rerank), probs, torch.gather(log_probs, 1, rerank)
         return torch.gather(topk_ids, 1, rerank), probs
 
     @torch.no_grad()
