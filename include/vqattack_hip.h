@@ -414,6 +414,20 @@ int vqa_gemm_bf16x6(const float* A, long lda, const void* packed, const float* b
 int vqa_gemm_bf16x6_tile(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M,
                          int N, int K, int tile, vqa_stream_t stream);
 
+/* vqa_gemm_bf16x6_half: vqa_gemm_bf16x6 on 128 x 128 output tiles (half a large tile's k-loop work per workgroup, one
+ *   workgroup per CU like them); argument rules and return codes of vqa_gemm_bf16x6, the same bits.
+ * vqa_gemm_bf16x6_tail: one product in two launches, back to back on `stream`: rows [0, m_split) on `tile` as
+ *   vqa_gemm_bf16x6_tile runs them, rows [m_split, M) on the 128 x 128 tile.  The large tiles run in rounds of one
+ *   workgroup per CU and the last round takes as long as a full one; with m_split at the end of the last full round
+ *   (ops.gemm_tail_plan) the remaining rows run as twice as many workgroups of half the length.  Every output has the
+ *   bits vqa_gemm_bf16x6_tile gives it.  Argument rules and return codes of vqa_gemm_bf16x6_tile; 0 <= m_split <= M, else
+ *   VQA_ERR_SHAPE.  m_split == M is vqa_gemm_bf16x6_tile itself, m_split == 0 vqa_gemm_bf16x6_half itself.  A refused call
+ *   launches nothing.  Never allocates, never synchronises. */
+int vqa_gemm_bf16x6_half(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M,
+                         int N, int K, vqa_stream_t stream);
+int vqa_gemm_bf16x6_tail(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M,
+                         int N, int K, int tile, long m_split, vqa_stream_t stream);
+
 /* vqa_gemm_bf16x6_small: the same product from the same packed operand on 64 x 128 output tiles, for row counts whose
  *   256 x 128 tiles cannot fill the device, with an optional deterministic split over K.  Argument rules and return
  *   codes of vqa_gemm_bf16x6; 1 <= ksplit <= min(K / 32, 16), else VQA_ERR_SHAPE.  With nk = K / 32 k-steps, part p covers

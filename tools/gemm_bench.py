@@ -5,6 +5,13 @@ TunableOp solutions active, as in bench.py).  For the shapes whose N is the FFN 
 GELU epilogues of ``ops.gemm(..., epilogue=)`` are timed as further interleaved variants against the two-step form they
 replace, on the tile the policy picks for the shape: "fused_gelu" (h stored) and "fused_gelu_nosave" against
 "pair_gelu" (GEMM + ``vqa_gelu_fwd``), "fused_gelu_grad" against "pair_gelu_grad" (GEMM + ``vqa_gelu_bwd`` in place).
+Every shape is also run whole on the 128 x 128 tile ("half", ``ops.gemm_half``).  Where ``ops.gemm_tail_plan`` cuts the
+shape on this device's CU count (``VQA_GEMM_TAIL_CUS`` pins another), "tail" -- the policy tile up to the cut, the half
+tile behind it (``vqa_gemm_bf16x6_tail``) -- is timed against "unsplit", the same entry point with the cut at M, by the
+rule of ``_fused.TAIL_POLICY``; for comparison only, "tail_small" runs the rows behind the cut through
+``gemm_small(ksplit=1)``, and "main" / "half_main" run the rows ahead of the cut (whole rounds of either tile) on the
+policy tile and on the half tile, which gives the time of a round of half tiles over a round of full ones.  Each
+carries ``same_bits_as_kernel``.
 
 Random data (activations ~ N(0, 1), weights ~ N(0, 0.02^2)): bf16 MFMA loops hold a lower clock on random data than on
 zeros.  The variants are interleaved in one process over several rounds; per shape the median and min time per call, the
@@ -77,6 +84,8 @@ def main():
     args = ap.parse_args()
     tuned = tuned_gemms.enable()
     dev = torch.device("cuda")
+    # CUs the tail cut is planned for: the device's, or the pinned count the dispatch would use
+    cus = int(os.environ.get("VQA_GEMM_TAIL_CUS") or torch.cuda.get_device_properties(dev).multi_processor_count)
     gen = torch.Generator(device=dev).manual_seed(0)
     results = []
     ksplits = [int(v) for v in args.ksplit.split(",") if v]
@@ -110,6 +119,24 @@ def main():
         for k in small:
             variants.append(("small%d" % k, lambda k=k: ops.gemm_small(a, packed, bias, out=out_s, ksplit=k)))
         epi_tile = _fused.gemm_tile(M, N, K)
+        # the 128 x 128 tile: alone ("half"), and behind the last full round of the policy tile's launch where
+        # ops.gemm_tail_plan cuts the shape on this device ("tail", against "unsplit" = the same tile uncut).  For
+        # comparison only: the same rows behind the cut on the 64 x 128 kernel ("tail_small"), and the rows ahead of the
+        # cut -- whole rounds on either tile -- alone on the policy tile ("main") and on the half tile ("half_main").
+        out_h = torch.empty(M, N, device=dev)
+        variants.append(("half", lambda: ops.gemm_half(a, packed, bias, out=out_h)))
+        cut = ops.gemm_tail_plan(M, N, epi_tile, cus)
+        out_t = torch.empty(M, N, device=dev)
+        if cut < M:
+            def tail_small():
+                ops.gemm(a[:cut], packed, bias, out=out_t[:cut], tile=epi_tile, m_split=cut)
+                ops.gemm_small(a[cut:], packed, bias, out=out_t[cut:], ksplit=1)
+
+            variants += [("unsplit", lambda: ops.gemm(a, packed, bias, out=out_t, tile=epi_tile, m_split=M)),
+                         ("tail", lambda: ops.gemm(a, packed, bias, out=out_t, tile=epi_tile, m_split=cut)),
+                         ("tail_small", tail_small),
+                         ("main", lambda: ops.gemm(a[:cut], packed, bias, out=out_t[:cut], tile=epi_tile, m_split=cut)),
+                         ("half_main", lambda: ops.gemm_half(a[:cut], packed, bias, out=out_t[:cut]))]
         if N == MODELS[args.model][1]:
             h_e, act_e, dh_e = (torch.empty(M, N, device=dev) for _ in range(3))
             h_p, act_p, dh_p = (torch.empty(M, N, device=dev) for _ in range(3))
@@ -176,11 +203,40 @@ def main():
                         err_rms=ew[1], same_bits_as_kernel=bool(torch.equal(out_w, out_k)),
                         speedup_vs_kernel_median=statistics.median(times["kernel"]) / statistics.median(tw),
                         bf16_mfma_tflops=12.0 * M * N * K / statistics.median(tw) / 1e9)
+
+        def med(key):
+            return statistics.median(times[key])
+
+        def stats(key):
+            ts = times[key]
+            return dict(ms_median=statistics.median(ts), ms_min=min(ts), ms_spread=max(ts) - min(ts))
+
+        ops.gemm_half(a, packed, bias, out=out_h)
+        torch.cuda.synchronize()
+        half = dict(stats("half"), same_bits_as_kernel=bool(torch.equal(out_h, out_k)), workgroups=-(-M // 128) * (N // 128),
+                    speedup_vs_kernel_median=med("kernel") / med("half"))
+        tail = None
+        if "tail" in times:
+            tail = dict(tile=epi_tile, cus=cus, m_split=cut, tail_workgroups=-(-(M - cut) // 128) * (N // 128),
+                        policy_cuts=_fused.gemm_tail_split(M, N, K, epi_tile, dev) < M)
+            for key in ("unsplit", "tail", "tail_small", "main", "half_main"):
+                out_t.fill_(7.0)
+                dict(variants)[key]()
+                torch.cuda.synchronize()
+                rows = cut if key in ("main", "half_main") else M
+                tail[key] = dict(stats(key), same_bits_as_kernel=bool(torch.equal(out_t[:rows], out_k[:rows])))
+            for key in ("tail", "tail_small"):
+                t, u = tail[key], tail["unsplit"]
+                t["speedup_vs_unsplit_median"] = u["ms_median"] / t["ms_median"]
+                # the policy's rule: the medians' difference against the larger round-to-round spread of the two
+                t["margin_ms"] = u["ms_median"] - t["ms_median"]
+                t["larger_spread_ms"] = max(t["ms_spread"], u["ms_spread"])
+                t["passes_rule"] = t["margin_ms"] > t["larger_spread_ms"]
+            # rows [0, cut) are whole rounds of the policy tile and twice as many of the half tile: the time of a round
+            # of half tiles over the time of a round of full ones (0.5 = a half tile costs half a full one)
+            tail["half_round_over_full_round"] = tail["half_main"]["ms_median"] / (2.0 * tail["main"]["ms_median"])
         epilogue = None
         if "fused_gelu" in times:
-            def stats(key):
-                ts = times[key]
-                return dict(ms_median=statistics.median(ts), ms_min=min(ts), ms_spread=max(ts) - min(ts))
             pair_gelu()
             pair_gelu_grad()
             ops.gemm(a, packed, bias, out=act_e, tile=epi_tile, epilogue="gelu", aux=h_e)
@@ -211,11 +267,11 @@ def main():
                    kernel_ms_spread=max(times["kernel"]) - min(times["kernel"]),
                    library_ms_spread=max(times["library"]) - min(times["library"]),
                    big_workgroups=ops.gemm_workgroups(M, N), small_tiles=ops.gemm_small_workgroups(M, N), small=small_rows,
-                   wide=wide, policy_tile=_fused.gemm_tile(M, N, K), epilogue=epilogue,
+                   wide=wide, policy_tile=_fused.gemm_tile(M, N, K), half=half, tail=tail, epilogue=epilogue,
                    kernel_err_max=ek[0], kernel_err_rms=ek[1], library_err_max=el[0], library_err_rms=el[1])
         print(json.dumps(row), flush=True)
         results.append(row)
-        del a, w, packed, out_k, out_l, out_s, out_w
+        del a, w, packed, out_k, out_l, out_s, out_w, out_h, out_t
         torch.cuda.empty_cache()
     summary = dict(model=args.model, batch=args.batch or MODELS[args.model][4], tuned_gemms=tuned, device=torch.cuda.get_device_name(),
                    rounds=args.rounds, reps=args.reps, warmup=args.warmup, graph=args.graph, shapes=results)
@@ -234,6 +290,23 @@ def main():
                   "bits {}".format("*" if r["policy_tile"] == "wide" else " ", wd["speedup_vs_kernel_median"],
                                    wd["ms_median"], wd["ms_spread"], r["kernel_ms_median"], r["kernel_ms_spread"],
                                    wd["bf16_mfma_tflops"], "equal" if wd["same_bits_as_kernel"] else "DIFFER"))
+        hf = r["half"]
+        print("  half tile    {:>8.3f}x kernel   {:.4f} ms (spread {:.4f})  {} workgroups  bits {}".format(
+            hf["speedup_vs_kernel_median"], hf["ms_median"], hf["ms_spread"], hf["workgroups"],
+            "equal" if hf["same_bits_as_kernel"] else "DIFFER"))
+        if r["tail"]:
+            tl = r["tail"]
+            for key in ("tail", "tail_small"):
+                t, u = tl[key], tl["unsplit"]
+                print("  {:<11}{} {:>8.3f}x unsplit  {:.4f} ms (spread {:.4f}; unsplit {:.4f} spread {:.4f})  margin {:+.4f} {}  "
+                      "tile {} cut {} + {} half tiles on {} CUs  bits {}".format(
+                          key, "*" if key == "tail" and tl["policy_cuts"] else " ", t["speedup_vs_unsplit_median"],
+                          t["ms_median"], t["ms_spread"], u["ms_median"], u["ms_spread"], t["margin_ms"],
+                          "passes" if t["passes_rule"] else "fails", tl["tile"], tl["m_split"], tl["tail_workgroups"],
+                          tl["cus"], "equal" if t["same_bits_as_kernel"] and u["same_bits_as_kernel"] else "DIFFER"))
+            print("  rows ahead of the cut: {} tile {:.4f} ms, half tile {:.4f} ms: a round of half tiles takes {:.3f} of a "
+                  "round of full ones".format(tl["tile"], tl["main"]["ms_median"], tl["half_main"]["ms_median"],
+                                              tl["half_round_over_full_round"]))
         if r["epilogue"]:
             ep = r["epilogue"]
             for fused, pair, epi in EPILOGUE_AB:

@@ -40,6 +40,11 @@
 // and aux on 16-byte boundaries and ldc, ldaux % 4 == 0 (GemmArgs::vec, worked out by the wrappers); the entry points
 // still take 4-byte-aligned pointers and any stride >= N, which run the same lane map with dword accesses.
 //
+// Rounds: at 144 KiB of LDS the large tiles run one workgroup per CU, so a launch takes ceil(tiles / CUs) rounds of equal
+// length and a last round that is a quarter full costs a whole one.  gemm_bf16x6_half_kernel (128 x 128, 96 KiB, the
+// same loop with half the MFMAs per k-step, the same bits) takes the rows behind the last full round where they fit
+// one round of half tiles: vqa_gemm_bf16x6_tail launches the two back to back, cut at the row ops.gemm_tail_plan names.
+//
 // Deterministic: fixed summation order (per k-step the products a2b0, a1b1, a0b2, a1b0, a0b1, a0b0 in turn, k-steps in
 // order), no split-K, no atomics.  Rows >= M are read clamped to row M-1 and never stored.
 #include "common.hpp"
@@ -971,6 +976,166 @@ __global__ __launch_bounds__(kSmallThreads) void gemm_bf16x6_small_kernel(GemmAr
   }
 }
 
+// ---- half tile: 128 x 128 outputs per workgroup, for the rows behind the last full round of a large-tile launch ------
+// The 256 x 128 and 128 x 256 tiles run one workgroup per CU, so a launch proceeds in rounds of one tile per CU and its
+// last round is as long as the others however few tiles it holds.  vqa_gemm_bf16x6_tail runs the rows of that round on
+// this tile instead: twice as many workgroups of half the length, where they still fit one round.  Built like the two
+// large tiles -- BK = 32, packed B straight into LDS (3 x 16 B per thread and k-step), A split on the fly (one
+// (row, 8-k) piece per thread, as in the wide kernel), MFMA operands swapped so a lane holds four consecutive columns --
+// with 8 waves as 4 along M x 2 along N, 32 x 64 outputs each = 2 x 4 MFMA tiles.  LDS per k-step: A 8 m-tiles x 3
+// planes + B 8 n-tiles x 3 planes = 48 KiB, double-buffered = 96 KiB (one workgroup per CU).  Per k-step a wave issues
+// 18 fragment reads and 48 MFMAs; the five global loads of the next step go out in the first half of them (the A pair
+// ahead of the first MFMA, B pieces 0 and 1 behind the 6th, piece 2 behind the 12th).  Same split, packed B, product
+// and k-step order: every output has the bits of the other kernels.  No split-K and no fused epilogue.  Its own copy
+// of the loop, like the _epi kernels: the large tiles' code objects do not change.
+constexpr int kHalfBM = 128;                                           // x kGemmBN = 128 columns
+constexpr int kHalfMT = kHalfBM / 16;                                  // 8 m-tiles (and kGemmNT = 8 n-tiles) per workgroup
+constexpr int kHalfABytes = kHalfMT * 3 * kTileBytes;                  // 24 KiB
+constexpr int kHalfStage = kHalfABytes + kGemmBBytes;                  // 48 KiB
+constexpr int kHalfLoadPair = 6;                                       // MFMAs behind each pair of global loads of the next step
+
+// gemm_store_rows for a wave's 32 x 64 block: register r of tile (i, j), i < 2, is row i * 16 + (lane & 15), column
+// j * 16 + (lane >> 4) * 4 + r.  The bias is added to all 8 tiles ahead of the first store, as there.
+template <bool VEC, bool FULL>
+__device__ __forceinline__ void gemm_store_rows_half(const f32x4 (&acc)[2][4], const GemmArgs& g, long row0, int col0, int lane) {
+  const int colq = col0 + (lane >> 4) * 4;
+  f32x4 v[2][4];
+  if (g.bias) {
+    f32x4 bv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bv[j] = load4<VEC>(g.bias + colq + j * 16);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[i][j] = acc[i][j] + bv[j];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[i][j] = acc[i][j];
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const long row = row0 + i * 16 + (lane & 15);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (FULL || row < g.M) store4<VEC>(g.C + row * g.ldc + colq + j * 16, v[i][j]);
+  }
+}
+
+__global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_half_kernel(GemmArgs g) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * kHalfStage];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);   // the same value, known to be uniform
+  const int wm = wave >> 1, wn = wave & 1;                 // this wave's 32 x 64 output block
+  const int ntb = g.N / kGemmBN;
+  const int mtb = static_cast<int>((g.M + kHalfBM - 1) / kHalfBM);
+  // XCD remap as above
+  const int nwg = mtb * ntb, orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, rem = nwg & 7;
+  const int wg = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (orig >> 3);
+  const int mb = wg / ntb, nb = wg - mb * ntb;
+  const long m0 = static_cast<long>(mb) * kHalfBM;
+  const int n0 = nb * kGemmBN;
+  const int nk = g.K / kGemmBK;
+  const int nt16 = g.N / 16;
+
+  // staging: this thread splits one (row, 8-k chunk) piece of A per k-step -- m-tile wave, row lane & 15, chunk
+  // lane >> 4 -- and stages 3 x 16 B of packed B
+  long r = m0 + wave * 16 + (lane & 15);
+  r = r < g.M ? r : g.M - 1;
+  const float* arow = g.A + r * g.lda + 8 * (lane >> 4);
+  const bf16x8* bsrc = g.B + static_cast<size_t>(nb) * kGemmNT * 3 * 64;
+  const size_t bstep = static_cast<size_t>(nt16) * 3 * 64;            // bf16x8 per k-step of packed B
+
+  f32x4 ra[2];
+  auto load = [&](int kt) {
+    ra[0] = *reinterpret_cast<const f32x4*>(arow + kt * kGemmBK);
+    ra[1] = *reinterpret_cast<const f32x4*>(arow + kt * kGemmBK + 4);
+  };
+  // piece p of step kt's packed B into stage s, with no register in between: the wave's KiB lands at the base given
+  // here + lane * 16 = byte (p * kGemmThreads + tid) * 16 of the stage's image of B
+  char* const bwave = smem + kHalfABytes + wave_u * kTileBytes;
+  auto load_b = [&](int kt, int s, int p) {
+    stage_b16(bsrc + kt * bstep + p * kGemmThreads + tid, bwave + s * kHalfStage + p * kGemmThreads * 16);
+  };
+  auto store = [&](int s) {
+    char* base = smem + s * kHalfStage;
+    bf16x8 p0, p1, p2;
+    split8(ra[0], ra[1], p0, p1, p2);
+    bf16x8* dst = reinterpret_cast<bf16x8*>(base) + wave * 3 * 64 + lane;
+    dst[0] = p0;
+    dst[64] = p1;
+    dst[128] = p2;
+  };
+
+  f32x4 acc[2][4];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+  load(0);
+#pragma unroll
+  for (int p = 0; p < kGemmBPieces; ++p) load_b(0, 0, p);
+  store(0);
+  stage_b_wait();
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const int cur = kt & 1;
+    const int nxt = kt + 1 < nk ? kt + 1 : kt;   // the last step reloads its own tile into the idle buffer: no branch
+    load(nxt);
+    const bf16x8* sa = reinterpret_cast<const bf16x8*>(smem + cur * kHalfStage) + wm * 2 * 3 * 64 + lane;
+    const bf16x8* sb = reinterpret_cast<const bf16x8*>(smem + cur * kHalfStage + kHalfABytes) + wn * 4 * 3 * 64 + lane;
+    bf16x8 fa[3][2], fb[3][4];
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) fa[p][i] = sa[(i * 3 + p) * 64];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) fb[p][j] = sb[(j * 3 + p) * 64];
+    }
+    constexpr int kPa[6] = {2, 1, 0, 1, 0, 0}, kPb[6] = {0, 1, 2, 0, 1, 0};   // the order of gemm_bf16x6_kernel
+#pragma unroll
+    for (int t = 0; t < 6; ++t) {
+      if (t == 3) store(cur ^ 1);
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[kPb[t]][j], fa[kPa[t]][i], acc[i][j], 0, 0, 0);   // transposed
+          // B pieces 0, 1 behind the 6th MFMA and piece 2 behind the 12th.  Stage cur ^ 1 was last read in the step
+          // that the barrier above this one ended
+          if (t * 8 + i * 4 + j + 1 == kHalfLoadPair) {
+            load_b(nxt, cur ^ 1, 0);
+            load_b(nxt, cur ^ 1, 1);
+          }
+          if (t * 8 + i * 4 + j + 1 == 2 * kHalfLoadPair) load_b(nxt, cur ^ 1, 2);
+        }
+    }
+    // placement of the 5 global loads, as in the large tiles: the A pair ahead of the first MFMA (group barriers:
+    // hints), B where the source has it; tests/test_gemm_tail.py checks where they land
+#pragma unroll
+    for (int n = 0; n < (2 + kGemmBPieces + 1) / 2; ++n) {
+      __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);                  // two vector-memory reads
+      __builtin_amdgcn_sched_group_barrier(0x008, kHalfLoadPair, 0);      // kHalfLoadPair MFMAs
+    }
+    stage_b_wait();
+    __syncthreads();
+  }
+
+  // epilogue: accumulator register r of tile (i, j) is row lane & 15, column (lane >> 4) * 4 + r (operands swapped).
+  // The vector form unguarded where all 32 rows of the wave's block are below M (row0 is the wave's: uniform)
+  const long row0 = m0 + wm * 32;
+  const int col0 = n0 + wn * 64;
+  if (!g.vec) {
+    gemm_store_rows_half<false, false>(acc, g, row0, col0, lane);
+  } else if (__builtin_amdgcn_readfirstlane(row0 + 32 <= g.M)) {
+    gemm_store_rows_half<true, true>(acc, g, row0, col0, lane);
+  } else {
+    gemm_store_rows_half<true, false>(acc, g, row0, col0, lane);
+  }
+}
+
 // C = ((P0 + P1) + ... + P(ksplit-1)) + bias over the [ksplit][M][N] partials, one thread per 4 columns of a row.
 __global__ __launch_bounds__(kBlock) void gemm_splitk_combine_kernel(const f32x4* __restrict__ ws,
                                                                      const float* __restrict__ bias, float* __restrict__ C,
@@ -1113,6 +1278,38 @@ int vqa_gemm_bf16x6_tile(const float* A, long lda, const void* packed, const flo
   const int grid = static_cast<int>((M + kWideBM - 1) / kWideBM * (N / kWideBN));
   gemm_bf16x6_wide_kernel<<<grid, kGemmThreads, 0, static_cast<hipStream_t>(stream)>>>(g);
   return launch_status();
+}
+
+int vqa_gemm_bf16x6_half(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M,
+                         int N, int K, vqa_stream_t stream) {
+  clear_stale_error();
+  if (!A || !packed || !C) return VQA_ERR_NULL;
+  if (M < 0 || N <= 0 || K <= 0 || K % kGemmBK || N % kGemmBN || lda < K || lda % 4 || ldc < N) return VQA_ERR_SHAPE;
+  if ((M + kHalfBM - 1) / kHalfBM * (N / kGemmBN) > 0x7fffffffL) return VQA_ERR_SHAPE;
+  if (!aligned16(A) || !aligned16(packed) || !aligned4(C) || (bias && !aligned4(bias))) return VQA_ERR_ALIGN;
+  if (M == 0) return VQA_OK;
+  GemmArgs g{A, static_cast<const bf16x8*>(packed), bias, C, lda, ldc, M, N, K, gemm_vec_ok(C, ldc, bias)};
+  const int grid = static_cast<int>((M + kHalfBM - 1) / kHalfBM * (N / kGemmBN));
+  gemm_bf16x6_half_kernel<<<grid, kGemmThreads, 0, static_cast<hipStream_t>(stream)>>>(g);
+  return launch_status();
+}
+
+int vqa_gemm_bf16x6_tail(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M,
+                         int N, int K, int tile, long m_split, vqa_stream_t stream) {
+  clear_stale_error();
+  if (tile != VQA_GEMM_TILE_256X128 && tile != VQA_GEMM_TILE_128X256) return VQA_ERR_SHAPE;
+  if (!A || !packed || !C) return VQA_ERR_NULL;
+  if (M < 0 || m_split < 0 || m_split > M) return VQA_ERR_SHAPE;
+  if (m_split == M) return vqa_gemm_bf16x6_tile(A, lda, packed, bias, C, ldc, M, N, K, tile, stream);
+  if (m_split == 0) return vqa_gemm_bf16x6_half(A, lda, packed, bias, C, ldc, M, N, K, stream);
+  // the whole shape is checked ahead of the first launch: a refused call leaves C untouched.  Rows [m_split, M) are a
+  // GEMM of their own on A + m_split * lda and C + m_split * ldc (lda % 4 == 0 keeps A on its 16-byte boundary; C's
+  // alignment, and with it the vector epilogue, is worked out per part)
+  if (N <= 0 || K <= 0 || K % kGemmBK || N % kGemmBN || lda < K || lda % 4 || ldc < N) return VQA_ERR_SHAPE;
+  if (!aligned16(A) || !aligned16(packed) || !aligned4(C) || (bias && !aligned4(bias))) return VQA_ERR_ALIGN;
+  const int rc = vqa_gemm_bf16x6_tile(A, lda, packed, bias, C, ldc, m_split, N, K, tile, stream);
+  if (rc != VQA_OK) return rc;
+  return vqa_gemm_bf16x6_half(A + m_split * lda, lda, packed, bias, C + m_split * ldc, ldc, M - m_split, N, K, stream);
 }
 
 int vqa_gemm_bf16x6_epi(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M,

@@ -785,11 +785,34 @@ GEMM_TILES = {"large": 0, "wide": 1}      # VQA_GEMM_TILE_256X128, VQA_GEMM_TILE
 GEMM_EPILOGUES = {"gelu": 1, "gelu_grad": 2}   # VQA_GEMM_EPI_GELU, VQA_GEMM_EPI_GELU_GRAD of include/vqattack_hip.h
 
 
-def gemm(a, packed, bias=None, out=None, tile=None, epilogue=None, aux=None):
+def gemm_tail_plan(M, N, tile, cus):
+    """Where ``vqa_gemm_bf16x6_tail`` should cut (M, N) on ``tile`` for a device of ``cus`` compute units: the row count
+    ``m_split`` of the launch's full rounds (one ``tile`` workgroup per CU at a time), the rows behind it going to the
+    128 x 128 tile -- or M (no cut) where the grid is below one round or a whole number of rounds, or where those rows
+    need more 128 x 128 workgroups than one round holds.  Pure arithmetic, no device."""
+    if tile not in GEMM_TILES:
+        raise ValueError("tile must be one of {}, got {!r}".format(sorted(GEMM_TILES), tile))
+    M, N, cus = int(M), int(N), int(cus)
+    bm, bn = (128, 256) if tile == "wide" and N % 256 == 0 else (256, 128)     # "wide" at another N runs "large"
+    ntb = N // bn
+    nwg = -(-M // bm) * ntb
+    full = (nwg // cus) * cus if cus > 0 else 0
+    if full == 0 or nwg == full:
+        return M
+    m_split = (full // ntb) * bm
+    tail = -(-(M - m_split) // 128) * (N // 128)
+    return m_split if tail <= cus else M
+
+
+def gemm(a, packed, bias=None, out=None, tile=None, epilogue=None, aux=None, m_split=None):
     """``out = a @ B (+ bias)`` on the bf16 matrix pipe (bf16x6, fp32-grade), B a ``PackedWeight``.  ``a``: fp32 (M, K)
     with unit column stride and a row stride that is a multiple of 4 floats.  ``tile``: the output tile of a workgroup,
     "large" (256 x 128) or "wide" (128 x 256: half the in-loop split work; N % 256 == 0, any other N runs "large");
     both give the same bits.  None = what ``whitebox/_fused.py`` records for the shape (``gemm_tile``).
+
+    ``m_split``: None, or the row from which the 128 x 128 tile takes over (``vqa_gemm_bf16x6_tail``: rows
+    ``[0, m_split)`` on ``tile``, the rest on the half tile, the same bits); 0 <= m_split <= M, no epilogue.  None leaves
+    the cut to ``whitebox/_fused.py`` (``gemm_tail_split``: nowhere unless the shape is listed or VQA_GEMM_TAIL=1).
 
     ``epilogue``: None, or the FFN's activation applied to the accumulators inside the GEMM (``vqa_gemm_bf16x6_epi``),
     with the bits of the two-step form.  "gelu": ``out = gelu(h)`` with ``h = a @ B (+ bias)``; ``aux``, if given, is
@@ -817,12 +840,34 @@ def gemm(a, packed, bias=None, out=None, tile=None, epilogue=None, aux=None):
         tile = _fused.gemm_tile(a.shape[0], packed.N, packed.K)
     if tile not in GEMM_TILES:
         raise ValueError("tile must be one of {}, got {!r}".format(sorted(GEMM_TILES), tile))
+    if m_split is not None:
+        if epilogue is not None:
+            raise ValueError("m_split does not go with an epilogue")
+        if isinstance(m_split, bool) or not isinstance(m_split, int) or not 0 <= m_split <= a.shape[0]:
+            raise ValueError("m_split must be an integer in [0, {}], got {!r}".format(a.shape[0], m_split))
+        return _gemm_rows(a, packed, bias, out, tile, m_split)
     if epilogue is not None:
         return _gemm_epilogue(a, packed, bias, out, tile, epilogue, aux)
     return _gemm_tiled(a, packed, bias, out, tile)
 
 
+def gemm_half(a, packed, bias=None, out=None):
+    """``gemm`` with the whole product on the 128 x 128 tile (``vqa_gemm_bf16x6_half``): the same bits."""
+    return _gemm_rows(a, packed, bias, out, None, 0)
+
+
 def _gemm_tiled(a, packed, bias, out, tile):
+    """``tile`` from row 0 to the cut ``whitebox/_fused.py`` names for the shape -- M, the whole product on
+    ``vqa_gemm_bf16x6_tile``, unless the shape is listed there or VQA_GEMM_TAIL=1 -- and the 128 x 128 tile behind it."""
+    return _gemm_rows(a, packed, bias, out, tile, None)
+
+
+TAIL_CALLS = [0]     # calls of vqa_gemm_bf16x6_tail with a cut inside the matrix (tests and tools read it)
+
+
+def _gemm_rows(a, packed, bias, out, tile, m_split):
+    """Rows ``[0, m_split)`` on ``tile``, the rest on the 128 x 128 tile; ``m_split=None``: the cut of
+    ``_fused.gemm_tail_split``; ``tile=None``: every row on the 128 x 128 tile."""
     dev_f32(a, "a", contiguous=False)
     if a.dim() != 2 or a.shape[1] != packed.K or a.stride(1) != 1 or a.stride(0) % 4:
         raise ValueError("a must be (M, {}) with unit column stride and a row stride % 4 == 0, got shape {} strides {}"
@@ -837,9 +882,22 @@ def _gemm_tiled(a, packed, bias, out, tile):
         dev_f32(bias, "bias"), _rows_ok("bias", bias, packed.N)
     same_device(a, packed.data, bias, out)
     if M:
+        planned = tile is not None and m_split is None          # an m_split of the caller's goes to the tail entry as it is
+        if planned:
+            from .whitebox import _fused
+            m_split = _fused.gemm_tail_split(M, packed.N, packed.K, tile, a.device)
         with _on(a):
-            check(lib().vqa_gemm_bf16x6_tile(_p(a), a.stride(0), _p(packed.data), ptr(bias), _p(out), packed.N, M, packed.N,
-                                             packed.K, GEMM_TILES[tile], stream_for(a)), "vqa_gemm_bf16x6_tile")
+            if tile is None:
+                check(lib().vqa_gemm_bf16x6_half(_p(a), a.stride(0), _p(packed.data), ptr(bias), _p(out), packed.N, M,
+                                                 packed.N, packed.K, stream_for(a)), "vqa_gemm_bf16x6_half")
+            elif planned and m_split >= M:
+                check(lib().vqa_gemm_bf16x6_tile(_p(a), a.stride(0), _p(packed.data), ptr(bias), _p(out), packed.N, M,
+                                                 packed.N, packed.K, GEMM_TILES[tile], stream_for(a)), "vqa_gemm_bf16x6_tile")
+            else:
+                TAIL_CALLS[0] += 1
+                check(lib().vqa_gemm_bf16x6_tail(_p(a), a.stride(0), _p(packed.data), ptr(bias), _p(out), packed.N, M,
+                                                 packed.N, packed.K, GEMM_TILES[tile], m_split, stream_for(a)),
+                      "vqa_gemm_bf16x6_tail")
     return out
 
 

@@ -79,6 +79,29 @@ WIDE_POLICY = {(768, 768): _WIDE_ROWS, (3072, 768): _WIDE_ROWS, (768, 3072): _WI
 # 2560 rows (1.25-1.29x) and at ALBEF-base's 147712 rows (1.21-1.22x).
 EPILOGUE_POLICY = {"gelu": {}, "gelu_grad": {(3072, 768): _WIDE_ROWS}}
 
+# The two large tiles run one workgroup per CU, so a launch proceeds in rounds of one tile per CU, and its last round,
+# however few tiles it holds, costs most of a full one: the N = 768 GEMMs at 35264-37824 rows are 828-888 tiles =
+# 3.23-3.47 rounds on 256 CUs.
+# ops.gemm_tail_plan cuts such a launch behind its last full round and vqa_gemm_bf16x6_tail runs the rows behind the cut
+# on a 128 x 128 tile (twice as many workgroups of half the length, the same bits).  A shape class (N, K) -> (fewest
+# rows, most rows), both inclusive, is listed only by the rule of WIDE_POLICY: the split call's median in
+# tools/gemm_bench.py beat the unsplit call's by more than the larger round-to-round spread of the two in BOTH records of
+# the shape, and the benchmark with the entries in place beat the one without (profiles/r15/README.md).  A listed class
+# must be one the plan cuts at 256 CUs.  VQA_GEMM_TAIL=1 cuts every shape the plan cuts, =0 none; VQA_GEMM_TAIL_CUS=n
+# pins the CU count the plan is made for (experiments and tests).  Plain ops.gemm calls only: the GELU and LSE epilogues
+# have no half tile.
+# Recorded (profiles/r15/README.md, VLMO-base, batch 64, 256 CUs, two records): a last round that is 23-47 % full costs
+# 0.56-0.78 of a full one and a round of half tiles 0.59-0.66 of a round of full ones, so the cut gains 1.03-1.04x per call
+# on (768, 768) at 37824 rows and on (768, 3072) at 35264 rows (passing in both records), 1.01x at 37824 rows of
+# (768, 3072) (fails three of four), fails one record of (768, 2304) and loses on (2304, 768).  With the two passing
+# classes listed the benchmark read 16.43-16.44 examples/s against the previous commit's 16.41-16.46 in three alternating
+# rounds: no difference ((768, 3072) at 35264 rows is a row count of tools/gemm_bench.py that the benchmark's image expert,
+# at 64 x 577 rows, never runs, and the projections alone are 0.2 % of a step).  So nothing is listed and the unset
+# switch runs what the previous commit ran.  VQA_GEMM_TAIL=1 read 1.008x of VQA_GEMM_TAIL=0 in one tree (two rounds).
+TAIL_POLICY = {}
+
+_CUS = {}
+
 
 def _mode():
     """VQA_GEMM: "library" = the library everywhere, "large" = the 256 x 128 kernel from MIN_WORKGROUPS up and the library
@@ -99,6 +122,27 @@ def gemm_tile(rows, n, k):
 
 def _kernel_gemms():
     return _mode() != "library"
+
+
+def gemm_tail_split(rows, n, k, tile, device):
+    """The row from which ops._gemm_tiled hands (rows, n, k) on ``tile`` to the 128 x 128 tile; ``rows`` = nowhere.  The
+    device is asked for its CU count (once) only where a cut is wanted at all and VQA_GEMM_TAIL_CUS does not pin it."""
+    switch = os.environ.get("VQA_GEMM_TAIL", "")
+    if switch == "0":
+        return rows
+    if switch != "1":
+        lo, hi = TAIL_POLICY.get((n, k), (1, 0))
+        if switch != "" or not lo <= rows <= hi:
+            return rows
+    pinned = os.environ.get("VQA_GEMM_TAIL_CUS")
+    if pinned:
+        cus = int(pinned)
+    else:
+        dev = torch.device(device).index or 0
+        if dev not in _CUS:
+            _CUS[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
+        cus = _CUS[dev]
+    return ops.gemm_tail_plan(rows, n, tile, cus)
 
 
 def _small_gemm(rows, n, k):
