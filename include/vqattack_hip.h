@@ -463,6 +463,29 @@ int vqa_gemm_bf16x6_small(const float* A, long lda, const void* packed, const fl
 int vqa_gemm_bf16x6_epi(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M,
                         int N, int K, int tile, int epilogue, float* aux, long ldaux, vqa_stream_t stream);
 
+/* vqa_gemm_bf16x6_grouped: up to VQA_GEMM_MAX_GROUPS products with one (N, K) -- group i is
+ *   C[i] = epilogue(A[i] . packed[i] (+ bias[i])) on M[i] rows -- as ONE launch of 128 x 256 tiles: the expert FFNs of a
+ *   multiway block (text and image rows through different weights, VLMO_VQAttack/vlmo/modules/multiway_transformer.py:
+ *   193-197), where the small expert's tiles ride in the last, partly empty round of the large one's instead of a launch
+ *   that cannot fill the device.  The tile list is group 0's row blocks, then group 1's, ...; a workgroup finds its
+ *   group from its row block.  Prologue, k-loop and epilogues are those of vqa_gemm_bf16x6_epi on
+ *   VQA_GEMM_TILE_128X256: every output of group i has the bits of that call on group i alone.
+ *   A, lda, packed, bias, C, ldc, aux, ldaux, M are HOST arrays of n_groups entries, read during the call and copied into
+ *   the kernel arguments (no device-side table: capture-safe).  `bias` may be NULL (no group has one) and so may any
+ *   bias[i]; `aux` / `ldaux` may be NULL where no group has an aux; with VQA_GEMM_EPI_NONE aux and ldaux are ignored.
+ *   1 <= n_groups <= VQA_GEMM_MAX_GROUPS, N % 256 == 0, K % 32 == 0, every M[i] >= 0, at most 2^31 - 1 tiles in all, an
+ *   epilogue of vqa_gemm_bf16x6_epi: else VQA_ERR_SHAPE.  A group with M[i] == 0 contributes nothing and its other
+ *   entries are not looked at; every group with rows obeys the argument rules of vqa_gemm_bf16x6_epi and gets its return
+ *   codes (aux[i] required for VQA_GEMM_EPI_GELU_GRAD; aux[i] == C[i] or A[i] VQA_ERR_SHAPE; a NULL table VQA_ERR_NULL).
+ *   Every group is checked ahead of the launch: a refused call leaves every C untouched.  All M[i] == 0: VQA_OK, no
+ *   launch.  The 16-byte epilogue runs only where every group with rows qualifies for it, the dword form otherwise (same
+ *   bits).  The output (and aux) ranges of different groups must not overlap each other or any group's A or aux: that
+ *   is the caller's duty, nothing here detects it.  Never allocates, never synchronises. */
+#define VQA_GEMM_MAX_GROUPS 4
+int vqa_gemm_bf16x6_grouped(const float* const* A, const long* lda, const void* const* packed, const float* const* bias,
+                            float* const* C, const long* ldc, float* const* aux, const long* ldaux, const long* M,
+                            int n_groups, int N, int K, int epilogue, vqa_stream_t stream);
+
 /* vqa_gemm_bf16x6_lse: the cross entropy of an LM head without its logits -- row_loss[row] = logsumexp_c(x[row, c]) -
  *   x[row, targets[row]] over c < n_valid, with x = A . B + bias the product vqa_gemm_bf16x6_tile would have stored.
  *   It replaces the vocabulary logits and F.cross_entropy(reduction='none') of the reference's answer ranking

@@ -24,6 +24,14 @@ graphs of ``--reps`` calls, as that path is replayed.
     python tools/gemm_bench.py [--model vlmo_base|albef_base|vlmo_large] [--batch B] [--ksplit 1,2,4,8] [--graph]
                                [--rounds 5] [--reps 10] [--warmup 3] [--only NAMES] [--out FILE]
 (the per-kernel records since round 13 use --warmup 10 --rounds 7 --reps 50).
+
+``--grouped`` times something else: per expert pair of a multiway layer (fc1 / fc2, forward and input gradient) the ONE
+``ops.gemm_grouped`` launch over the image and the text expert's rows ("grouped", with the epilogue the dispatch gives
+it) against the two calls that ``whitebox/_fused.py`` dispatches today ("today": each expert on the bf16x6 tile or the
+library as its row count decides, GELU kernels included wherever either side launches them), by the rule of
+``_fused.GROUPED_POLICY``; "image_only" is today's call on the image rows alone, so grouped - image_only is what the
+text tiles cost in the image expert's last round.  ``--image-rows`` / ``--text-rows`` name the row counts (default: VLMO-base
+at batch 64 with 577 image tokens, and 14 or 40 text tokens per sample).  One JSON line per pair and text row count.
 """
 import argparse
 import json
@@ -68,6 +76,147 @@ def err(c, ref):
     return float(e.max()), float(e.pow(2).mean().sqrt())
 
 
+def grouped_main(args):
+    """``--grouped``: one record per (expert pair, text rows)."""
+    tuned = tuned_gemms.enable()
+    dev = torch.device("cuda")
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    gen = torch.Generator(device=dev).manual_seed(0)
+    d, f = MODELS[args.model][:2]
+    m_img = args.image_rows
+    # (name, N, K, bias, the GELU stage the GEMM feeds: None, "gelu" (forward) or "gelu_grad" (backward))
+    pairs = [("fc1_fwd", f, d, True, "gelu"), ("fc2_fwd", d, f, True, None), ("fc2_bwd", f, d, False, "gelu_grad"),
+             ("fc1_bwd", d, f, False, None)]
+    results = []
+    for m_txt in [int(v) for v in args.text_rows.split(",") if v]:
+        for name, N, K, has_bias, stage in pairs:
+            if args.only and name not in args.only.split(","):
+                continue
+            ex = []
+            for m in (m_img, m_txt):                                    # the larger group first, as the dispatch orders them
+                a = torch.randn(m, K, device=dev, generator=gen)
+                w = torch.randn(N, K, device=dev, generator=gen) * 0.02
+                bias = torch.randn(N, device=dev, generator=gen) * 0.02 if has_bias else None
+                ex.append(dict(m=m, a=a, bt=w.t(), bias=bias, packed=ops.gemm_pack(w, trans=True),
+                               h=torch.randn(m, N, device=dev, generator=gen),          # the backward's pre-activation
+                               out=[torch.empty(m, N, device=dev) for _ in range(2)],     # [today, grouped]
+                               act=[torch.empty(m, N, device=dev) for _ in range(2)],
+                               kernel=_fused._kernel_gemms() and ops.gemm_workgroups(m, N) >= _fused.MIN_WORKGROUPS))
+            for e in ex:
+                e["fuse"] = bool(stage) and e["kernel"] and _fused.gelu_epilogue(e["m"], N, K, stage)
+            fuse_grouped = ex[0]["fuse"]                                    # the larger group's decision serves the launch
+
+            def gelu_kernels(e, slot):
+                if stage == "gelu":
+                    ops.gelu_fwd(e["out"][slot], out=e["act"][slot])
+                elif stage == "gelu_grad":
+                    ops.gelu_bwd(e["h"], e["out"][slot])
+
+            def one(e):
+                """What _linear / _linear_gelu / _linear_grad_gelu launch for this expert today."""
+                if e["fuse"]:
+                    if stage == "gelu":
+                        ops.gemm(e["a"], e["packed"], e["bias"], out=e["act"][0], epilogue="gelu", aux=e["out"][0])
+                    else:
+                        ops.gemm(e["a"], e["packed"], e["bias"], out=e["out"][0], epilogue="gelu_grad", aux=e["h"])
+                    return
+                if e["kernel"]:
+                    ops.gemm(e["a"], e["packed"], e["bias"], out=e["out"][0])
+                elif e["bias"] is not None:
+                    torch.addmm(e["bias"], e["a"], e["bt"], out=e["out"][0])
+                else:
+                    torch.mm(e["a"], e["bt"], out=e["out"][0])
+                gelu_kernels(e, 0)
+
+            def today():
+                one(ex[1]), one(ex[0])                                      # text first, as the layer loop runs them
+
+            def grouped():
+                lists = ([e["a"] for e in ex], [e["packed"] for e in ex], [e["bias"] for e in ex])
+                if fuse_grouped and stage == "gelu":
+                    ops.gemm_grouped(*lists, out_list=[e["act"][1] for e in ex], epilogue="gelu",
+                                     aux_list=[e["out"][1] for e in ex])
+                elif fuse_grouped:
+                    ops.gemm_grouped(*lists, out_list=[e["out"][1] for e in ex], epilogue="gelu_grad",
+                                     aux_list=[e["h"] for e in ex])
+                else:
+                    ops.gemm_grouped(*lists, out_list=[e["out"][1] for e in ex])
+                    for e in ex:
+                        gelu_kernels(e, 1)
+
+            variants = [("today", today), ("grouped", grouped), ("image_only", lambda: one(ex[0])),
+                        ("text_only", lambda: one(ex[1]))]
+            times = {key: [] for key, _ in variants}
+            for _ in range(args.warmup):
+                for _, fn in variants:
+                    fn()
+            torch.cuda.synchronize()
+            for _ in range(args.rounds):
+                for key, fn in variants:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(args.reps):
+                        fn()
+                    e1.record()
+                    e1.synchronize()
+                    times[key].append(e0.elapsed_time(e1) / args.reps)
+            # bits: the image rows keep today's; the text rows have those of ops.gemm on them (today's where they run
+            # the kernel already).  In-place GELU' outputs are recomputed from scratch on both sides.
+            today(), grouped()
+            torch.cuda.synchronize()
+            final = "act" if stage == "gelu" else "out"
+            img_same = bool(torch.equal(ex[0][final][0], ex[0][final][1]))
+            txt_today_same = bool(torch.equal(ex[1][final][0], ex[1][final][1]))
+            t = ex[1]
+            ref = ops.gemm(t["a"], t["packed"], t["bias"], tile="wide")
+            if stage == "gelu":
+                ref = ops.gelu_fwd(ref)
+            elif stage == "gelu_grad":
+                ref = ops.gelu_bwd(t["h"], ref)
+            txt_same = bool(torch.equal(ref, t[final][1]))
+            txt_diff = float((t[final][0] - t[final][1]).abs().max())
+
+            def stats(key):
+                ts = times[key]
+                return dict(ms_median=statistics.median(ts), ms_min=min(ts), ms_spread=max(ts) - min(ts))
+            starts, grid = ops.gemm_grouped_blocks((m_img, m_txt), N)
+            img_grid = starts[1] * (N // 256)
+            row = dict(pair=name, N=N, K=K, bias=has_bias, image_rows=m_img, text_rows=m_txt, stage=stage,
+                       grouped_epilogue=stage if fuse_grouped else None, image_today_fused=ex[0]["fuse"],
+                       text_today="kernel" if ex[1]["kernel"] else "library", text_today_fused=ex[1]["fuse"],
+                       grid=grid, image_grid=img_grid, cus=cus, rounds_grouped=grid / cus, rounds_image=img_grid / cus,
+                       policy_groups=_fused.gemm_grouped_pair((m_img, m_txt), N, K),
+                       image_same_bits_as_today=img_same, text_same_bits_as_ops_gemm=txt_same,
+                       text_same_bits_as_today=txt_today_same, text_max_abs_diff_to_today=txt_diff,
+                       **{key: stats(key) for key, _ in variants})
+            g, u = row["grouped"], row["today"]
+            g["speedup_vs_today_median"] = u["ms_median"] / g["ms_median"]
+            g["margin_ms"] = u["ms_median"] - g["ms_median"]
+            g["larger_spread_ms"] = max(g["ms_spread"], u["ms_spread"])
+            g["passes_rule"] = g["margin_ms"] > g["larger_spread_ms"]
+            g["text_price_ms"] = g["ms_median"] - row["image_only"]["ms_median"]
+            print(json.dumps(row), flush=True)
+            results.append(row)
+            del ex, ref
+            torch.cuda.empty_cache()
+    summary = dict(model=args.model, grouped=True, tuned_gemms=tuned, device=torch.cuda.get_device_name(), rounds=args.rounds,
+                   reps=args.reps, warmup=args.warmup, pairs=results)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(summary, fh, indent=1)
+    print("pair      text rows  grouped ms (spread)   today ms (spread)   x today  margin   rule   image only  text price  text today")
+    for r in results:
+        g, u = r["grouped"], r["today"]
+        print("{:<10}{:>9}  {:.4f} ({:.4f})     {:.4f} ({:.4f})   {:>7.3f}  {:+.4f}  {}  {:.4f}      {:+.4f}     {:.4f} {}{}  bits img {} txt {}"
+              .format(r["pair"], r["text_rows"], g["ms_median"], g["ms_spread"], u["ms_median"], u["ms_spread"],
+                      g["speedup_vs_today_median"], g["margin_ms"], "passes" if g["passes_rule"] else "fails ",
+                      r["image_only"]["ms_median"], g["text_price_ms"], r["text_only"]["ms_median"], r["text_today"],
+                      " epi " + r["grouped_epilogue"] if r["grouped_epilogue"] else "",
+                      "equal" if r["image_same_bits_as_today"] else "DIFFER",
+                      "equal" if r["text_same_bits_as_ops_gemm"] else "DIFFER"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="vlmo_base", choices=sorted(MODELS))
@@ -81,7 +230,13 @@ def main():
                     help="time each variant as ONE captured graph of --reps calls (device time without the host's launch "
                          "cost: how the batch-1 path runs, which is replayed from a captured graph)")
     ap.add_argument("--out", default="")
+    ap.add_argument("--grouped", action="store_true",
+                    help="time ops.gemm_grouped per expert pair against the two calls dispatched today (see above)")
+    ap.add_argument("--image-rows", type=int, default=64 * 577, help="--grouped: rows of the image expert")
+    ap.add_argument("--text-rows", default="896,2560", help="--grouped: comma-separated row counts of the text expert")
     args = ap.parse_args()
+    if args.grouped:
+        return grouped_main(args)
     tuned = tuned_gemms.enable()
     dev = torch.device("cuda")
     # CUs the tail cut is planned for: the device's, or the pinned count the dispatch would use

@@ -81,6 +81,7 @@ SIGNATURES = {
     "vqa_gemm_small_ws_bytes": (_sz, [_l, _i, _i]),
     "vqa_gemm_bf16x6_small": (_i, [_p, _l, _p, _p, _p, _l, _l, _i, _i, _i, _p, _p]),
     "vqa_gemm_bf16x6_epi": (_i, [_p, _l, _p, _p, _p, _l, _l, _i, _i, _i, _i, _p, _l, _p]),
+    "vqa_gemm_bf16x6_grouped": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "vqa_gemm_lse_ws_floats": (_l, [_l, _i]),
     "vqa_gemm_bf16x6_lse": (_i, [_p, _l, _p, _p, _l, _i, _i, _i, _p, _l, _p, _p, _p, _p, _i, _p]),
 }

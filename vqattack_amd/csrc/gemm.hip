@@ -45,6 +45,10 @@
 // same loop with half the MFMAs per k-step, the same bits) takes the rows behind the last full round where they fit
 // one round of half tiles: vqa_gemm_bf16x6_tail launches the two back to back, cut at the row ops.gemm_tail_plan names.
 //
+// Groups: gemm_bf16x6_grouped_kernel<EPI> runs the 128 x 256 tiles of up to four products with one (N, K) -- the expert
+// FFNs of a multiway block -- as one grid, so a product too small for a launch of its own fills the last round of a
+// large one (vqa_gemm_bf16x6_grouped; the groups travel in the kernel arguments).  The same loop, the same bits per group.
+//
 // Deterministic: fixed summation order (per k-step the products a2b0, a1b1, a0b2, a1b0, a0b1, a0b0 in turn, k-steps in
 // order), no split-K, no atomics.  Rows >= M are read clamped to row M-1 and never stored.
 #include "common.hpp"
@@ -856,6 +860,155 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_wide_epi_kernel(Gemm
   gemm_epilogue<EPI>(acc, g, m0 + wm * 64, n0 + wn * 64, lane);
 }
 
+// ---- grouped launch: the 128 x 256 tiles of up to four (A, packed B, C) problems with one (N, K) in ONE grid ---------
+// A mixture-of-experts FFN runs the same (N, K) product on several row sets with a weight each.  The large tiles run one
+// workgroup per CU, so every launch ends in a round that is partly empty, and a small problem (VLMo's text expert:
+// 7 m-blocks beside the image expert's 289) cannot fill the device by itself at all.  gemm_bf16x6_grouped_kernel<EPI>
+// puts the tiles of all groups into one list -- the m-blocks of group 0, then those of group 1, ..., within an m-block
+// the N / 256 column blocks as in gemm_bf16x6_wide_kernel -- and applies that kernel's XCD remap to the combined list.
+// The groups travel BY VALUE in the kernel arguments (no device-side table, no allocation, no copy: the launch is
+// graph-capturable); a workgroup compares its m-block against the cumulative block counts (blockIdx arithmetic: scalar
+// registers) and takes that group's pointers, strides and M.  A group with M == 0 has no m-block.  From there on it is
+// gemm_bf16x6_wide_epi_kernel up to the epilogue, as a copy (see the note above GemmEpiArgs): rows >= M of the GROUP
+// are read clamped to the group's row M - 1 and never stored; same split, packed B, load placement, product and k-step
+// order, so every output has the bits of the wide kernel run on its group alone.  EPI == 0 ends in gemm_store, the
+// others in gemm_epilogue<EPI>, on a per-group argument block built in registers.  One `vec` serves the launch: set
+// only where every group with rows passes gemm_vec_ok.
+struct GemmGroup {
+  const float* A;
+  const bf16x8* B;     // packed planes
+  const float* bias;   // nullable
+  float* C;
+  float* aux;          // as GemmEpiArgs::aux
+  long lda, ldc, ldaux, M;
+};
+
+struct GemmGroupedArgs {
+  GemmGroup grp[VQA_GEMM_MAX_GROUPS];
+  int start[VQA_GEMM_MAX_GROUPS + 1];   // start[i] = m-blocks of the groups ahead of group i; start[4] = all of them
+  int N, K;
+  int vec;
+};
+
+template <int EPI>
+__global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_grouped_kernel(GemmGroupedArgs ga) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * kWideStage];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);   // the same value, known to be uniform
+  const int wm = wave >> 2, wn = wave & 3;                 // this wave's 64 x 64 output block
+  const int ntb = ga.N / kWideBN;
+  const int mtb = ga.start[VQA_GEMM_MAX_GROUPS];
+  // XCD remap as above, over the combined list
+  const int nwg = mtb * ntb, orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, rem = nwg & 7;
+  const int wg = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (orig >> 3);
+  const int mb_all = wg / ntb, nb = wg - mb_all * ntb;
+  // the group of this m-block: the last one whose first block is not behind it (an empty group shares its successor's
+  // start and is skipped; groups behind the last one with rows start at mtb, which no m-block reaches)
+  const int gi = (mb_all >= ga.start[1]) + (mb_all >= ga.start[2]) + (mb_all >= ga.start[3]);
+  const GemmGroup& grp = ga.grp[gi];
+  GemmEpiArgs g;
+  g.A = grp.A, g.B = grp.B, g.bias = grp.bias, g.C = grp.C;
+  g.lda = grp.lda, g.ldc = grp.ldc, g.M = grp.M;
+  g.N = ga.N, g.K = ga.K, g.vec = ga.vec;
+  g.aux = grp.aux, g.ldaux = grp.ldaux;
+  const int mb = mb_all - ga.start[gi];
+  const long m0 = static_cast<long>(mb) * kWideBM;
+  const int n0 = nb * kWideBN;
+  const int nk = g.K / kGemmBK;
+  const int nt16 = g.N / 16;
+
+  // staging: this thread splits one (row, 8-k chunk) piece of A per k-step -- m-tile wave, row lane & 15, chunk
+  // lane >> 4 -- and stages 6 x 16 B of packed B
+  long r = m0 + wave * 16 + (lane & 15);
+  r = r < g.M ? r : g.M - 1;
+  const float* arow = g.A + r * g.lda + 8 * (lane >> 4);
+  const bf16x8* bsrc = g.B + static_cast<size_t>(nb) * kWideNT * 3 * 64;
+  const size_t bstep = static_cast<size_t>(nt16) * 3 * 64;            // bf16x8 per k-step of packed B
+
+  f32x4 ra[2];
+  auto load = [&](int kt) {
+    ra[0] = *reinterpret_cast<const f32x4*>(arow + kt * kGemmBK);
+    ra[1] = *reinterpret_cast<const f32x4*>(arow + kt * kGemmBK + 4);
+  };
+  // piece p of step kt's packed B into stage s, with no register in between: the wave's KiB lands at the base given
+  // here + lane * 16, which is where bdst[p * kGemmThreads + tid] = bsrc[...] used to put it
+  char* const bwave = smem + kWideABytes + wave_u * kTileBytes;
+  auto load_b = [&](int kt, int s, int p) {
+    stage_b16(bsrc + kt * bstep + p * kGemmThreads + tid, bwave + s * kWideStage + p * kGemmThreads * 16);
+  };
+  auto store = [&](int s) {
+    char* base = smem + s * kWideStage;
+    bf16x8 p0, p1, p2;
+    split8(ra[0], ra[1], p0, p1, p2);
+    bf16x8* dst = reinterpret_cast<bf16x8*>(base) + wave * 3 * 64 + lane;
+    dst[0] = p0;
+    dst[64] = p1;
+    dst[128] = p2;
+  };
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+  load(0);
+#pragma unroll
+  for (int p = 0; p < kWideBPieces; ++p) load_b(0, 0, p);
+  store(0);
+  stage_b_wait();
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const int cur = kt & 1;
+    const int nxt = kt + 1 < nk ? kt + 1 : kt;   // the last step reloads its own tile into the idle buffer: no branch
+    load(nxt);
+    const bf16x8* sa = reinterpret_cast<const bf16x8*>(smem + cur * kWideStage) + wm * 4 * 3 * 64 + lane;
+    const bf16x8* sb = reinterpret_cast<const bf16x8*>(smem + cur * kWideStage + kWideABytes) + wn * 4 * 3 * 64 + lane;
+    bf16x8 fa[3][4], fb[3][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int p = 0; p < 3; ++p) {
+        fa[p][i] = sa[(i * 3 + p) * 64];
+        fb[p][i] = sb[(i * 3 + p) * 64];
+      }
+    constexpr int kPa[6] = {2, 1, 0, 1, 0, 0}, kPb[6] = {0, 1, 2, 0, 1, 0};   // the order of gemm_bf16x6_kernel
+#pragma unroll
+    for (int t = 0; t < 6; ++t) {
+      if (t == 3) store(cur ^ 1);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[kPb[t]][j], fa[kPa[t]][i], acc[i][j], 0, 0, 0);   // transposed
+          // a pair of B pieces behind every kWideLoadPair MFMAs of the first half.  Stage cur ^ 1 was last read in
+          // the step that the barrier above this one ended
+          if ((t * 16 + i * 4 + j + 1) % kWideLoadPair == 0 && (t * 16 + i * 4 + j + 1) / kWideLoadPair <= kWideBPieces / 2) {
+            const int pair = (t * 16 + i * 4 + j + 1) / kWideLoadPair - 1;
+            load_b(nxt, cur ^ 1, 2 * pair);
+            load_b(nxt, cur ^ 1, 2 * pair + 1);
+          }
+        }
+    }
+    // placement of the 8 global loads: as in gemm_bf16x6_wide_kernel (a pair per kWideLoadPair MFMAs over the first
+    // half of the step, the A pair first)
+#pragma unroll
+    for (int n = 0; n < (2 + kWideBPieces) / 2; ++n) {
+      __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);                  // two vector-memory reads
+      __builtin_amdgcn_sched_group_barrier(0x008, kWideLoadPair, 0);      // kWideLoadPair MFMAs
+    }
+    stage_b_wait();
+    __syncthreads();
+  }
+
+  // rows and M are the group's own: the FULL form runs for a wave whose 64 rows are all below its group's M
+  if constexpr (EPI == VQA_GEMM_EPI_NONE) {
+    gemm_store(acc, g, m0 + wm * 64, n0 + wn * 64, lane);
+  } else {
+    gemm_epilogue<EPI>(acc, g, m0 + wm * 64, n0 + wn * 64, lane);
+  }
+}
+
 // ---- small-tile variant for grids the 256 x 128 tile cannot fill (a few hundred rows, or a narrow N) ---------------
 // Same packed B, same split, same product and k-step order, so with ksplit == 1 every output has the bits of
 // gemm_bf16x6_kernel.  Tile: 64 x 128 outputs per workgroup of 4 waves (2 along M x 2 along N, 32 x 64 each = 2 x 4 MFMA
@@ -1339,6 +1492,46 @@ int vqa_gemm_bf16x6_epi(const float* A, long lda, const void* packed, const floa
     if (epilogue == VQA_GEMM_EPI_GELU) gemm_bf16x6_epi_kernel<VQA_GEMM_EPI_GELU><<<nwg, kGemmThreads, 0, st>>>(e);
     else gemm_bf16x6_epi_kernel<VQA_GEMM_EPI_GELU_GRAD><<<nwg, kGemmThreads, 0, st>>>(e);
   }
+  return launch_status();
+}
+
+int vqa_gemm_bf16x6_grouped(const float* const* A, const long* lda, const void* const* packed, const float* const* bias,
+                            float* const* C, const long* ldc, float* const* aux, const long* ldaux, const long* M,
+                            int n_groups, int N, int K, int epilogue, vqa_stream_t stream) {
+  clear_stale_error();
+  if (n_groups < 1 || n_groups > VQA_GEMM_MAX_GROUPS) return VQA_ERR_SHAPE;
+  if (epilogue != VQA_GEMM_EPI_NONE && epilogue != VQA_GEMM_EPI_GELU && epilogue != VQA_GEMM_EPI_GELU_GRAD) return VQA_ERR_SHAPE;
+  if (!A || !lda || !packed || !C || !ldc || !M || (aux && !ldaux)) return VQA_ERR_NULL;
+  if (N <= 0 || K <= 0 || K % kGemmBK || N % kWideBN) return VQA_ERR_SHAPE;
+  // every group is checked ahead of the launch: a refused call leaves every C untouched.  A group without rows is
+  // skipped whatever its pointers are
+  GemmGroupedArgs ga{};
+  ga.N = N, ga.K = K, ga.vec = 1;
+  long blocks = 0;
+  for (int i = 0; i < n_groups; ++i) {
+    if (M[i] < 0) return VQA_ERR_SHAPE;
+    ga.start[i] = static_cast<int>(blocks);
+    if (M[i] == 0) continue;
+    const float* b = bias ? bias[i] : nullptr;
+    float* x = (aux && epilogue != VQA_GEMM_EPI_NONE) ? aux[i] : nullptr;        // no epilogue: aux, ldaux ignored
+    const long ldx = x ? ldaux[i] : 0;
+    if (!A[i] || !packed[i] || !C[i] || (epilogue == VQA_GEMM_EPI_GELU_GRAD && !x)) return VQA_ERR_NULL;
+    if (lda[i] < K || lda[i] % 4 || ldc[i] < N || (x && ldx < N)) return VQA_ERR_SHAPE;
+    blocks += (M[i] + kWideBM - 1) / kWideBM;
+    if (blocks * (N / kWideBN) > 0x7fffffffL) return VQA_ERR_SHAPE;
+    if (!aligned16(A[i]) || !aligned16(packed[i]) || !aligned4(C[i]) || (b && !aligned4(b)) || (x && !aligned4(x)))
+      return VQA_ERR_ALIGN;
+    if (x && (x == C[i] || x == A[i])) return VQA_ERR_SHAPE;
+    ga.grp[i] = GemmGroup{A[i], static_cast<const bf16x8*>(packed[i]), b, C[i], x, lda[i], ldc[i], ldx, M[i]};
+    ga.vec = ga.vec && gemm_vec_ok(C[i], ldc[i], b, x, ldx);
+  }
+  for (int i = n_groups; i <= VQA_GEMM_MAX_GROUPS; ++i) ga.start[i] = static_cast<int>(blocks);
+  if (blocks == 0) return VQA_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int nwg = static_cast<int>(blocks * (N / kWideBN));
+  if (epilogue == VQA_GEMM_EPI_GELU) gemm_bf16x6_grouped_kernel<VQA_GEMM_EPI_GELU><<<nwg, kGemmThreads, 0, st>>>(ga);
+  else if (epilogue == VQA_GEMM_EPI_GELU_GRAD) gemm_bf16x6_grouped_kernel<VQA_GEMM_EPI_GELU_GRAD><<<nwg, kGemmThreads, 0, st>>>(ga);
+  else gemm_bf16x6_grouped_kernel<VQA_GEMM_EPI_NONE><<<nwg, kGemmThreads, 0, st>>>(ga);
   return launch_status();
 }
 

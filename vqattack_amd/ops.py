@@ -930,6 +930,101 @@ def _gemm_epilogue(a, packed, bias, out, tile, epilogue, aux):
     return out
 
 
+GEMM_MAX_GROUPS = 4      # VQA_GEMM_MAX_GROUPS of include/vqattack_hip.h
+
+
+def gemm_grouped_blocks(Ms, N):
+    """Tile list of one ``vqa_gemm_bf16x6_grouped`` launch over groups of ``Ms`` rows at N columns (N % 256 == 0):
+    ``(starts, grid)`` with ``starts[i]`` the 128-row blocks ahead of group i (``len(Ms) + 1`` entries, the last one the
+    total) and ``grid = starts[-1] * (N // 256)`` workgroups.  Pure arithmetic, no device."""
+    N = int(N)
+    if N <= 0 or N % 256:
+        raise ValueError("the grouped launch runs 128 x 256 tiles: N % 256 == 0, got {}".format(N))
+    starts = [0]
+    for m in Ms:
+        m = int(m)
+        if m < 0:
+            raise ValueError("row counts must be >= 0, got {}".format(tuple(Ms)))
+        starts.append(starts[-1] + -(-m // 128))
+    return tuple(starts), starts[-1] * (N // 256)
+
+
+def gemm_grouped(a_list, packed_list, bias_list=None, out_list=None, epilogue=None, aux_list=None):
+    """``[gemm(a, packed, bias, tile="wide", epilogue=..., aux=...) for each group]`` as ONE launch
+    (``vqa_gemm_bf16x6_grouped``): up to four products with one (K, N) and a weight each -- the expert FFNs of a multiway
+    block -- whose 128 x 256 tiles share a grid, so a group too small to fill the device rides in the last round of a
+    large one.  Every output has the bits of the per-group call.  Returns the outputs in the caller's order.
+
+    ``a_list`` / ``packed_list``: per group, as ``gemm``'s ``a`` / ``packed``; all ``PackedWeight``s share (K, N), else
+    ValueError.  ``bias_list`` / ``out_list`` / ``aux_list``: None, or one entry (a tensor or None) per group.  One
+    ``epilogue`` (None, "gelu", "gelu_grad") serves every group; ``aux`` as in ``gemm``.  ``out`` entries: unit column
+    stride and any row stride >= N.  Outputs of different groups must not overlap (not detected).  N % 256 != 0 or more
+    than four groups: one ``gemm(..., tile="wide")`` per group -- the same bits (the C entry point refuses both)."""
+    n = len(a_list)
+    if n == 0 or len(packed_list) != n:
+        raise ValueError("need one packed weight per group and at least one group")
+    bias_list = [None] * n if bias_list is None else list(bias_list)
+    out_list = [None] * n if out_list is None else list(out_list)
+    aux_list = [None] * n if aux_list is None else list(aux_list)
+    if not len(bias_list) == len(out_list) == len(aux_list) == n:
+        raise ValueError("bias_list, out_list and aux_list take one entry per group")
+    if epilogue is not None and epilogue not in GEMM_EPILOGUES:
+        raise ValueError("epilogue must be None or one of {}, got {!r}".format(sorted(GEMM_EPILOGUES), epilogue))
+    K, N = packed_list[0].K, packed_list[0].N
+    if any((p.K, p.N) != (K, N) for p in packed_list):
+        raise ValueError("the groups of one launch share (K, N), got {}".format([(p.K, p.N) for p in packed_list]))
+    if epilogue is None and any(x is not None for x in aux_list):
+        raise ValueError("aux goes with an epilogue")
+    if epilogue == "gelu_grad" and any(x is None for x in aux_list):
+        raise ValueError("epilogue 'gelu_grad' needs aux = the pre-activation h of every group")
+    if N % 256 or n > GEMM_MAX_GROUPS:
+        # (a group without rows keeps its aux out of gemm's alias check: empty tensors share the null address)
+        return [gemm(a, p, b, out=o, tile="wide", epilogue=epilogue, aux=x) if a.shape[0] or x is None else
+                (o if o is not None else torch.empty(0, N, dtype=torch.float32, device=a.device))
+                for a, p, b, o, x in zip(a_list, packed_list, bias_list, out_list, aux_list)]
+    outs = []
+    for i, (a, p, b, o, x) in enumerate(zip(a_list, packed_list, bias_list, out_list, aux_list)):
+        dev_f32(a, "a", contiguous=False)
+        if a.dim() != 2 or a.shape[1] != K or a.stride(1) != 1 or a.stride(0) % 4:
+            raise ValueError("a of group {} must be (M, {}) with unit column stride and a row stride % 4 == 0, got shape {} "
+                             "strides {}".format(i, K, tuple(a.shape), a.stride()))
+        M = a.shape[0]
+        if o is None:
+            o = torch.empty(M, N, dtype=torch.float32, device=a.device)
+        dev_f32(o, "out", contiguous=False)
+        if tuple(o.shape) != (M, N) or o.stride(1) != 1 or (M > 1 and o.stride(0) < N):
+            raise ValueError("out of group {} must be ({}, {}) with unit column stride, got {} strides {}".format(
+                i, M, N, tuple(o.shape), o.stride()))
+        if b is not None:
+            dev_f32(b, "bias"), _rows_ok("bias", b, N)
+        if x is not None:
+            if x is o:
+                raise ValueError("aux must not be out")
+            if not isinstance(x, torch.Tensor) or tuple(x.shape) != (M, N) or x.stride(1) != 1 or \
+                    (M > 1 and x.stride(0) < N):
+                raise ValueError("aux of group {} must be a ({}, {}) tensor with unit column stride, got {}".format(
+                    i, M, N, (tuple(x.shape), x.stride()) if isinstance(x, torch.Tensor) else type(x)))
+            dev_f32(x, "aux", contiguous=False)
+            if M and x.data_ptr() in (o.data_ptr(), a.data_ptr()):
+                raise ValueError("aux must not alias out or a")
+        same_device(a_list[0], a, p.data, b, o, x)
+        outs.append(o)
+    if any(a.shape[0] for a in a_list):
+        ptrs, longs = ctypes.c_void_p * n, ctypes.c_long * n
+        live = [a.shape[0] > 0 for a in a_list]                   # a group without rows: its entries are not looked at
+
+        def table(ts):
+            return ptrs(*[(t.data_ptr() if t is not None and ok else None) for t, ok in zip(ts, live)])
+        with _on(a_list[0]):
+            check(lib().vqa_gemm_bf16x6_grouped(
+                table(a_list), longs(*[a.stride(0) for a in a_list]), table([p.data for p in packed_list]),
+                table(bias_list), table(outs), longs(*[max(o.stride(0), N) for o in outs]), table(aux_list),
+                longs(*[max(x.stride(0), N) if x is not None else 0 for x in aux_list]),
+                longs(*[a.shape[0] for a in a_list]), n, N, K, GEMM_EPILOGUES[epilogue] if epilogue else 0,
+                stream_for(a_list[0])), "vqa_gemm_bf16x6_grouped")
+    return outs
+
+
 # Planner constants of the small-tile kernel (measured: profiles/r08/): one 64 x 128 tile per workgroup, two workgroups
 # resident per CU.  The split over K raises the grid towards SMALL_TARGET_WORKGROUPS while every part keeps at least
 # SMALL_MIN_KSTEPS k-steps (32 columns of A each) to amortise its prologue and its partial-tile traffic.

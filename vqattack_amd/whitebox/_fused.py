@@ -100,6 +100,22 @@ EPILOGUE_POLICY = {"gelu": {}, "gelu_grad": {(3072, 768): _WIDE_ROWS}}
 # switch runs what the previous commit ran.  VQA_GEMM_TAIL=1 read 1.008x of VQA_GEMM_TAIL=0 in one tree (two rounds).
 TAIL_POLICY = {}
 
+# A multiway layer sends its text rows and its image rows through two FFNs: four GEMMs per layer (fc1 / fc2, forward and
+# input gradient) run twice, once per expert.  At the benchmark's shape the text expert's are 24-96 workgroups -- below
+# MIN_WORKGROUPS, so they are library calls -- while the image expert's 128 x 256 tiles end in a round that is partly
+# empty.  ops.gemm_grouped (vqa_gemm_bf16x6_grouped) runs both experts' tiles in ONE launch, larger group first, with the
+# bits of ops.gemm on each expert's rows; the GELU epilogue of the launch is what gelu_epilogue decides for the larger
+# group.  A pair is grouped only where both experts are packed, N % 256 == 0, both have rows and the larger one alone
+# would run a bf16x6 large tile (from MIN_WORKGROUPS up, VQA_GEMM != library).  A shape class (N, K) -> (fewest rows, most
+# rows) OF THE LARGER GROUP, both inclusive, is to be listed only by the rule of WIDE_POLICY (tools/gemm_bench.py
+# --grouped: the grouped call's median against the median of the two calls it replaces) plus the benchmark.
+# VQA_GEMM_GROUPED=1 groups every eligible pair, =0 none.
+# Grouping moves the smaller expert's rows from the library's fp32 GEMM to the bf16x6 kernel, which changes their bits
+# (fp32-grade either way); the larger expert's outputs keep theirs.  Nothing is listed: the unset switch launches what
+# the previous commit launched, and listing a class is a change of its own that weighs that.  See profiles/r16/README.md
+# for what was measured.
+GROUPED_POLICY = {}
+
 _CUS = {}
 
 
@@ -212,6 +228,113 @@ def _linear_grad_gelu(g, w, packed, h):
     if pk is not None and gelu_epilogue(g.shape[0], pk.N, pk.K, "gelu_grad"):
         return ops.gemm(g, pk, epilogue="gelu_grad", aux=h)
     return ops.gelu_bwd(h, _linear_grad(g, w, packed))                  # in place on the GEMM's output
+
+
+def gemm_grouped_pair(rows, n, k):
+    """Whether the two experts' GEMMs (rows[0] and rows[1] rows, one (n, k)) run as one grouped launch."""
+    big = max(rows)
+    if not _kernel_gemms() or n % 256 or min(rows) <= 0 or ops.gemm_workgroups(big, n) < MIN_WORKGROUPS:
+        return False
+    switch = os.environ.get("VQA_GEMM_GROUPED", "")
+    if switch in ("0", "1"):
+        return switch == "1"
+    lo, hi = GROUPED_POLICY.get((n, k), (1, 0))
+    return lo <= big <= hi
+
+
+def _pair_order(rows, pks):
+    """The order -- larger group first -- in which a two-expert layer's GEMMs on ``pks`` go into ONE ops.gemm_grouped
+    launch, or None where they run as the two calls of ``_linear`` / ``_linear_grad``."""
+    if len(pks) != 2 or pks[0] is None or pks[1] is None or (pks[0].N, pks[0].K) != (pks[1].N, pks[1].K):
+        return None
+    if not gemm_grouped_pair(rows, pks[0].N, pks[0].K):
+        return None
+    return (0, 1) if rows[0] >= rows[1] else (1, 0)
+
+
+def _pair_call(order, xs, pks, biases=None, epilogue=None, aux=None):
+    """One grouped launch over the experts in ``order``; the outputs come back in expert order."""
+    def pick(ts):
+        return None if ts is None else [ts[e] for e in order]
+    outs = ops.gemm_grouped(pick(xs), pick(pks), pick(biases), epilogue=epilogue, aux_list=pick(aux))
+    back = [None] * len(order)
+    for e, o in zip(order, outs):
+        back[e] = o
+    return back
+
+
+def _pair_linear_gelu(order, ys, lay, save):
+    """``_linear_gelu`` of both experts' fc1 as one launch: ([h or None per expert], [gelu(h) per expert])."""
+    pks = [lay.packed["fc1_%d" % e][0] for e in range(2)]
+    b1s = [m[1] for m in lay.mlp]
+    big = order[0]
+    if gelu_epilogue(ys[big].shape[0], pks[big].N, pks[big].K):
+        hs = [torch.empty(y.shape[0], pks[big].N, dtype=torch.float32, device=y.device) for y in ys] if save else None
+        return (hs if save else [None, None]), _pair_call(order, ys, pks, b1s, epilogue="gelu", aux=hs)
+    hs = _pair_call(order, ys, pks, b1s)
+    return (hs if save else [None, None]), [ops.gelu_fwd(h) for h in hs]
+
+
+def _pair_linear_grad_gelu(order, dm, lay, hs):
+    """``_linear_grad_gelu`` of both experts' fc2 as one launch."""
+    pks = [lay.packed["fc2_%d" % e][1] for e in range(2)]
+    big = order[0]
+    if gelu_epilogue(dm[big].shape[0], pks[big].N, pks[big].K, "gelu_grad"):
+        return _pair_call(order, dm, pks, epilogue="gelu_grad", aux=hs)
+    return [ops.gelu_bwd(h, da) for h, da in zip(hs, _pair_call(order, dm, pks))]     # in place on the GEMM's output
+
+
+def _ffn_forward(ys, lay, save):
+    """The FFN of every expert of a layer on its rows ``ys[e]``: ([h or None per expert], [fc2 output per expert]).  A
+    two-expert layer runs a stage of both experts as one grouped launch where ``_pair_order`` allows it, and exactly the
+    per-expert calls where it allows neither stage."""
+    erows = [ye.shape[0] for ye in ys]
+    o1 = _pair_order(erows, [lay.packed["fc1_%d" % e][0] for e in range(len(ys))])
+    o2 = _pair_order(erows, [lay.packed["fc2_%d" % e][0] for e in range(len(ys))])
+    if o1 is None and o2 is None:
+        hs, ms = [], []
+        for e, (ye, (w1, b1, w2, b2)) in enumerate(zip(ys, lay.mlp)):
+            h, a = _linear_gelu(ye, w1, b1, lay.packed["fc1_%d" % e], save)
+            ms.append(_linear(a, w2, b2, lay.packed["fc2_%d" % e]))
+            hs.append(h)
+            del a
+    else:                         # both experts stage by stage: each stage one grouped launch where it is eligible
+        if o1 is not None:
+            hs, acts = _pair_linear_gelu(o1, ys, lay, save)
+        else:
+            hs, acts = map(list, zip(*[_linear_gelu(ye, m[0], m[1], lay.packed["fc1_%d" % e], save)
+                                       for e, (ye, m) in enumerate(zip(ys, lay.mlp))]))
+        if o2 is not None:
+            ms = _pair_call(o2, acts, [lay.packed["fc2_%d" % e][0] for e in range(2)], [m[3] for m in lay.mlp])
+        else:
+            ms = [_linear(a, m[2], m[3], lay.packed["fc2_%d" % e]) for e, (a, m) in enumerate(zip(acts, lay.mlp))]
+        del acts
+    return hs, ms
+
+
+def _ffn_backward(dm, hs, lay):
+    """The input gradient of every expert's FFN from the gradients ``dm[e]`` of its output and the saved ``hs[e]``."""
+    erows = [dme.shape[0] for dme in dm]
+    o2 = _pair_order(erows, [lay.packed["fc2_%d" % e][1] for e in range(len(dm))])
+    o1 = _pair_order(erows, [lay.packed["fc1_%d" % e][1] for e in range(len(dm))])
+    if o1 is None and o2 is None:
+        dys = []
+        for e, (dme, h, (w1, _b1, w2, _b2)) in enumerate(zip(dm, hs, lay.mlp)):
+            da = _linear_grad_gelu(dme, w2, lay.packed["fc2_%d" % e], h)      # (rows_e, 4D): dh
+            dys.append(_linear_grad(da, w1, lay.packed["fc1_%d" % e]))
+            del da
+    else:                         # stage by stage, as in _forward
+        if o2 is not None:
+            das = _pair_linear_grad_gelu(o2, dm, lay, hs)
+        else:
+            das = [_linear_grad_gelu(dme, m[2], lay.packed["fc2_%d" % e], h)
+                   for e, (dme, h, m) in enumerate(zip(dm, hs, lay.mlp))]
+        if o1 is not None:
+            dys = _pair_call(o1, das, [lay.packed["fc1_%d" % e][1] for e in range(2)])
+        else:
+            dys = [_linear_grad(da, m[0], lay.packed["fc1_%d" % e]) for e, (da, m) in enumerate(zip(das, lay.mlp))]
+        del das
+    return dys
 
 
 class LayerSpec:
@@ -344,12 +467,7 @@ def _forward(x0, call, save):
             ys = [torch.empty(rows, d, dtype=f32, device=dev)]
             ops.ln_fwd(x_l, lay.ln2[0][0], lay.ln2[0][1], ys[0], mean2, rstd2, lay.eps, r0=p, rscale=lay.gamma1, x_out=x1)
         del p
-        hs, ms = [], []
-        for e, (ye, (w1, b1, w2, b2)) in enumerate(zip(ys, lay.mlp)):
-            h, a = _linear_gelu(ye, w1, b1, lay.packed["fc1_%d" % e], save)
-            ms.append(_linear(a, w2, b2, lay.packed["fc2_%d" % e]))
-            hs.append(h)
-            del a
+        hs, ms = _ffn_forward(ys, lay, save)
         del ys
         if save:
             saved.append(dict(x_l=x_l, mean1=mean1, rstd1=rstd1, qkv=qkv, o=o, lse=lse, scores=scores, bias=bias_t,
@@ -403,11 +521,7 @@ def _backward(saved, call, g_feats, g_states, shape):
     for li in range(n - 1, -1, -1):
         lay, sv = spec.layers[li], saved[li]
         two = len(lay.mlp) == 2
-        dys = []
-        for e, (dme, h, (w1, _b1, w2, _b2)) in enumerate(zip(dm, sv["hs"], lay.mlp)):
-            da = _linear_grad_gelu(dme, w2, lay.packed["fc2_%d" % e], h)      # (rows_e, 4D): dh
-            dys.append(_linear_grad(da, w1, lay.packed["fc1_%d" % e]))
-            del da
+        dys = _ffn_backward(dm, sv["hs"], lay)
         del dm
         dx1 = torch.empty(rows, d, dtype=torch.float32, device=dev)
         dp = torch.empty(rows, d, dtype=torch.float32, device=dev) if lay.gamma1 is not None else dx1
