@@ -414,6 +414,17 @@ int vqa_gemm_bf16x6(const float* A, long lda, const void* packed, const float* b
 int vqa_gemm_bf16x6_tile(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M,
                          int N, int K, int tile, vqa_stream_t stream);
 
+/* vqa_gemm_bf16x6_persistent: the 128 x 256 tile of vqa_gemm_bf16x6_tile as ONE launch of `workgroups` workgroups that
+ *   each walk a fixed list of tiles (blockIdx arithmetic: no atomics, no counters, nothing to reset between launches, so
+ *   the launch may be captured and replayed).  A tile's last k-step stages the first k-step of the workgroup's next
+ *   tile, so only a workgroup's first tile waits for its operands with the matrix pipe idle.  Every output has the bits
+ *   of vqa_gemm_bf16x6_tile.  Argument rules and return codes of vqa_gemm_bf16x6_tile with VQA_GEMM_TILE_128X256, except
+ *   that N % 256 != 0 is VQA_ERR_SHAPE (there is no other tile to run).  workgroups: at least 1, else VQA_ERR_SHAPE;
+ *   one per compute unit is the intended value, and a value above the tile count ceil(M / 128) * (N / 256) is clamped to
+ *   it.  A refused call launches nothing.  Never allocates, never synchronises. */
+int vqa_gemm_bf16x6_persistent(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M,
+                               int N, int K, int workgroups, vqa_stream_t stream);
+
 /* vqa_gemm_bf16x6_half: vqa_gemm_bf16x6 on 128 x 128 output tiles (half a large tile's k-loop work per workgroup, one
  *   workgroup per CU like them); argument rules and return codes of vqa_gemm_bf16x6, the same bits.
  * vqa_gemm_bf16x6_tail: one product in two launches, back to back on `stream`: rows [0, m_split) on `tile` as

@@ -11,7 +11,11 @@ tile behind it (``vqa_gemm_bf16x6_tail``) -- is timed against "unsplit", the sam
 rule of ``_fused.TAIL_POLICY``; for comparison only, "tail_small" runs the rows behind the cut through
 ``gemm_small(ksplit=1)``, and "main" / "half_main" run the rows ahead of the cut (whole rounds of either tile) on the
 policy tile and on the half tile, which gives the time of a round of half tiles over a round of full ones.  Each
-carries ``same_bits_as_kernel``.
+carries ``same_bits_as_kernel``.  Where N % 256 == 0, "persistent" -- ``ops.gemm_persistent``, the 128 x 256 tile as one
+launch of one workgroup per CU -- is timed against the tile ``_fused.gemm_tile`` picks for the shape (what is dispatched
+without an entry in ``_fused.PERSISTENT_POLICY``), by that table's rule.  ``--image-rows`` replaces the image expert's row
+count (the benchmark's own is 64 x 577 = 36928; the default here is batch x (tokens - text tokens)) and ``--rows`` the row
+count of the shapes that see every token (qkv and the projections).
 
 Random data (activations ~ N(0, 1), weights ~ N(0, 0.02^2)): bf16 MFMA loops hold a lower clock on random data than on
 zeros.  The variants are interleaved in one process over several rounds; per shape the median and min time per call, the
@@ -50,14 +54,14 @@ MODELS = {"vlmo_base": (768, 3072, 591, 40, 64), "albef_base": (768, 3072, 577, 
           "vlmo_large": (1024, 4096, 591, 40, 128)}
 
 
-def shapes(model, batch=0):
+def shapes(model, batch=0, img_rows=0, all_rows=0):
     """(name, M, N, K, bias) of every encoder GEMM of one layer, forward and input-gradient backward."""
     d, f, s, t, b = MODELS[model]
     b = batch or b
-    rows = b * s
+    rows = all_rows or b * s
     out = [("qkv_fwd", rows, 3 * d, d, True), ("qkv_bwd", rows, d, 3 * d, False),
            ("proj_fwd", rows, d, d, True), ("proj_bwd", rows, d, d, False)]
-    experts = [("img", b * (s - t)), ("txt", b * t)] if t else [("all", rows)]
+    experts = [("img", img_rows or b * (s - t)), ("txt", b * t)] if t else [("all", rows)]
     if t:
         experts.append(("vl", rows))
     for tag, m in experts:
@@ -83,7 +87,7 @@ def grouped_main(args):
     cus = torch.cuda.get_device_properties(dev).multi_processor_count
     gen = torch.Generator(device=dev).manual_seed(0)
     d, f = MODELS[args.model][:2]
-    m_img = args.image_rows
+    m_img = args.image_rows or 64 * 577
     # (name, N, K, bias, the GELU stage the GEMM feeds: None, "gelu" (forward) or "gelu_grad" (backward))
     pairs = [("fc1_fwd", f, d, True, "gelu"), ("fc2_fwd", d, f, True, None), ("fc2_bwd", f, d, False, "gelu_grad"),
              ("fc1_bwd", d, f, False, None)]
@@ -230,9 +234,11 @@ def main():
                     help="time each variant as ONE captured graph of --reps calls (device time without the host's launch "
                          "cost: how the batch-1 path runs, which is replayed from a captured graph)")
     ap.add_argument("--out", default="")
+    ap.add_argument("--rows", type=int, default=0, help="rows of the shapes that see every token (default: batch x tokens)")
     ap.add_argument("--grouped", action="store_true",
                     help="time ops.gemm_grouped per expert pair against the two calls dispatched today (see above)")
-    ap.add_argument("--image-rows", type=int, default=64 * 577, help="--grouped: rows of the image expert")
+    ap.add_argument("--image-rows", type=int, default=0,
+                    help="rows of the image expert (default: batch x image tokens; with --grouped 64 x 577)")
     ap.add_argument("--text-rows", default="896,2560", help="--grouped: comma-separated row counts of the text expert")
     args = ap.parse_args()
     if args.grouped:
@@ -244,7 +250,7 @@ def main():
     gen = torch.Generator(device=dev).manual_seed(0)
     results = []
     ksplits = [int(v) for v in args.ksplit.split(",") if v]
-    for name, M, N, K, has_bias in shapes(args.model, args.batch):
+    for name, M, N, K, has_bias in shapes(args.model, args.batch, args.image_rows, args.rows):
         if args.only and name not in args.only.split(","):
             continue
         a = torch.randn(M, K, device=dev, generator=gen)
@@ -268,6 +274,9 @@ def main():
         out_w = torch.empty(M, N, device=dev)
         if N % 256 == 0:
             variants.append(("wide", lambda: ops.gemm(a, packed, bias, out=out_w, tile="wide")))
+        out_p = torch.empty(M, N, device=dev)
+        if N % 256 == 0:
+            variants.append(("persistent", lambda: ops.gemm_persistent(a, packed, bias, out=out_p)))
         planned = ops.gemm_small_plan(M, N, K)
         small = sorted({k for k in ksplits + [planned] if 1 <= k <= min(K // 32, 16)}) if ksplits else []
         out_s = torch.empty(M, N, device=dev)
@@ -370,6 +379,23 @@ def main():
         torch.cuda.synchronize()
         half = dict(stats("half"), same_bits_as_kernel=bool(torch.equal(out_h, out_k)), workgroups=-(-M // 128) * (N // 128),
                     speedup_vs_kernel_median=med("kernel") / med("half"))
+        persistent = None
+        if "persistent" in times:
+            out_p.fill_(7.0)
+            ops.gemm_persistent(a, packed, bias, out=out_p)
+            torch.cuda.synchronize()
+            today = "wide" if epi_tile == "wide" else "kernel"          # the variant that runs _fused.gemm_tile's tile
+            u = stats(today)
+            persistent = dict(stats("persistent"), same_bits_as_kernel=bool(torch.equal(out_p, out_k)), today=today,
+                              tiles=-(-M // 128) * (N // 256), workgroups=min(_fused.device_cus(dev), -(-M // 128) * (N // 256)),
+                              policy_lists=_fused.gemm_persistent(M, N, K), today_ms_median=u["ms_median"],
+                              today_ms_spread=u["ms_spread"], speedup_vs_today_median=u["ms_median"] / med("persistent"))
+            # the policy's rule: the medians' difference against the larger round-to-round spread of the two
+            persistent["margin_ms"] = u["ms_median"] - persistent["ms_median"]
+            persistent["larger_spread_ms"] = max(persistent["ms_spread"], u["ms_spread"])
+            persistent["passes_rule"] = persistent["margin_ms"] > persistent["larger_spread_ms"]
+            if "wide" in times:
+                persistent["speedup_vs_wide_median"] = med("wide") / med("persistent")
         tail = None
         if "tail" in times:
             tail = dict(tile=epi_tile, cus=cus, m_split=cut, tail_workgroups=-(-(M - cut) // 128) * (N // 128),
@@ -423,10 +449,11 @@ def main():
                    library_ms_spread=max(times["library"]) - min(times["library"]),
                    big_workgroups=ops.gemm_workgroups(M, N), small_tiles=ops.gemm_small_workgroups(M, N), small=small_rows,
                    wide=wide, policy_tile=_fused.gemm_tile(M, N, K), half=half, tail=tail, epilogue=epilogue,
+                   persistent=persistent,
                    kernel_err_max=ek[0], kernel_err_rms=ek[1], library_err_max=el[0], library_err_rms=el[1])
         print(json.dumps(row), flush=True)
         results.append(row)
-        del a, w, packed, out_k, out_l, out_s, out_w, out_h, out_t
+        del a, w, packed, out_k, out_l, out_s, out_w, out_h, out_t, out_p
         torch.cuda.empty_cache()
     summary = dict(model=args.model, batch=args.batch or MODELS[args.model][4], tuned_gemms=tuned, device=torch.cuda.get_device_name(),
                    rounds=args.rounds, reps=args.reps, warmup=args.warmup, graph=args.graph, shapes=results)
@@ -449,6 +476,14 @@ def main():
         print("  half tile    {:>8.3f}x kernel   {:.4f} ms (spread {:.4f})  {} workgroups  bits {}".format(
             hf["speedup_vs_kernel_median"], hf["ms_median"], hf["ms_spread"], hf["workgroups"],
             "equal" if hf["same_bits_as_kernel"] else "DIFFER"))
+        if r["persistent"]:
+            ps = r["persistent"]
+            print("  persistent {} {:>8.3f}x {:<7}  {:.4f} ms (spread {:.4f}; {} {:.4f} spread {:.4f})  margin {:+.4f} {}  "
+                  "{} tiles on {} workgroups  bits {}".format(
+                      "*" if ps["policy_lists"] else " ", ps["speedup_vs_today_median"], ps["today"], ps["ms_median"],
+                      ps["ms_spread"], ps["today"], ps["today_ms_median"], ps["today_ms_spread"], ps["margin_ms"],
+                      "passes" if ps["passes_rule"] else "fails", ps["tiles"], ps["workgroups"],
+                      "equal" if ps["same_bits_as_kernel"] else "DIFFER"))
         if r["tail"]:
             tl = r["tail"]
             for key in ("tail", "tail_small"):

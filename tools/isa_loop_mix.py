@@ -5,9 +5,10 @@ instruction inside a tile loop is paid in matrix-pipe time; the quarter-rate int
 per kernel: registers, occupancy, and for the innermost loop the MFMA count, the other vector instructions and the slow
 ones (v_mul_lo / v_mul_hi / v_mad_u64) -- all blocks of the loop, so conditional paths (last tile, key hole, lazy
 rescale) are included.
-    python tools/isa_loop_mix.py [file.s] [--src loss.hip] [-v] [--waits]
-(without a .s file: compiles csrc/<src>, default attn.hip).  --waits prints, per kernel, the order of the loop's vector
-memory instructions and `s_waitcnt vmcnt(N)`: L = load, S = store, wN = wait until at most N are outstanding.  The
+    python tools/isa_loop_mix.py [file.s] [--src loss.hip] [-v] [--waits] [--innermost]
+(without a .s file: compiles csrc/<src>, default attn.hip).  --innermost counts, where loops are nested (a persistent
+kernel's tile loop around its k-loop), the deepest loop's blocks only; a kernel whose loops are not nested prints what it
+prints without the option.  --waits prints, per kernel, the order of the loop's vector memory instructions and `s_waitcnt vmcnt(N)`: L = load, S = store, wN = wait until at most N are outstanding.  The
 counter is ONE for loads and stores, in issue order; behind a branch that only some path takes the compiler no longer
 knows N and waits for more than the data it needs -- `S w0` ahead of arithmetic means "wait for that store to be
 acknowledged", `L L L w0` right after a prefetch means the prefetch is not one.
@@ -30,8 +31,31 @@ def assembly(src="attn.hip"):
     return out
 
 
-def kernels(path):
-    """Per kernel of an assembly file: (demangled name, {NumVgprs, Occupancy, ScratchSize}, loop body text)."""
+def innermost_body(kernel_text):
+    """The blocks of a kernel's deepest loop only.  A block's comment names its loop and depth ("in Loop: Header=BB2_15
+    Depth=2"; a header: "This Inner Loop Header: Depth=2", on the label's line or on the comment line behind a "Parent
+    Loop" one).  For a kernel whose loops are not nested this is the body `kernels` yields without the option."""
+    blocks, depth = [], 0
+    lines = kernel_text.split("\n")
+    for n, line in enumerate(lines):
+        if re.match(r"(\.LBB\d+_\d+:|; %bb\.\d+:)", line):
+            head = line
+            for more in lines[n + 1:]:              # the label's comment runs on over lines that hold a comment only
+                if not re.match(r"\s+;", more):
+                    break
+                head += more
+            found = re.search(r"(?:Loop Header: Depth=|in Loop: Header=\S+ Depth=)(\d+)", head)
+            depth = int(found.group(1)) if found else 0
+            blocks.append((depth, []))
+        elif blocks and depth:
+            blocks[-1][1].append(line)
+    deepest = max([d for d, _b in blocks] + [0])
+    return "\n".join(l for d, b in blocks if d == deepest and d for l in b)
+
+
+def kernels(path, innermost=False):
+    """Per kernel of an assembly file: (demangled name, {NumVgprs, Occupancy, ScratchSize}, loop body text).
+    ``innermost``: of nested loops only the deepest one's blocks (a tile loop around a k-loop: the k-loop)."""
     text = open(path).read()
     for k in re.split(r"\n(?=_ZN3vqa[^\n]*:\s+; @)", text):
         name = k.split(":")[0]
@@ -47,7 +71,7 @@ def kernels(path):
                 inside = "Loop Header" in line or "in Loop:" in line
             elif inside:
                 body.append(line)
-        yield demangled, meta, "\n".join(body)
+        yield demangled, meta, innermost_body(k) if innermost else "\n".join(body)
 
 
 def memory_sequence(body):
@@ -76,7 +100,7 @@ def main():
     files = [a for a in args if a.endswith(".s")]
     path = files[0] if files else assembly(src)
     verbose, waits = "-v" in args, "--waits" in args
-    for demangled, meta, body in kernels(path):
+    for demangled, meta, body in kernels(path, innermost="--innermost" in args):
         ins = [l.split()[0] for l in body.split("\n") if l.startswith("\t") and l.split() and not l.strip().startswith(";")]
         valu = [x for x in ins if x.startswith("v_") and not x.startswith("v_mfma")]
         slow = [x for x in valu if x.startswith(("v_mul_lo", "v_mul_hi", "v_mad_u64", "v_mad_i64"))]

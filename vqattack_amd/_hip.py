@@ -76,6 +76,7 @@ SIGNATURES = {
     "vqa_gemm_pack_b": (_i, [_p, _l, _i, _p, _i, _i, _p]),
     "vqa_gemm_bf16x6": (_i, [_p, _l, _p, _p, _p, _l, _l, _i, _i, _p]),
     "vqa_gemm_bf16x6_tile": (_i, [_p, _l, _p, _p, _p, _l, _l, _i, _i, _i, _p]),
+    "vqa_gemm_bf16x6_persistent": (_i, [_p, _l, _p, _p, _p, _l, _l, _i, _i, _i, _p]),
     "vqa_gemm_bf16x6_half": (_i, [_p, _l, _p, _p, _p, _l, _l, _i, _i, _p]),
     "vqa_gemm_bf16x6_tail": (_i, [_p, _l, _p, _p, _p, _l, _l, _i, _i, _i, _l, _p]),
     "vqa_gemm_small_ws_bytes": (_sz, [_l, _i, _i]),

@@ -49,6 +49,11 @@
 // FFNs of a multiway block -- as one grid, so a product too small for a launch of its own fills the last round of a
 // large one (vqa_gemm_bf16x6_grouped; the groups travel in the kernel arguments).  The same loop, the same bits per group.
 //
+// Persistent: gemm_bf16x6_persistent_kernel runs the 128 x 256 tiles of one product as ONE launch of one workgroup per
+// CU, each walking a fixed, blockIdx-derived list of tiles (vqa_gemm_bf16x6_persistent).  The last k-step of a tile
+// stages the first k-step of the workgroup's next tile in place of the wide kernel's redundant reload, so only a
+// workgroup's first tile waits for its operands with the matrix pipe idle.  The same loop, the same bits.
+//
 // Deterministic: fixed summation order (per k-step the products a2b0, a1b1, a0b2, a1b0, a0b1, a0b0 in turn, k-steps in
 // order), no split-K, no atomics.  Rows >= M are read clamped to row M-1 and never stored.
 #include "common.hpp"
@@ -1009,6 +1014,170 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_grouped_kernel(GemmG
   }
 }
 
+// ---- persistent launch of the 128 x 256 tile: one workgroup per CU walks a list of tiles -----------------------------
+// At 144 KiB of LDS a large tile is alone on its CU, so nothing covers what a tile pays once: the wait for its first
+// operands (global loads, the split, a barrier) with the matrix pipe idle.  gemm_bf16x6_persistent_kernel is
+// gemm_bf16x6_wide_kernel with a tile loop around its k-loop, as a copy (see the note above GemmEpiArgs), launched with
+// `workgroups` <= tiles workgroups.  In a tile's LAST k-step -- where the wide kernel reloads the step it is running into
+// the idle LDS buffer only to avoid a branch -- the loads fetch step 0 of the workgroup's next tile (its rows clamped to
+// M - 1, its column block of packed B), so behind the barrier that ends the step the next tile's operands are staged
+// and published: the wave stores its accumulators, zeroes them and goes straight into the next k-loop.  The buffer
+// parity runs on across tiles (a tile with an odd number of k-steps hands over in the other buffer); with one k-step
+// the only step is also the last.  The workgroup's last tile keeps the wide kernel's reload of itself, so nothing is
+// read that the wide kernel would not read.
+//
+// Tile list: tiles are numbered m-block major, the N / 256 column blocks fastest, as in the wide kernel.  The XCD remap
+// of the wide kernel, applied to the WORKGROUPS, gives the grid's workgroups an order in which those of one XCD are
+// neighbours at positions [pos, pos + wx); the XCD's run of the tile list is [tiles * pos / W, tiles * (pos + wx) / W)
+// -- ONE contiguous run per XCD, in proportion to its workgroups -- and they deal it out in turn: workgroup i of wx
+// takes tiles i, i + wx, i + 2 wx, ... of the run.  At any time an XCD therefore works on a window of neighbouring tiles
+// (the same rows of A, every column block of B), as a round of the wide kernel does, no workgroup has more than
+// ceil(tiles / W) tiles, and the workgroups that have one tile more than the others are spread over all XCDs, as the
+// part-filled last round of the wide kernel is.  (Cutting the list into W equal runs first puts those workgroups on
+// the first XCDs, which then run their last tile as slowly as a full round: measured 3-10 % slower than the wide kernel,
+// profiles/r17/README.md.)  The assignment is blockIdx arithmetic: no atomics, no counters, nothing to reset between
+// launches (graph replay).  With workgroups <= tiles every workgroup has a tile; one without returns before it touches
+// memory.
+//
+// Same split, packed B, load placement, product and k-step order per tile, and gemm_store: every output has the bits
+// of gemm_bf16x6_wide_kernel.
+__global__ __launch_bounds__(kGemmThreads) void gemm_bf16x6_persistent_kernel(GemmArgs g, int ntiles) {
+  __shared__ __attribute__((aligned(16))) char smem[2 * kWideStage];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);   // the same value, known to be uniform
+  const int wm = wave >> 2, wn = wave & 3;                 // this wave's 64 x 64 output block
+  const int ntb = g.N / kWideBN;
+  const int nk = g.K / kGemmBK;
+  const int nt16 = g.N / 16;
+  // this workgroup's tiles: run0 + i, run0 + i + wx, ... below run1 (see above)
+  const int nwg = gridDim.x, orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, rem = nwg & 7;
+  const int wx = q + (xcd < rem ? 1 : 0);                                              // workgroups of this XCD
+  const int pos = xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;         // the first of them, remapped
+  const int run0 = static_cast<int>(static_cast<long>(ntiles) * pos / nwg);
+  const int run1 = static_cast<int>(static_cast<long>(ntiles) * (pos + wx) / nwg);
+  int tile = run0 + (orig >> 3);
+  if (tile >= run1) return;
+
+  // staging: this thread splits one (row, 8-k chunk) piece of A per k-step -- m-tile wave, row lane & 15, chunk
+  // lane >> 4 -- and stages 6 x 16 B of packed B
+  const size_t bstep = static_cast<size_t>(nt16) * 3 * 64;            // bf16x8 per k-step of packed B
+  // where tile t starts: its first row and column, this thread's row of A (step 0) and the tile's run of packed B
+  auto locate = [&](int t, long& m0, int& n0, const float*& arow, const bf16x8*& bsrc) {
+    const int mb = t / ntb, nb = t - mb * ntb;
+    m0 = static_cast<long>(mb) * kWideBM;
+    n0 = nb * kWideBN;
+    long r = m0 + wave * 16 + (lane & 15);
+    r = r < g.M ? r : g.M - 1;
+    arow = g.A + r * g.lda + 8 * (lane >> 4);
+    bsrc = g.B + static_cast<size_t>(nb) * kWideNT * 3 * 64;
+  };
+  long m0;
+  int n0;
+  const float* arow;
+  const bf16x8* bsrc;
+  locate(tile, m0, n0, arow, bsrc);
+
+  f32x4 ra[2];
+  auto load = [&](const float* src) {
+    ra[0] = *reinterpret_cast<const f32x4*>(src);
+    ra[1] = *reinterpret_cast<const f32x4*>(src + 4);
+  };
+  // piece p of the k-step of packed B at src into stage s, with no register in between: the wave's KiB lands at the
+  // base given here + lane * 16
+  char* const bwave = smem + kWideABytes + wave_u * kTileBytes;
+  auto load_b = [&](const bf16x8* src, int s, int p) {
+    stage_b16(src + p * kGemmThreads + tid, bwave + s * kWideStage + p * kGemmThreads * 16);
+  };
+  auto store = [&](int s) {
+    char* base = smem + s * kWideStage;
+    bf16x8 p0, p1, p2;
+    split8(ra[0], ra[1], p0, p1, p2);
+    bf16x8* dst = reinterpret_cast<bf16x8*>(base) + wave * 3 * 64 + lane;
+    dst[0] = p0;
+    dst[64] = p1;
+    dst[128] = p2;
+  };
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+  // the only prologue of the workgroup: step 0 of its first tile
+  load(arow);
+#pragma unroll
+  for (int p = 0; p < kWideBPieces; ++p) load_b(bsrc, 0, p);
+  store(0);
+  stage_b_wait();
+  __syncthreads();
+  int cur = 0;                                   // the buffer that holds the step about to run: flips per k-step, across tiles
+  for (;;) {
+    // what the tile's last k-step loads: step 0 of the next tile, or (the workgroup's last tile) that step again
+    const int tnext = tile + wx;
+    const bool more = tnext < run1;
+    long m0n = m0;
+    int n0n = n0;
+    const float* arow_n = arow + (nk - 1) * kGemmBK;
+    const bf16x8* bsrc_n = bsrc + (nk - 1) * bstep;
+    if (more) locate(tnext, m0n, n0n, arow_n, bsrc_n);
+    // one k-step on the operands in buffer cur; anxt / bnxt: what it stages into the other buffer
+    auto step = [&](const float* anxt, const bf16x8* bnxt) {
+      load(anxt);
+      const bf16x8* sa = reinterpret_cast<const bf16x8*>(smem + cur * kWideStage) + wm * 4 * 3 * 64 + lane;
+      const bf16x8* sb = reinterpret_cast<const bf16x8*>(smem + cur * kWideStage + kWideABytes) + wn * 4 * 3 * 64 + lane;
+      bf16x8 fa[3][4], fb[3][4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+          fa[p][i] = sa[(i * 3 + p) * 64];
+          fb[p][i] = sb[(i * 3 + p) * 64];
+        }
+      constexpr int kPa[6] = {2, 1, 0, 1, 0, 0}, kPb[6] = {0, 1, 2, 0, 1, 0};   // the order of gemm_bf16x6_kernel
+#pragma unroll
+      for (int t = 0; t < 6; ++t) {
+        if (t == 3) store(cur ^ 1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[kPb[t]][j], fa[kPa[t]][i], acc[i][j], 0, 0, 0);   // transposed
+            // a pair of B pieces behind every kWideLoadPair MFMAs of the first half.  Stage cur ^ 1 was last read in
+            // the step that the barrier above this one ended -- of this tile or of the one before
+            if ((t * 16 + i * 4 + j + 1) % kWideLoadPair == 0 && (t * 16 + i * 4 + j + 1) / kWideLoadPair <= kWideBPieces / 2) {
+              const int pair = (t * 16 + i * 4 + j + 1) / kWideLoadPair - 1;
+              load_b(bnxt, cur ^ 1, 2 * pair);
+              load_b(bnxt, cur ^ 1, 2 * pair + 1);
+            }
+          }
+      }
+      // placement of the 8 global loads: as in gemm_bf16x6_wide_kernel (a pair per kWideLoadPair MFMAs over the first
+      // half of the step, the A pair first)
+#pragma unroll
+      for (int n = 0; n < (2 + kWideBPieces) / 2; ++n) {
+        __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);                  // two vector-memory reads
+        __builtin_amdgcn_sched_group_barrier(0x008, kWideLoadPair, 0);      // kWideLoadPair MFMAs
+      }
+      stage_b_wait();
+      __syncthreads();
+      cur ^= 1;
+    };
+    // the wide kernel's loop over all steps but the last, which is the same step on other pointers: no select in the loop
+    for (int kt = 0; kt + 1 < nk; ++kt) step(arow + (kt + 1) * kGemmBK, bsrc + (kt + 1) * bstep);
+    step(arow_n, bsrc_n);
+
+    // epilogue of the wide kernel.  The stores read registers only; the next tile's first step is already in LDS
+    gemm_store(acc, g, m0 + wm * 64, n0 + wn * 64, lane);
+    if (!more) break;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    tile = tnext, m0 = m0n, n0 = n0n, arow = arow_n, bsrc = bsrc_n;
+  }
+}
+
 // ---- small-tile variant for grids the 256 x 128 tile cannot fill (a few hundred rows, or a narrow N) ---------------
 // Same packed B, same split, same product and k-step order, so with ksplit == 1 every output has the bits of
 // gemm_bf16x6_kernel.  Tile: 64 x 128 outputs per workgroup of 4 waves (2 along M x 2 along N, 32 x 64 each = 2 x 4 MFMA
@@ -1430,6 +1599,21 @@ int vqa_gemm_bf16x6_tile(const float* A, long lda, const void* packed, const flo
   GemmArgs g{A, static_cast<const bf16x8*>(packed), bias, C, lda, ldc, M, N, K, gemm_vec_ok(C, ldc, bias)};
   const int grid = static_cast<int>((M + kWideBM - 1) / kWideBM * (N / kWideBN));
   gemm_bf16x6_wide_kernel<<<grid, kGemmThreads, 0, static_cast<hipStream_t>(stream)>>>(g);
+  return launch_status();
+}
+
+int vqa_gemm_bf16x6_persistent(const float* A, long lda, const void* packed, const float* bias, float* C, long ldc, long M,
+                               int N, int K, int workgroups, vqa_stream_t stream) {
+  clear_stale_error();
+  if (!A || !packed || !C) return VQA_ERR_NULL;
+  if (M < 0 || N <= 0 || K <= 0 || K % kGemmBK || N % kWideBN || lda < K || lda % 4 || ldc < N || workgroups < 1) return VQA_ERR_SHAPE;
+  if ((M + kWideBM - 1) / kWideBM * (N / kWideBN) > 0x7fffffffL) return VQA_ERR_SHAPE;
+  if (!aligned16(A) || !aligned16(packed) || !aligned4(C) || (bias && !aligned4(bias))) return VQA_ERR_ALIGN;
+  if (M == 0) return VQA_OK;
+  GemmArgs g{A, static_cast<const bf16x8*>(packed), bias, C, lda, ldc, M, N, K, gemm_vec_ok(C, ldc, bias)};
+  const int ntiles = static_cast<int>((M + kWideBM - 1) / kWideBM * (N / kWideBN));
+  const int grid = workgroups < ntiles ? workgroups : ntiles;          // every workgroup has a tile
+  gemm_bf16x6_persistent_kernel<<<grid, kGemmThreads, 0, static_cast<hipStream_t>(stream)>>>(g, ntiles);
   return launch_status();
 }
 

@@ -808,7 +808,9 @@ def gemm(a, packed, bias=None, out=None, tile=None, epilogue=None, aux=None, m_s
     """``out = a @ B (+ bias)`` on the bf16 matrix pipe (bf16x6, fp32-grade), B a ``PackedWeight``.  ``a``: fp32 (M, K)
     with unit column stride and a row stride that is a multiple of 4 floats.  ``tile``: the output tile of a workgroup,
     "large" (256 x 128) or "wide" (128 x 256: half the in-loop split work; N % 256 == 0, any other N runs "large");
-    both give the same bits.  None = what ``whitebox/_fused.py`` records for the shape (``gemm_tile``).
+    both give the same bits.  "persistent": ``gemm_persistent`` with one workgroup per compute unit (N % 256 == 0, no
+    epilogue, no m_split; the same bits).  None = what ``whitebox/_fused.py`` records for the shape (``gemm_tile``, and
+    ``gemm_persistent`` for a plain product that ``gemm_tail_split`` does not cut).
 
     ``m_split``: None, or the row from which the 128 x 128 tile takes over (``vqa_gemm_bf16x6_tail``: rows
     ``[0, m_split)`` on ``tile``, the rest on the half tile, the same bits); 0 <= m_split <= M, no epilogue.  None leaves
@@ -835,11 +837,15 @@ def gemm(a, packed, bias=None, out=None, tile=None, epilogue=None, aux=None, m_s
                 (M > 1 and aux.stride(0) < packed.N):
             raise ValueError("aux must be a ({}, {}) tensor with unit column stride, got {}".format(
                 M, packed.N, (tuple(aux.shape), aux.stride()) if isinstance(aux, torch.Tensor) else type(aux)))
+    if tile == "persistent":
+        if epilogue is not None or m_split is not None:
+            raise ValueError("tile 'persistent' goes with neither an epilogue nor m_split")
+        return gemm_persistent(a, packed, bias, out)
     if tile is None:
         from .whitebox import _fused
-        tile = _fused.gemm_tile(a.shape[0], packed.N, packed.K)
+        tile = _PolicyTile(_fused.gemm_tile(a.shape[0], packed.N, packed.K))
     if tile not in GEMM_TILES:
-        raise ValueError("tile must be one of {}, got {!r}".format(sorted(GEMM_TILES), tile))
+        raise ValueError("tile must be one of {}, got {!r}".format(sorted(GEMM_TILES) + ["persistent"], tile))
     if m_split is not None:
         if epilogue is not None:
             raise ValueError("m_split does not go with an epilogue")
@@ -851,6 +857,46 @@ def gemm(a, packed, bias=None, out=None, tile=None, epilogue=None, aux=None, m_s
     return _gemm_tiled(a, packed, bias, out, tile)
 
 
+class _PolicyTile(str):
+    """A tile name that ``gemm`` took from ``_fused.gemm_tile`` because its caller named none: equal to the plain name
+    everywhere, and the mark by which ``_gemm_tiled`` knows that ``_fused.gemm_persistent`` may replace the launch."""
+
+
+def gemm_persistent(a, packed, bias=None, out=None, workgroups=None):
+    """``gemm`` on the 128 x 256 tile as ONE launch of ``workgroups`` workgroups that each walk a fixed list of tiles
+    (``vqa_gemm_bf16x6_persistent``): a tile's last k-step stages the next tile's first, so only a workgroup's first tile
+    waits for its operands.  The bits of ``gemm(tile="wide")``.  N % 256 == 0.  ``workgroups``: None = one per compute
+    unit of ``a``'s device; at least 1, a value above the tile count ``ceil(M / 128) * (N / 256)`` is clamped to it.
+    ``out``: (M, N) with unit column stride and any row stride >= N."""
+    dev_f32(a, "a", contiguous=False)
+    if a.dim() != 2 or a.shape[1] != packed.K or a.stride(1) != 1 or a.stride(0) % 4:
+        raise ValueError("a must be (M, {}) with unit column stride and a row stride % 4 == 0, got shape {} strides {}"
+                         .format(packed.K, tuple(a.shape), a.stride()))
+    M, N = a.shape[0], packed.N
+    if N % 256:
+        raise ValueError("the persistent launch runs 128 x 256 tiles: N % 256 == 0, got N = {}".format(N))
+    if workgroups is not None and (isinstance(workgroups, bool) or not isinstance(workgroups, int) or workgroups < 1):
+        raise ValueError("workgroups must be None or an integer >= 1, got {!r}".format(workgroups))
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float32, device=a.device)
+    dev_f32(out, "out", contiguous=False)
+    if tuple(out.shape) != (M, N) or out.stride(1) != 1 or (M > 1 and out.stride(0) < N):
+        raise ValueError("out must be ({}, {}) with unit column stride, got {} strides {}".format(
+            M, N, tuple(out.shape), out.stride()))
+    if bias is not None:
+        dev_f32(bias, "bias"), _rows_ok("bias", bias, N)
+    same_device(a, packed.data, bias, out)
+    if M:
+        if workgroups is None:
+            from .whitebox import _fused
+            workgroups = _fused.device_cus(a.device)          # one query per device, shared with the tail plan
+        with _on(a):
+            check(lib().vqa_gemm_bf16x6_persistent(_p(a), a.stride(0), _p(packed.data), ptr(bias), _p(out),
+                                                   max(out.stride(0), N), M, N, packed.K, min(workgroups, 0x7fffffff),
+                                                   stream_for(a)), "vqa_gemm_bf16x6_persistent")
+    return out
+
+
 def gemm_half(a, packed, bias=None, out=None):
     """``gemm`` with the whole product on the 128 x 128 tile (``vqa_gemm_bf16x6_half``): the same bits."""
     return _gemm_rows(a, packed, bias, out, None, 0)
@@ -858,7 +904,15 @@ def gemm_half(a, packed, bias=None, out=None):
 
 def _gemm_tiled(a, packed, bias, out, tile):
     """``tile`` from row 0 to the cut ``whitebox/_fused.py`` names for the shape -- M, the whole product on
-    ``vqa_gemm_bf16x6_tile``, unless the shape is listed there or VQA_GEMM_TAIL=1 -- and the 128 x 128 tile behind it."""
+    ``vqa_gemm_bf16x6_tile``, unless the shape is listed there or VQA_GEMM_TAIL=1 -- and the 128 x 128 tile behind it.
+    An uncut product whose tile is the policy's (``_PolicyTile``) runs as ``gemm_persistent`` where
+    ``_fused.gemm_persistent`` says so."""
+    M = a.shape[0]
+    if isinstance(tile, _PolicyTile) and packed.N % 256 == 0 and M:
+        from .whitebox import _fused
+        # a product that the tail plan cuts stays cut: the persistent launch takes whole products only
+        if _fused.gemm_persistent(M, packed.N, packed.K) and _fused.gemm_tail_split(M, packed.N, packed.K, tile, a.device) >= M:
+            return gemm_persistent(a, packed, bias, out)
     return _gemm_rows(a, packed, bias, out, tile, None)
 
 

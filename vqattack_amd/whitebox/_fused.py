@@ -116,6 +116,30 @@ TAIL_POLICY = {}
 # for what was measured.
 GROUPED_POLICY = {}
 
+# The two large tiles run one workgroup per CU, so nothing covers what a tile pays once: while a workgroup waits for
+# its first operands the CU's matrix pipe is idle.  ops.gemm_persistent (vqa_gemm_bf16x6_persistent) launches one
+# workgroup per CU that walks a list of 128 x 256 tiles and stages a tile's first k-step in the last k-step of the tile
+# before it, with the bits of ops.gemm.  A shape class (N, K) -> (fewest rows, most rows), both inclusive, is listed only
+# by the rule of WIDE_POLICY: the persistent call's median in tools/gemm_bench.py beat the median of what this module
+# dispatches for the class without the entry (the qkv classes: the 256 x 128 kernel) by more than the larger
+# round-to-round spread of the two in BOTH records of the shape, and the benchmark with the entries in place beat the one
+# without (profiles/r17/README.md).  VQA_GEMM_PERSISTENT=1 runs every plain large-tile GEMM with N % 256 == 0 that
+# names no tile of its own as the persistent launch, =0 none; a VQA_GEMM that forces a kernel overrides both.  Plain ops.gemm calls only: the GELU, GELU' and LSE
+# epilogues, the tail cut and the grouped launch have no persistent form; a product that gemm_tail_split cuts stays cut.
+# Recorded at the benchmark's row counts (VLMO-base, batch 64; profiles/r17/README.md, two records): the fixed cost of a
+# tile is 5-8 us, of which the wait for the first operands -- all this launch removes -- is 0.9-1.1 us and the epilogue's
+# stores the rest.  Listed: the qkv classes (2304, 768) and (768, 2304) from 37312 to 39488 rows -- batch 64 with 6 to
+# 40 text tokens beside 577 image tokens; recorded at 37312, 37760, 37824, 37888, 38848 and 39488 rows, two records each,
+# all passing -- 1.08-1.10x of the 256 x 128 kernel they ran before, margins 2.6-18 times the larger spread (most of it is the 128 x 256 tile, which failed WIDE_POLICY's
+# rule on the 256 x 128 kernel's spread; the persistent launch is 1.03-1.04x and 1.00-1.01x of the wide kernel).  Not
+# listed: (3072, 768), 1.025-1.034x of the wide kernel in all eight records but inside the wide kernel's own max - min
+# in one of the two at 36928 rows; (768, 768), 1.02-1.04x, passing in one record of two; (768, 3072), no difference at
+# 36928 rows and 0.98x at 35264 (96 k-steps per tile: the wait is 0.5 % of a tile).  With the two entries the benchmark
+# read 16.36-16.38 examples/s against the previous commit's 16.11-16.15 in three alternating rounds (1.015x, outputs
+# bitwise equal).  ALBEF-base was not measured.
+_QKV_ROWS = (37312, 39488)
+PERSISTENT_POLICY = {(2304, 768): _QKV_ROWS, (768, 2304): _QKV_ROWS}
+
 _CUS = {}
 
 
@@ -136,8 +160,27 @@ def gemm_tile(rows, n, k):
     return "wide" if mode == "" and lo <= rows <= hi else "large"
 
 
+def gemm_persistent(rows, n, k):
+    """Whether ops.gemm runs (rows, n, k), where the caller names no tile, as the persistent launch of 128 x 256 tiles."""
+    if n % 256 or _mode() != "":          # VQA_GEMM=large / wide / small force a kernel: the switch and the table stand back
+        return False
+    switch = os.environ.get("VQA_GEMM_PERSISTENT", "")
+    if switch in ("0", "1"):
+        return switch == "1"
+    lo, hi = PERSISTENT_POLICY.get((n, k), (1, 0))
+    return lo <= rows <= hi
+
+
 def _kernel_gemms():
     return _mode() != "library"
+
+
+def device_cus(device):
+    """Compute units of ``device``, asked for once per device (the tail plan and the persistent launch's grid)."""
+    dev = torch.device(device).index or 0
+    if dev not in _CUS:
+        _CUS[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
+    return _CUS[dev]
 
 
 def gemm_tail_split(rows, n, k, tile, device):
@@ -151,14 +194,7 @@ def gemm_tail_split(rows, n, k, tile, device):
         if switch != "" or not lo <= rows <= hi:
             return rows
     pinned = os.environ.get("VQA_GEMM_TAIL_CUS")
-    if pinned:
-        cus = int(pinned)
-    else:
-        dev = torch.device(device).index or 0
-        if dev not in _CUS:
-            _CUS[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
-        cus = _CUS[dev]
-    return ops.gemm_tail_plan(rows, n, tile, cus)
+    return ops.gemm_tail_plan(rows, n, tile, int(pinned) if pinned else device_cus(device))
 
 
 def _small_gemm(rows, n, k):
