@@ -51,6 +51,8 @@ def parse(argv=None):
     ap.add_argument("--checkpoint_vqa", default="", help="VQA fine-tuned checkpoint -> victim (adv_attack.py:96)")
     ap.add_argument("--sim_threshold", default=0.95, type=float,
                     help="sentence-similarity floor of a substitution (adv_attack.py:303)")
+    ap.add_argument("--decay_factor", default=None, type=float,
+                    help="MI-FGSM momentum decay of the image attack (Dong et al. 2017); absent: plain PGD")
     ap.add_argument("--mlm_checkpoint", default="", help="BertForMaskedLM state dict -> candidate proposer (adv_attack.py:110)")
     ap.add_argument("--answer_list", default=None,
                     help="ALBEF answer_list json (configs: answer_list): the victim ranks it and acc_vqa compares answer "
@@ -122,7 +124,8 @@ def main():
                     rank, world, joint=not args.image_only, save_dir=out_dir, seed=args.seed,
                     max_words=4 if args.tiny else 12, dual_every=args.dual_every, mixed=args.mixed,
                     force_collective=dist.is_initialized(), source=source, mlm_logits_fn=proposer, banned_ids=banned,
-                    config=AttackConfig(sim_threshold=args.sim_threshold), scoring=scoring)
+                    config=AttackConfig(sim_threshold=args.sim_threshold, decay_factor=args.decay_factor),
+                    scoring=scoring)
     finish(rank, world, res, os.path.join(args.output_dir, "adv_txt.json") if args.output_dir else None,
            os.path.join(args.output_dir, "adv_txt_dict_albef.txt") if args.output_dir and scoring else None)
 

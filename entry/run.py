@@ -37,7 +37,8 @@ NAMED = {
 DEFAULTS = dict(arch="vlmo_base", image_size=384, max_text_len=40, per_gpu_batchsize=64, seed=1, test_only=True,
                 n_samples=128, image_only=False, attack_dir="", dual_every=0, mixed=False, questions="", image_root="",
                 vocab_file="", tables_dir="", pretrain_path="", load_path="", mlm_checkpoint="", sim_threshold=0.95,
-                id2answer="")
+                id2answer="", decay_factor=None)
+OPTIONAL_FLOATS = ("decay_factor",)     # absent = off (None); MI-FGSM momentum of the image attack when given
 
 
 def parse(argv):
@@ -50,6 +51,9 @@ def parse(argv):
             if k not in cfg:
                 raise SystemExit("unknown config key '{}'".format(k))
             old = cfg[k]
+            if k in OPTIONAL_FLOATS:
+                cfg[k] = float(v)
+                continue
             cfg[k] = (v.lower() in ("1", "true", "yes")) if isinstance(old, bool) else type(old)(v)
         elif tok in NAMED:
             cfg.update(NAMED[tok])
@@ -103,7 +107,8 @@ def main():
                     save_dir=cfg["attack_dir"] or None, seed=cfg["seed"],
                     max_words=4 if cfg["arch"] == "vlmo_tiny" else 12, dual_every=cfg["dual_every"], mixed=cfg["mixed"],
                     force_collective=dist.is_initialized(), source=source, mlm_logits_fn=proposer, banned_ids=banned,
-                    config=AttackConfig(sim_threshold=cfg["sim_threshold"]),      # adv_attack.py:303: 0.95
+                    config=AttackConfig(sim_threshold=cfg["sim_threshold"],       # adv_attack.py:303: 0.95
+                                        decay_factor=cfg["decay_factor"]),
                     scoring=scoring)
     # adversarial images <qid>.pt and the adversarial-text json go to attack_dir (vlmo_module.py:166-167,2059-2062,2095-2097)
     finish(rank, world, res, os.path.join(cfg["attack_dir"], "adv_txt.json") if cfg["attack_dir"] else None,

@@ -62,7 +62,9 @@ const char* vqa_error_string(int code);
  *   option 9: dQ-from-dS^T attention kernel, 1 = dS^T tile staged through LDS with 16-byte loads (default), 0 = direct
  *             dword loads into the MFMA operand (round 3's form)
  *   option 10: block-glue kernels, bit0 = non-temporal loads of the activation streams, bit1 = non-temporal stores of GELU
- *             results larger than the Infinity Cache (default 3) */
+ *             results larger than the Infinity Cache (default 3)
+ *   option 13: momentum kernels: 16-byte tiles in flight per lane and stream (2 or 4), + 8 = a momentum tensor larger
+ *             than the Infinity Cache is loaded and stored non-temporally (default 2 + 8 = 10) */
 int vqa_set_option(int option, int value);
 #endif
 
@@ -148,6 +150,31 @@ int vqa_l1_fgm(const float* x, const float* g, const float* amax, const float* t
  */
 int vqa_scale_per_sample(const float* t, const float* stat, const float* stat2, float* out, int batch,
                          size_t n_per_sample, float eps, int kind, int* flag, vqa_stream_t stream);
+
+/* ---------------------------------------------------------------- momentum (MI-FGSM, Dong et al. 2017)
+ * The reference tree ships the method for TensorFlow only (cleverhans/tf2/attacks/momentum_iterative_method.py); these
+ * entry points give it to the torch operators.  Per gradient evaluation and sample b of n elements (:88-95 there):
+ *   den_b = max(1e-12, sumabs[b] / (float)n)        grad / max(1e-12, reduce_mean(|grad|))     :91-94
+ *   m    <- decay * m + g / den_b                   momentum = decay_factor * momentum + grad  :95
+ * in fp32 with one rounding per operation (multiply, IEEE divide, add; no contraction).  The image update that follows
+ * (:97-103) is this library's own chain with m in place of g.
+ */
+
+/* out[b] = sum_i |g[b,i]|: the two-stage reduction of vqa_sumsq_per_sample (same chunks, same workspace size), no
+ * atomics, bitwise reproducible.  4 B/element. */
+int vqa_sumabs_per_sample(const float* g, float* out, int batch, size_t n_per_sample, float* ws, vqa_stream_t stream);
+
+/* m <- decay * m + g / den_b, in place.  The L2 loop runs it in front of vqa_l2_fgm(x, m, ...).  12 B/element. */
+int vqa_momentum_accumulate(const float* g, const float* sumabs, float* m, int batch, size_t n_per_sample, float decay,
+                            vqa_stream_t stream);
+
+/* The accumulate above and the L-infinity update in ONE pass: m is updated in place, then out = vqa_linf_step(x, m, x0)
+ * -- or, for x0 == NULL, out = vqa_linf_fgm(x, m) (no projection: the first sub-step of the dual-loss loop) -- bit for
+ * bit what the two launches give.  24 B/element (reads x, g, x0, m; writes out, m), 20 without x0.  `out` may alias `x`;
+ * mode / flag as in vqa_linf_step. */
+int vqa_linf_momentum_step(const float* x, const float* g, const float* sumabs, const float* x0, float* m, float* out,
+                           int batch, size_t n_per_sample, float decay, float eps_iter, float eps, float cmin,
+                           float cmax, unsigned mode, int* flag, vqa_stream_t stream);
 
 /* ---------------------------------------------------------------- cross-modal loss reduction
  * Rows of D contiguous floats, addressed as row(o, i) = base + o*stride0 + i*stride1 (strides in ELEMENTS) for

@@ -107,6 +107,35 @@ def linf_section(x, x0, g, eta, out, n):
     report("vqa_linf_init (eta)", 12 * n, timeit(lambda: ops.linf_init(x0, eta, 0.125, -1, 1, out=out)))
     report("vqa_linf_init (zero)", 8 * n, timeit(lambda: ops.linf_init(x0, None, 0.125, -1, 1, out=out)))
     report("vqa_linf_project", 12 * n, timeit(lambda: ops.linf_project(x, x0, 0.125, -1, 1, out=out)))
+    # momentum (MI-FGSM): the |grad| reduction, the stand-alone accumulate and the fused step with / without x0.  The
+    # per-sample sums are computed once, so every line times ONE kernel; decay 0.9 keeps the momentum bounded over the reps
+    report("vqa_l2_fgm (update only, sums given)", 12 * n, _l2_fgm_only(x, g, out), "yardstick: a (chunks, batch) grid")
+    sums, ws, m = ops.sumabs_per_sample(g), ops.reduce_workspace(g), torch.zeros_like(g)
+    report("vqa_sumabs_per_sample", 4 * n, timeit(lambda: ops.sumabs_per_sample(g, out=sums, ws=ws)),
+           "two-stage deterministic")
+    # option 13 of the tuning build: tiles in flight (2 or 4) + 8 = non-temporal momentum above 256 MB; shipped: 2 + 8
+    for knob in (10, 2, 12, 4):
+        tag = " [{} tiles in flight, m {}]".format(knob & 7, "nt above 256 MB" if knob & 8 else "plain") \
+            if _hip.set_option(13, knob) else ""
+        report("vqa_momentum_accumulate" + tag, 12 * n, timeit(lambda: ops.momentum_accumulate(g, m, 0.9, sumabs=sums)))
+        report("vqa_linf_momentum_step" + tag, 24 * n,
+               timeit(lambda: ops.linf_momentum_step(x, g, x0, m, 0.9, 0.01, 0.125, -1, 1, out=out, sumabs=sums)))
+        report("vqa_linf_momentum_step in place" + tag, 24 * n,
+               timeit(lambda: ops.linf_momentum_step(out, g, x0, m, 0.9, 0.01, 0.125, -1, 1, out=out, sumabs=sums)))
+        report("vqa_linf_momentum_step without x0" + tag, 20 * n,
+               timeit(lambda: ops.linf_momentum_step(x, g, None, m, 0.9, 0.01, 0.125, -1, 1, out=out, sumabs=sums)))
+        if not tag:
+            break
+    _hip.set_option(13, 10)
+
+
+def _l2_fgm_only(x, g, out):
+    """vqa_l2_fgm without its reduction (ops.l2_fgm runs both): the per-sample update kernel on its own."""
+    ss = ops.sumsq_per_sample(g)
+    batch, n_per = x.shape[0], x.numel() // x.shape[0]
+    lib, p, stream = _hip.lib(), _hip.ptr, _hip.stream_for(x)
+    return timeit(lambda: _hip.check(lib.vqa_l2_fgm(p(x), p(g), p(ss), p(out), batch, n_per, 0.5, -1.0, 1.0, 1, None,
+                                                    stream), "vqa_l2_fgm"))
 
 
 def norm_section(x, x0, g, out, n):

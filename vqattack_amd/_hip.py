@@ -48,6 +48,9 @@ SIGNATURES = {
     "vqa_l2_project": (_i, [_p, _p, _p, _p, _i, _sz, _f, _f, _f, _u, _p]),
     "vqa_l1_fgm": (_i, [_p, _p, _p, _p, _p, _i, _sz, _f, _f, _f, _u, _p, _p]),
     "vqa_scale_per_sample": (_i, [_p, _p, _p, _p, _i, _sz, _f, _i, _p, _p]),
+    "vqa_sumabs_per_sample": (_i, [_p, _p, _i, _sz, _p, _p]),
+    "vqa_momentum_accumulate": (_i, [_p, _p, _p, _i, _sz, _f, _p]),
+    "vqa_linf_momentum_step": (_i, [_p, _p, _p, _p, _p, _p, _i, _sz, _f, _f, _f, _f, _f, _u, _p, _p]),
     "vqa_neg_cos_partials": (_i, []),
     "vqa_neg_cos_rows": (_i, [_p, _p, _p, _p, _p, _l, _l, _l, _i, _l, _l, _l, _l, _l, _l, _f, _f, _p, _i, _p]),
     "vqa_neg_cos_max_layers": (_i, []),

@@ -17,6 +17,7 @@ Attack hyper-parameters default to the reference's hard-coded literals (adv_atta
 L-inf, clip [-1, 1]).
 """
 from dataclasses import dataclass, field
+from typing import Optional
 
 import numpy as np
 import torch
@@ -42,6 +43,13 @@ class AttackConfig:
     use_graph: bool = False            # replay PGD iterations from a hipGraph (small, launch-bound batches)
     patch_layout: bool = False         # keep the PGD state patch-major (layout.py); measured neutral end to end, see DESIGN
     live_mlm_rows: bool = True         # dual loss: MLM head + cross entropy at the live label rows only (False: dense B x L)
+    decay_factor: Optional[float] = None   # not None: MI-FGSM, one momentum buffer per attack (attacks.projected_gradient_descent)
+
+    def __post_init__(self):
+        attacks._validate_decay(self.decay_factor)
+        if self.decay_factor is not None and self.patch_layout:
+            # the per-sample sum of |grad| is folded in memory order: a patch-major image would round it differently
+            raise ValueError("decay_factor and patch_layout=True cannot be combined")
 
 
 @dataclass
@@ -101,10 +109,16 @@ class BatchedVQAttack:
             return [mlm_labels, targets[0], targets[1]]
         return [mlm_labels, targets[1], targets[2]]
 
-    def _pgd_block(self, adv, clean, targets, steps, time, dual, mlm_labels, init_eta=None):
+    def _new_momentum(self, images):
+        """The attack's momentum buffer (zeros, one per attack_batch / attack_mixed call), None without a decay factor."""
+        if self.cfg.decay_factor is None:
+            return None
+        return torch.zeros_like(images, dtype=torch.float32, memory_format=torch.contiguous_format)
+
+    def _pgd_block(self, adv, clean, targets, steps, time, dual, mlm_labels, init_eta=None, momentum=None):
         c = self.cfg
         common = dict(clip_min=c.clip_min, clip_max=c.clip_max, time=time, ori_x=clean,
-                      sanity_checks=c.sanity_checks, init_eta=init_eta)
+                      sanity_checks=c.sanity_checks, init_eta=init_eta, decay_factor=c.decay_factor, momentum=momentum)
         a = self.adapters
         if not dual:
             return self.pgd(a.pgd_attack, adv, c.eps, c.eps_iter, steps, c.norm, y=self._y_feature(targets), ls=1,
@@ -176,12 +190,14 @@ class BatchedVQAttack:
             else:
                 a.set_mlm_rows(None)
         targets = a.gen_ori_feats(images)
+        mom = self._new_momentum(images)         # carried through every PGD block and every probe of this attack
         res = BatchResult(adv_images=adv, adv_text_ids=adv_ids)
         first_time = 0 if c.random_start else 1
         rounds = []
         if not blocks:
             with torch.enable_grad():
-                adv, losses = self._pgd_block(adv, images, targets, c.budget, first_time, dual, mlm_labels, init_eta)
+                adv, losses = self._pgd_block(adv, images, targets, c.budget, first_time, dual, mlm_labels, init_eta,
+                                              momentum=mom)
             res.loss_lists.append(losses)
             res.gradient_steps = c.budget
         else:
@@ -202,7 +218,7 @@ class BatchedVQAttack:
                 a.set_text(adv_ids, text_masks, text_ids_mlm=mlm_ids, text_mask_mlm=mlm_mask)
                 with torch.enable_grad():
                     adv, losses = self._pgd_block(adv, images, targets, steps, first_time if bi == 0 else 1, dual,
-                                                  mlm_labels, init_eta if bi == 0 else None)
+                                                  mlm_labels, init_eta if bi == 0 else None, momentum=mom)
                 res.loss_lists.append(losses)
                 res.gradient_steps += steps
                 if bi == len(blocks) - 1:
@@ -211,7 +227,8 @@ class BatchedVQAttack:
                     adv, text_grad = self.pgd_vl(a.pgd_attack_vl, [adv, adv_emb], c.eps, c.eps_iter,
                                                  1, c.norm, clip_min=c.clip_min, clip_max=c.clip_max,
                                                  y=self._y_feature(targets), time=1, ori_x=images, ls=1,
-                                                 attack_mask=positions, sanity_checks=c.sanity_checks)
+                                                 attack_mask=positions, sanity_checks=c.sanity_checks,
+                                                 decay_factor=c.decay_factor, momentum=mom)
                 res.gradient_steps += 1
                 if plan is not None:
                     scores = text_update.score_plan(self.tables, e_ori, text_grad, plan)
@@ -346,6 +363,7 @@ class BatchedVQAttack:
         if eta is None and c.random_start:
             eta = torch.empty_like(images, memory_format=torch.contiguous_format).uniform_(-c.eps, c.eps)
         cur = ops.linf_init(images.contiguous(), eta, c.eps, c.clip_min, c.clip_max, flag=flag)
+        mom = self._new_momentum(images)          # in the sorted order of `images`; only the active prefix is updated
         losses = torch.zeros(max(total), dtype=torch.float32, device=dev)
         ws = ops.Workspace()
         res = BatchResult(adv_images=cur, adv_text_ids=adv_ids)
@@ -404,7 +422,7 @@ class BatchedVQAttack:
             else:
                 attacks._loss_and_grad(a.pgd_attack_vl, [leaf_img, leaf_txt], [leaf_img, leaf_txt], list(y), 1,
                                        self.flavor, False, slot, vl=True, ws=ws)
-            self._update_runs(cur, attacks._grad_of(leaf_img), images, now)
+            self._update_runs(cur, attacks._grad_of(leaf_img), images, now, mom)
             firing = [s for s in range(n_act) if kinds[s][t][1]]
             if firing:
                 sub = plan.restricted_to(firing)
@@ -465,16 +483,21 @@ class BatchedVQAttack:
                 labels[s, j, :len(row)] = torch.tensor(row)
         return tasks, text_ids, text_masks, attackable, mlm_ids, mlm_mask, (labels[:, 0] if k == 1 else labels).to(dev)
 
-    def _update_runs(self, cur, grad, images, now):
+    def _update_runs(self, cur, grad, images, now, mom=None):
         """The fused image update of one global step, in place on the active prefix of ``cur``: one launch per run of
         consecutive samples of one kind -- ``vqa_linf_fgm`` for ``N`` (first half of a dual iteration: no projection in
-        between, projected_gradient_descent.py:155-188), ``vqa_linf_step`` otherwise.  Finished samples stay untouched."""
+        between, projected_gradient_descent.py:155-188), ``vqa_linf_step`` otherwise.  Finished samples stay untouched.
+        ``mom`` (MI-FGSM): ``vqa_linf_momentum_step`` instead, without ``x0`` for ``N`` runs; a run accumulates into its own
+        rows of the momentum, so a finished sample's momentum stays as it was."""
         c, lo, n_act = self.cfg, 0, len(now)
         while lo < n_act:
             hi = lo + 1
             while hi < n_act and (now[hi] == "N") == (now[lo] == "N"):
                 hi += 1
-            if now[lo] == "N":
+            if mom is not None:
+                ops.linf_momentum_step(cur[lo:hi], grad[lo:hi], None if now[lo] == "N" else images[lo:hi], mom[lo:hi],
+                                       c.decay_factor, c.eps_iter, c.eps, c.clip_min, c.clip_max, out=cur[lo:hi])
+            elif now[lo] == "N":
                 ops.linf_fgm(cur[lo:hi], grad[lo:hi], c.eps_iter, c.clip_min, c.clip_max, out=cur[lo:hi])
             else:
                 ops.linf_step(cur[lo:hi], grad[lo:hi], images[lo:hi], c.eps_iter, c.eps, c.clip_min, c.clip_max,

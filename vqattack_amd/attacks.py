@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._hip import VQA_FLAG_BAD_LABEL, VQA_FLAG_DEGENERATE, VQA_FLAG_RANGE, HipExtensionError
+from ._hip import VQA_FLAG_BAD_LABEL, VQA_FLAG_DEGENERATE, VQA_FLAG_RANGE, HipExtensionError, dev_f32
 from .features import LayerFeatures, layer_pairs
 
 ALBEF = "albef"
@@ -70,6 +70,17 @@ def _validate_pgd(norm, eps, eps_iter, clip_min, clip_max):
         raise ValueError("clip_min must be less than or equal to clip_max, got clip_min={} and clip_max={}".format(
             clip_min, clip_max))
     return False
+
+
+def _validate_decay(decay_factor):
+    """None (momentum off) or the decay as a float; raised before any tensor is looked at, like the other arguments."""
+    if decay_factor is None:
+        return None
+    decay = float(decay_factor)
+    if not (0.0 <= decay < float("inf")):
+        raise ValueError("decay_factor must be a finite number greater than or equal to 0, got {} instead".format(
+            decay_factor))
+    return decay
 
 
 def _two_sided(clip_min, clip_max):
@@ -303,9 +314,36 @@ def _mixed_loss_and_grad(model_fn, leaves, model_in, y, flavor, slot, mlm_labels
 
 
 # ----------------------------------------------------------------------------------------- image updates
-def _fgm_update(x, grad, eps, norm, clip_min, clip_max, flag=None, out=None, check_range=True):
+class _Momentum:
+    """The MI-FGSM state of one operator call: the momentum tensor (the caller's, updated in place, or zeros), the decay
+    and -- allocated once, so that a captured iteration finds them at static addresses -- one |grad| sum per sample and
+    the reduction's workspace."""
+
+    def __init__(self, decay, like, momentum=None):
+        if momentum is None:
+            momentum = torch.zeros_like(like, memory_format=torch.contiguous_format)
+        else:
+            dev_f32(momentum, "momentum")
+            if momentum.shape != like.shape or momentum.device != like.device:
+                raise ValueError("momentum has shape {} on {}, expected {} on {}".format(
+                    tuple(momentum.shape), momentum.device, tuple(like.shape), like.device))
+        self.decay, self.m = decay, momentum
+        self.sumabs = torch.empty(like.shape[0] if like.dim() > 0 else 1, dtype=torch.float32, device=like.device)
+        self.ws = ops.reduce_workspace(like)
+
+    def sums(self, grad):
+        return ops.sumabs_per_sample(grad, out=self.sumabs, ws=self.ws)
+
+
+def _fgm_update(x, grad, eps, norm, clip_min, clip_max, flag=None, out=None, check_range=True, mom=None):
     """``flag``: range violations of ``x`` (``check_range``) and, for the L2 / L1 updates, the degenerate-gradient bit
-    that stands for the self-check asserts of the reference's ``optimize_linear`` (utils.py:101-104, :110-116)."""
+    that stands for the self-check asserts of the reference's ``optimize_linear`` (utils.py:101-104, :110-116).
+    ``mom``: accumulate ``grad`` into the momentum first and step along the momentum instead."""
+    if mom is not None and norm == np.inf:
+        return ops.linf_momentum_step(x, grad, None, mom.m, mom.decay, eps, 0.0, clip_min, clip_max,
+                                      flag=flag if check_range else None, out=out, sumabs=mom.sums(grad))
+    if mom is not None:
+        grad = ops.momentum_accumulate(grad, mom.m, mom.decay, sumabs=mom.sums(grad))
     if norm == np.inf:
         return ops.linf_fgm(x, grad, eps, clip_min, clip_max, flag=flag if check_range else None, out=out)
     if norm == 2:
@@ -313,7 +351,12 @@ def _fgm_update(x, grad, eps, norm, clip_min, clip_max, flag=None, out=None, che
     return ops.l1_fgm(x, grad, eps, clip_min, clip_max, flag=flag, out=out, check_range=check_range)
 
 
-def _fgm_then_project(x, grad, x0, eps_iter, eps, norm, clip_min, clip_max, out, flag=None):
+def _fgm_then_project(x, grad, x0, eps_iter, eps, norm, clip_min, clip_max, out, flag=None, mom=None):
+    if mom is not None and norm == np.inf:
+        return ops.linf_momentum_step(x, grad, x0, mom.m, mom.decay, eps_iter, eps, clip_min, clip_max, out=out,
+                                      sumabs=mom.sums(grad))
+    if mom is not None:
+        grad = ops.momentum_accumulate(grad, mom.m, mom.decay, sumabs=mom.sums(grad))
     if norm == np.inf:
         return ops.linf_step(x, grad, x0, eps_iter, eps, clip_min, clip_max, out=out)
     mid = ops.l2_fgm(x, grad, eps_iter, clip_min, clip_max, flag=flag, check_range=False)
@@ -422,7 +465,8 @@ def _finish(flag, eps, eps_iter, norm, clip_min, clip_max, sanity_checks):
         assert np.all(ok)
 
 
-def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, clip_min, clip_max, nb_iter, loss_buf):
+def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, clip_min, clip_max, nb_iter, loss_buf,
+                       mom=None):
     """``nb_iter`` feature-loss L-inf iterations with iterations 1.. replayed from ONE captured hipGraph.
 
     For the launch-bound regime (the reference's own batch 1: ~10^3 kernels of a few microseconds per iteration):
@@ -432,13 +476,16 @@ def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, cl
     iteration is the 4-byte copy of the loss word into its slot of the loss buffer.
     ``model_fn`` must be capturable: no host<->device copies or host RNG inside (ALBEF's per-forward token masking
     is not; use ``mlm_probability=0`` or eager mode there).
+    ``mom``: the |grad| reduction and the fused momentum step take the place of the step inside the captured iteration;
+    the momentum, the per-sample sums and the reduction's workspace were allocated before capture.
     """
     word = torch.zeros(1, dtype=torch.float32, device=cur.device)
 
     def iteration():
         leaf = cur.detach().requires_grad_(True)
         _loss_and_grad(model_fn, [leaf], leaf, y, 1, flavor, targeted, _LossSlot(word, 0))
-        ops.linf_step(cur, _grad_of(leaf), x0, eps_iter, eps, clip_min, clip_max, out=cur)   # in place: static address
+        _fgm_then_project(cur, _grad_of(leaf), x0, eps_iter, eps, np.inf, clip_min, clip_max, cur,   # in place: static
+                          mom=mom)                                                                    # address
 
     main = torch.cuda.current_stream(cur.device)
     side = torch.cuda.Stream(device=cur.device)
@@ -460,7 +507,7 @@ def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, cl
 def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_min=None, clip_max=None, y=None,
                                ori_x=None, time=None, targeted=False, rand_init=True, rand_minmax=None,
                                sanity_checks=True, ls=None, *, flavor=ALBEF, init_eta=None, graph=None,
-                               per_sample=False):
+                               per_sample=False, decay_factor=None, momentum=None):
     """PGD over a frozen white box; returns ``(adv_x, loss_list)``, bare ``x`` when eps or eps_iter is 0.
 
     ``ls == 1``: feature loss, ``model_fn`` a callable.  Otherwise the dual-loss loop: ``model_fn = [feature_fn,
@@ -475,10 +522,18 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
     unset are then replayed,
     every other call (dual loss, L1 / L2, one-sided clipping) runs eagerly as before.  The closure must be capturable
     (no host read such as ``.item()`` inside it).
+    ``decay_factor`` (extension, keyword-only): not None turns every update into MI-FGSM's (Dong et al. 2017; the
+    reference tree has it for TensorFlow only, tf2/attacks/momentum_iterative_method.py:88-95): each gradient evaluation
+    g does ``m <- decay_factor * m + g / max(1e-12, mean|g|)`` per sample and the update steps along ``m``.  The dual
+    loop accumulates twice per iteration into the same ``m`` (feature gradient, then MLM gradient).  ``momentum``: the
+    fp32 device tensor of ``x``'s shape that holds ``m``; it is updated in place, so a driver can carry it over several
+    calls (None: zeros for this call).  With ``decay_factor=None`` (default) nothing changes and ``momentum`` is ignored.
     Reference: A projected_gradient_descent.py:10-199, V :10-196.
     """
     _check_flavor(flavor)
-    if _validate_pgd(norm, eps, eps_iter, clip_min, clip_max):
+    unchanged = _validate_pgd(norm, eps, eps_iter, clip_min, clip_max)
+    decay = _validate_decay(decay_factor)
+    if unchanged:
         return x
     xin = _as_image(x)
     has_clip = clip_min is not None or clip_max is not None
@@ -494,6 +549,7 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
     dual = ls != 1
     loss_buf = torch.zeros(max(nb_iter, 1) * (2 if dual else 1), dtype=torch.float32, device=xin.device)
     n_loss = 0
+    mom = None if decay is None else _Momentum(decay, xin, momentum)
     ws = ops.Workspace()       # loss-gradient / CE scratch buffers live for the whole call, not per iteration
     bad_flag = flag if flag is not None else (
         ops.new_flag(xin.device) if ((dual and sanity_checks) or norm != np.inf) else None)
@@ -504,7 +560,7 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
             raise ValueError("graph=True supports the feature-loss (ls == 1) L-inf loop only")
         _two_sided(clip_min, clip_max)
         adv = _graphed_linf_loop(model_fn, adv, x0, y, flavor, targeted, eps_iter, eps, clip_min, clip_max, nb_iter,
-                                 loss_buf)
+                                 loss_buf, mom=mom)
         n_loss, nb_iter = nb_iter, 0
     for _ in range(nb_iter):
         if not dual:
@@ -514,7 +570,7 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
             n_loss += 1
             _two_sided(clip_min, clip_max)
             adv = _fgm_then_project(adv, _grad_of(leaf), x0, eps_iter, eps, norm, clip_min, clip_max, buf[1 - cur],
-                                    flag=bad_flag)
+                                    flag=bad_flag, mom=mom)
         else:
             if flavor == ALBEF:      # A :163,177-181 slices y; V :162,175 passes it whole
                 y_feat, y_mlm, extra = [y[1], y[2]], [y[0]], dict(bkp=model_fn[0], bkp_y=[y[1], y[2]])
@@ -526,13 +582,13 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
             n_loss += 1
             _two_sided(clip_min, clip_max)
             mid = _fgm_update(adv, _grad_of(leaf), eps_iter, norm, clip_min, clip_max, out=buf[1 - cur], flag=bad_flag,
-                              check_range=False)
+                              check_range=False, mom=mom)
             leaf = mid.detach().requires_grad_(True)
             _loss_and_grad(model_fn[1], [leaf], leaf, y_mlm, 0, flavor, targeted, _LossSlot(loss_buf, n_loss), ws=ws,
                            flag=bad_flag, per_sample=per_sample, **extra)
             n_loss += 1
             adv = _fgm_then_project(mid, _grad_of(leaf), x0, eps_iter, eps, norm, clip_min, clip_max, buf[cur],
-                                    flag=bad_flag)
+                                    flag=bad_flag, mom=mom)
             cur = 1 - cur            # result sits in buf[cur] again after the flip below
         cur = 1 - cur
         del leaf
@@ -543,12 +599,17 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
 
 def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, clip_min=None, clip_max=None, y=None,
                                   ori_x=None, time=None, targeted=False, rand_init=True, rand_minmax=None,
-                                  sanity_checks=True, ls=None, attack_mask=None, *, flavor=ALBEF, init_eta=None):
+                                  sanity_checks=True, ls=None, attack_mask=None, *, flavor=ALBEF, init_eta=None,
+                                  decay_factor=None, momentum=None):
     """PGD on ``x = [image, text_embeds]`` (only the image moves); returns ``(adv_image, text_embed_gradient)`` of
     the last iteration.  Only ``ls == 1`` is supported (``ValueError`` otherwise), as in the reference.
+    ``decay_factor`` / ``momentum`` (extensions, keyword-only): MI-FGSM on the image, as in
+    ``projected_gradient_descent``; ``momentum`` has the image's shape.
     Reference: A projected_gradient_descent_vl.py:10-168, V :10-164."""
     _check_flavor(flavor)
-    if _validate_pgd(norm, eps, eps_iter, clip_min, clip_max):
+    unchanged = _validate_pgd(norm, eps, eps_iter, clip_min, clip_max)
+    decay = _validate_decay(decay_factor)
+    if unchanged:
         return x
     img = _as_image(x[0], "x[0]")
     emb = _as_image(x[1], "x[1]")
@@ -565,6 +626,7 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
     text_grad = None
     loss_buf = torch.zeros(max(nb_iter, 1), dtype=torch.float32, device=img.device)
     ws = ops.Workspace()
+    mom = None if decay is None else _Momentum(decay, img, momentum)
     if attack_mask is not None and not isinstance(attack_mask, ops.RowIndex):   # validated + uploaded once per call
         attack_mask = ops.RowIndex(attack_mask, emb.shape[1], emb.device)
     for it in range(nb_iter):
@@ -575,8 +637,29 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
         text_grad = ops.gather_rows(_grad_of(leaf_txt), attack_mask)
         _two_sided(clip_min, clip_max)
         adv = _fgm_then_project(adv, _grad_of(leaf_img), x0, eps_iter, eps, norm, clip_min, clip_max, buf[1 - cur],
-                                flag=flag)
+                                flag=flag, mom=mom)
         cur = 1 - cur
         del leaf_img, leaf_txt
     _finish(flag, eps, eps_iter, norm, clip_min, clip_max, sanity_checks)
     return adv, text_grad
+
+
+# ----------------------------------------------------------------------------------------- MI-FGSM
+def momentum_iterative_method(model_fn, x, eps, eps_iter, nb_iter, norm, clip_min=None, clip_max=None, y=None,
+                              ori_x=None, targeted=False, decay_factor=1.0, sanity_checks=True, ls=1, *, flavor=ALBEF,
+                              graph=None, momentum=None):
+    """The momentum iterative method (Dong et al. 2017) on this project's losses; returns ``(adv_x, loss_list)`` like
+    ``projected_gradient_descent``, so a driver can swap one for the other.
+
+    The reference tree ships the method for TensorFlow only (tf2/attacks/momentum_iterative_method.py) and never ported
+    it to the torch operators its drivers call.  As there, the loop starts at ``x`` itself (no random start, :80-81),
+    ``norm == 1`` is refused first (:54-60) and every iteration normalises the gradient by its per-sample mean absolute
+    value, adds it to ``decay_factor`` times the momentum (:88-95) and steps along the momentum (:97-103).  ``ori_x``
+    (centre of the eps-ball) defaults to ``x``; ``ls``, ``flavor``, ``graph`` and ``momentum`` as in
+    ``projected_gradient_descent``, which runs the loop."""
+    if norm != 1 and decay_factor is None:
+        raise ValueError("decay_factor must be a number (use projected_gradient_descent for the attack without momentum)")
+    return projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_min=clip_min, clip_max=clip_max,
+                                      y=y, ori_x=x if ori_x is None else ori_x, time=None, targeted=targeted,
+                                      sanity_checks=sanity_checks, ls=ls, flavor=flavor, graph=graph,
+                                      decay_factor=decay_factor, momentum=momentum)

@@ -35,6 +35,32 @@ __device__ __forceinline__ bool out_of_range(float v, float lo, float hi) {
   return !(v >= lo) || !(v <= hi);   // true for NaN, like torch.all(ge) / torch.all(le) failing
 }
 
+// The two L-infinity image updates that more than one file launches: linf.hip streams them over the gradient, the
+// momentum step of lnorm.hip over the accumulated momentum -- one body, so the two cannot drift apart.
+struct StepParams {
+  float eps_iter, eps, cmin, cmax;
+  unsigned mode;
+};
+struct FgmOp {   // out = clamp(x + eps_iter * sign(g))
+  static constexpr int kIn = 2;
+  __device__ static float apply(const StepParams& p, float x, float g, float, bool& bad) {
+    if (p.mode & VQA_CHECK_RANGE) bad |= out_of_range(x, p.cmin, p.cmax);
+    float v = x + p.eps_iter * sign_torch(g);
+    return (p.mode & VQA_CLIP) ? clamp_torch(v, p.cmin, p.cmax) : v;
+  }
+};
+struct StepOp {   // FGM update + projection on the eps-ball around x0
+  static constexpr int kIn = 3;
+  __device__ static float apply(const StepParams& p, float x, float g, float x0, bool& bad) {
+    if (p.mode & VQA_CHECK_RANGE) bad |= out_of_range(x, p.cmin, p.cmax);
+    float a = x + p.eps_iter * sign_torch(g);
+    if (p.mode & VQA_CLIP) a = clamp_torch(a, p.cmin, p.cmax);
+    float e = clamp_torch(a - x0, -p.eps, p.eps);
+    float v = x0 + e;
+    return (p.mode & VQA_CLIP) ? clamp_torch(v, p.cmin, p.cmax) : v;
+  }
+};
+
 // Cross-lane reductions on the DPP path (v_add_f32_dpp / v_max_f32_dpp: one VALU op per step, no LDS crossbar
 // traffic and no lgkmcnt wait, unlike __shfl_xor which lowers to ds_bpermute_b32 on gfx9): two quad permutes, the
 // two row mirrors, then row_bcast:15 / row_bcast:31 funnel the four 16-lane rows into lane 63, which is broadcast

@@ -26,12 +26,7 @@ constexpr size_t kNtStoreBytes = 256ull << 20;
 VQA_KNOB g_opt_unroll = 4;          // option 2: 16-byte tiles in flight per lane and stream (2, 4 or 8)
 VQA_KNOB g_opt_chunked = 0;         // option 3: 0 = grid-stride tiles, 1 = one contiguous chunk per workgroup
 
-struct StepParams {
-  float eps_iter, eps, cmin, cmax;
-  unsigned mode;
-};
-
-// ---- per-element bodies -----------------------------------------------------------------------
+// ---- per-element bodies (StepParams, FgmOp and StepOp live in common.hpp: the momentum step of lnorm.hip uses them too)
 struct InitOp {   // out = clamp(x + clamp(eta, +-eps))
   static constexpr int kIn = 2;
   __device__ static float apply(const StepParams& p, float x, float eta, float, bool& bad) {
@@ -45,25 +40,6 @@ struct InitZeroOp {   // eta == 0: out = clamp(x + 0)
   __device__ static float apply(const StepParams& p, float x, float, float, bool& bad) {
     if (p.mode & VQA_CHECK_RANGE) bad |= out_of_range(x, p.cmin, p.cmax);
     float v = x + 0.0f;
-    return (p.mode & VQA_CLIP) ? clamp_torch(v, p.cmin, p.cmax) : v;
-  }
-};
-struct FgmOp {   // out = clamp(x + eps_iter * sign(g))
-  static constexpr int kIn = 2;
-  __device__ static float apply(const StepParams& p, float x, float g, float, bool& bad) {
-    if (p.mode & VQA_CHECK_RANGE) bad |= out_of_range(x, p.cmin, p.cmax);
-    float v = x + p.eps_iter * sign_torch(g);
-    return (p.mode & VQA_CLIP) ? clamp_torch(v, p.cmin, p.cmax) : v;
-  }
-};
-struct StepOp {   // FGM update + projection on the eps-ball around x0
-  static constexpr int kIn = 3;
-  __device__ static float apply(const StepParams& p, float x, float g, float x0, bool& bad) {
-    if (p.mode & VQA_CHECK_RANGE) bad |= out_of_range(x, p.cmin, p.cmax);
-    float a = x + p.eps_iter * sign_torch(g);
-    if (p.mode & VQA_CLIP) a = clamp_torch(a, p.cmin, p.cmax);
-    float e = clamp_torch(a - x0, -p.eps, p.eps);
-    float v = x0 + e;
     return (p.mode & VQA_CLIP) ? clamp_torch(v, p.cmin, p.cmax) : v;
   }
 };
@@ -264,6 +240,7 @@ int vqa_ce_set_variant(int variant);   // ce.hip
 int vqa_loss_set_option(int which, int value);   // loss.hip
 int vqa_attn_set_option(int value);              // attn.hip
 int vqa_block_set_option(int value);             // block.hip
+int vqa_momentum_set_option(int value);          // lnorm.hip
 
 int vqa_set_option(int option, int value) {
   switch (option) {
@@ -295,6 +272,8 @@ int vqa_set_option(int option, int value) {
       return vqa_block_set_option(value);
     case 12:
       return vqa_loss_set_option(option, value);
+    case 13:
+      return vqa_momentum_set_option(value);
     default:
       return VQA_ERR_SHAPE;
   }

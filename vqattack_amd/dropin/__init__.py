@@ -37,6 +37,8 @@ def load(flavor):
                                         fast_gradient_method=bind(attacks.fast_gradient_method_vl)),
             projected_gradient_descent_vl=mod("projected_gradient_descent_vl",
                                               projected_gradient_descent=bind(attacks.projected_gradient_descent_vl)),
+            momentum_iterative_method=mod("momentum_iterative_method",
+                                          momentum_iterative_method=bind(attacks.momentum_iterative_method)),
         )
         _cache[flavor] = ns
     return ns

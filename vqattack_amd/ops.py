@@ -162,6 +162,12 @@ def _workspace(t):
     return torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=t.device)
 
 
+def reduce_workspace(t):
+    """The workspace a per-sample reduction of a tensor shaped like ``t`` needs, for callers that reuse one (``ws=``)."""
+    dev_f32(t, "t")
+    return _workspace(t)
+
+
 def sumsq_per_sample(t, sub=None):
     """out[b] = sum((t[b] - sub[b])**2), deterministic two-stage reduction."""
     dev_f32(t, "t")
@@ -263,8 +269,87 @@ def scale_per_sample(t, stat, stat2, eps, kind, out=None, flag=None):
     return out
 
 
+# ----------------------------------------------------------------------------------------- momentum (MI-FGSM)
+def _stat_like(t, stat, name):
+    """A caller's per-sample statistic (one fp32 word per sample, used as is: static address for the graph loop)."""
+    batch, _ = _per_sample(t)
+    if stat is None:
+        return torch.empty(batch, dtype=torch.float32, device=t.device)
+    dev_f32(stat, name)
+    if stat.numel() != batch:
+        raise ValueError("{} has {} elements, expected one per sample ({})".format(name, stat.numel(), batch))
+    return stat
+
+
+def sumabs_per_sample(g, out=None, ws=None):
+    """out[b] = sum(|g[b]|), the deterministic two-stage reduction of ``sumsq_per_sample``.  ``out`` and ``ws``
+    (``reduce_workspace(g)``) are used as they are when given: nothing is allocated, as a captured loop needs."""
+    dev_f32(g, "grad")
+    same_device(g, out, ws)
+    out = _stat_like(g, out, "out")
+    batch, n_per = _per_sample(g)
+    if g.numel() == 0:
+        return out.zero_()
+    if ws is None:
+        ws = _workspace(g)
+    elif dev_f32(ws, "ws").numel() * 4 < lib().vqa_reduce_ws_bytes(batch, n_per):
+        raise ValueError("ws holds {} floats, too few for this reduction".format(ws.numel()))
+    with _on(g):
+        check(lib().vqa_sumabs_per_sample(ptr(g), ptr(out), batch, n_per, ptr(ws), stream_for(g)),
+              "vqa_sumabs_per_sample")
+    return out
+
+
+def _momentum_args(g, m, sumabs):
+    dev_f32(g, "grad"), dev_f32(m, "momentum")
+    if m.shape != g.shape:
+        raise ValueError("momentum shape {} != grad shape {}".format(tuple(m.shape), tuple(g.shape)))
+    same_device(g, m, sumabs)
+    if g.numel() == 0:
+        return None
+    return sumabs_per_sample(g) if sumabs is None else _stat_like(g, sumabs, "sumabs")
+
+
+def momentum_accumulate(g, m, decay, sumabs=None):
+    """``m <- decay * m + g / max(1e-12, mean|g[b]|)`` in place; returns ``m``.  ``sumabs``: the per-sample sum of |g|
+    when the caller has it already (``sumabs_per_sample``), computed here otherwise."""
+    sumabs = _momentum_args(g, m, sumabs)
+    if g.numel() == 0:
+        return m
+    batch, n_per = _per_sample(g)
+    with _on(g):
+        check(lib().vqa_momentum_accumulate(ptr(g), ptr(sumabs), ptr(m), batch, n_per, float(decay), stream_for(g)),
+              "vqa_momentum_accumulate")
+    return m
+
+
+def linf_momentum_step(x, g, x0, m, decay, eps_iter, eps, clip_min, clip_max, flag=None, out=None, sumabs=None):
+    """``momentum_accumulate`` and ``linf_step`` on the new momentum in one pass, 24 B/element; ``x0=None``: and
+    ``linf_fgm`` (no projection), 20 B/element.  ``m`` is updated in place; ``out`` may be ``x``."""
+    dev_f32(x, "x")
+    if x0 is not None:
+        dev_f32(x0, "ori_x")
+    if g.shape != x.shape or (x0 is not None and x0.shape != x.shape):
+        raise ValueError("shape mismatch: x {}, grad {}, ori_x {}".format(
+            tuple(x.shape), tuple(g.shape), None if x0 is None else tuple(x0.shape)))
+    same_device(x, g, x0, out, flag)
+    sumabs = _momentum_args(g, m, sumabs)
+    out = _out_like(x, out)
+    mode, lo, hi = _clip_args(clip_min, clip_max)
+    if flag is not None and mode:
+        mode |= VQA_CHECK_RANGE
+    if x.numel() == 0:
+        return out
+    batch, n_per = _per_sample(x)
+    with _on(x):
+        check(lib().vqa_linf_momentum_step(ptr(x), ptr(g), ptr(sumabs), ptr(x0), ptr(m), ptr(out), batch, n_per, float(decay),
+                                           eps_iter, eps, lo, hi, mode, ptr(flag), stream_for(x)),
+              "vqa_linf_momentum_step")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- loss
-_COS_EPS = 1e-6   # nn.CosineSimilarity(eps=1e-6) in the reference
+_COS_EPS = 1e-6  # nn.CosineSimilarity(eps=1e-6) in the reference
 _partials = {}
 
 
