@@ -330,6 +330,16 @@ int vqa_greedy_accept(const int32_t* cand, const int32_t* order, const int32_t* 
 int vqa_attn_fwd(const float* q, const float* k, const float* v, const float* bias, float* o, float* lse, float* scores,
                  int B, int H, int Sq, int Sk, const long* strides, const long* bias_strides, float scale,
                  const int* key_hole, int nsplit, float* split_ws, vqa_stream_t stream);
+/* vqa_attn_fwd with its two products on the bf16 matrix pipe: every fp32 operand split exactly into three bf16 planes,
+ * a product the six plane products that carry fp32's precision (the arithmetic of vqa_gemm_bf16x6), fp32 accumulation;
+ * results are fp32-grade and differ from vqa_attn_fwd's by rounding order.  The same arguments, outputs and `scores`
+ * layout (vqa_attn_bwd reads them as it reads vqa_attn_fwd's).  nsplit must be 1 (VQA_ERR_SHAPE otherwise; split_ws is
+ * ignored): the loop-split forms are vqa_attn_fwd's.  Meant for a forward that is not differentiated or whose vqa_attn_bwd is
+ * given these scores: the score-recomputing forms of vqa_attn_bwd round as vqa_attn_fwd does, and only its lse cancels that.  inf / NaN in q, k, v may come out as NaN.  Additive export: the
+ * ABI version stays. */
+int vqa_attn_fwd_x6(const float* q, const float* k, const float* v, const float* bias, float* o, float* lse,
+                    float* scores, int B, int H, int Sq, int Sk, const long* strides, const long* bias_strides,
+                    float scale, const int* key_hole, int nsplit, float* split_ws, vqa_stream_t stream);
 long vqa_attn_scores_floats(int B, int H, int Sq, int Sk);
 long vqa_attn_split_ws_floats(int B, int H, int Sq, int Sk, int nsplit);
 

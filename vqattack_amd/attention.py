@@ -139,6 +139,26 @@ def _split_ws(b, h, sq, sk, nsplit, device):
     return torch.empty(int(lib().vqa_attn_split_ws_floats(b, h, sq, sk, nsplit)), dtype=torch.float32, device=device)
 
 
+FORWARD_DEFAULT = "x6"
+
+
+def forward_grade(nsplit, recomputing_backward=False):
+    """Which forward kernel a call with ``nsplit`` loop parts runs: ``"x6"`` (``vqa_attn_fwd_x6``, the two products as
+    six exact bf16 products each) or ``"f32"`` (``vqa_attn_fwd``, fp32 MFMA).  ``VQA_ATTN_FWD=x6`` / ``f32`` pins it
+    (unset: FORWARD_DEFAULT) for every call that has an x6 form.  Two kinds of call have none and run fp32 whatever the
+    switch says: the loop-split forms (``nsplit > 1``, small batches), and a differentiated forward that cannot save its
+    scores (``recomputing_backward``).  The fp32 backward kernels then recompute q k^T with THEIR chain's rounding
+    (~1e-5 at scores of 32), which cancels in P = exp(s - lse) against the lse of the fp32 forward only; measured behind
+    the x6 forward, dq at hot queries was 3x further from float64 (profiles/r19/README.md)."""
+    import os
+    want = os.environ.get("VQA_ATTN_FWD")
+    if want and want not in ("x6", "f32"):
+        raise ValueError("VQA_ATTN_FWD must be 'x6' or 'f32', got '{}'".format(want))
+    if nsplit != 1 or recomputing_backward:
+        return "f32"
+    return want or FORWARD_DEFAULT
+
+
 def _forward(q, k, v, bias, bstr, scale, save_scores=False, key_hole=None):
     """Returns (o, lse, scores); ``scores`` is None unless ``save_scores`` and the buffer fits SCORES_LIMIT.
     ``key_hole``: int32 (B, 2) device tensor, see ``KeyHoleBias``."""
@@ -160,12 +180,13 @@ def _forward(q, k, v, bias, bstr, scale, save_scores=False, key_hole=None):
     if key_hole is not None and (key_hole.dtype != torch.int32 or tuple(key_hole.shape) != (b, 2) or
                                  not key_hole.is_cuda or not key_hole.is_contiguous()):
         raise TypeError("key_hole must be a contiguous int32 (B, 2) HIP tensor")
+    entry = "vqa_attn_fwd_x6" if forward_grade(nsplit, save_scores and scores is None) == "x6" else "vqa_attn_fwd"
     with torch.cuda.device(q.device):
-        check(lib().vqa_attn_fwd(ptr(q), ptr(k), ptr(v), ptr(bias), ptr(o), ptr(lse), ptr(scores), b, h, sq, sk, strides,
-                                 _longs(bstr) if bstr else None, scale,
-                                 None if key_hole is None else ctypes.c_void_p(key_hole.data_ptr()), nsplit, ptr(sws),
-                                 stream_for(q)),
-              "vqa_attn_fwd")
+        check(getattr(lib(), entry)(ptr(q), ptr(k), ptr(v), ptr(bias), ptr(o), ptr(lse), ptr(scores), b, h, sq, sk, strides,
+                                    _longs(bstr) if bstr else None, scale,
+                                    None if key_hole is None else ctypes.c_void_p(key_hole.data_ptr()), nsplit, ptr(sws),
+                                    stream_for(q)),
+              entry)
     return o, lse, scores
 
 

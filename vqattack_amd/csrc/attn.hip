@@ -13,6 +13,8 @@
 //   S^T = K . Q^T with the KEY on the accumulator rows and the QUERY on the lane, so that (a) a query's row maximum /
 //   sum is 16 in-register values + one exchange with lane ^ 32, and (b) the accumulator registers ARE the B operand of
 //   the second product  O^T += V^T . P^T  (k-pair of step i = keys r0(i), r0(i) + 4: no LDS round trip for P).
+//   attn_fwd_x6_kernel is the same forward with both products as six exact bf16 plane products each on
+//   v_mfma_f32_32x32x16_bf16 (the GEMMs' bf16x6 arithmetic; see the notes above it); the loop-split forms have no such copy.
 // Backward, deterministic (no float atomics): one kernel owns key blocks (dK, dV: 4 products per tile), one owns query
 //   blocks (dQ: 3 products per tile); both recompute P from the forward's log-sum-exp; the row constants -LSE and
 //   -delta (delta = rowsum(dO . O)) are loaded into the accumulators before the MFMA chains.
@@ -446,6 +448,250 @@ __global__ __launch_bounds__(kBlock, 2) void attn_fwd_kernel(const float* __rest
       }
     }
     return;
+  }
+  if (qi < d.Sq) {
+    l = halves_sum(l);
+    const float inv = 1.0f / l;
+    float* op = o + b * d.o_sb + head * d.o_sh + static_cast<long>(qi) * d.o_ss;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int dim = 8 * g + 4 * h;
+      f32x4 a = {o0[4 * g] * inv, o0[4 * g + 1] * inv, o0[4 * g + 2] * inv, o0[4 * g + 3] * inv};
+      f32x4 c = {o1[4 * g] * inv, o1[4 * g + 1] * inv, o1[4 * g + 2] * inv, o1[4 * g + 3] * inv};
+      *reinterpret_cast<f32x4*>(op + dim) = a;
+      *reinterpret_cast<f32x4*>(op + 32 + dim) = c;
+    }
+    if (h == 0) lse[(static_cast<long>(b) * d.H + head) * d.Sq + qi] = mc * kLn2 + __logf(l);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ forward, bf16x6
+// attn_fwd_x6_kernel is attn_fwd_kernel (the unsplit form) with its two products moved from v_mfma_f32_32x32x2_f32 to
+// v_mfma_f32_32x32x16_bf16, 1/16 of the cycles per product: every fp32 operand is split exactly into three bf16 planes
+// (split8 of common.hpp, the GEMM's) and a product is the six plane products that carry fp32's precision, summed small
+// terms first per k-step as in gemm.hip -- 48 MFMAs of 32 cycles per wave and key tile instead of 64 of 64.  The C/D
+// layout of the two instructions is the same, so everything between and behind the chains -- bias, hole, masks, lazy
+// maximum, exponentials, the blocked score store, the epilogue -- is the fp32 kernel's text.  The backward kernels stay
+// fp32 and start from the scores and lse stored here.
+//   S^T = K . (scale Q)^T: k-step s (of 4) of lane half h covers head dimensions 32 h + 8 s .. + 7 (the k order of a
+//     step is free as long as both operands agree).  Q's fragments are the lane's own qf[8 s ..], split once per
+//     workgroup; K's are published in FRAGMENT ORDER: 1 KiB per (k-step, plane), lane (key, h) at 16 (32 h + key).
+//   O^T += V^T . P^T: registers 8 s .. 8 s + 7 of the P accumulator, split in registers, are the B fragment of k-step s
+//     (of 2); its element j is key 16 s + 8 (j >> 2) + 4 h + (j & 3) of the tile, so the A fragment of lane (dim r, h)
+//     holds V of exactly those keys in that order: 1 KiB per (dim block, k-step, plane).  A publishing thread owns two
+//     adjacent keys of four dimensions and writes one 32-bit pair per dimension and plane; a lane's 16-byte slot sits at
+//     slot ^ ((slot >> 3) & 3), which spreads those writes over the banks and keeps every ds_read_b128 conflict-free.
+// LDS: 2 buffers x (12 + 12) KiB.  Non-finite Q / K / V: the splits here are the unchecked form of common.hpp (an inf or
+// NaN element has NaN correction planes; the checked form would not help, inf times a zero-valued plane is NaN as
+// well), so a query row or a key that holds one may come out NaN where the fp32 kernel gives inf.  A masked key (-inf
+// score) gives P = 0 exactly as before, and P in [0, 1] is always finite.
+constexpr int kX6Plane = 64 * 16;                // bytes of one fragment image
+constexpr int kX6Tile = 12 * kX6Plane;           // K: 4 k-steps x 3 planes; V: 2 dim blocks x 2 k-steps x 3 planes
+
+__device__ __forceinline__ f32x16 mfma_bf16(const bf16x8& a, const bf16x8& b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+
+// One thread's piece of a row of every 32-row tile, rows beyond the sequence clamped: TileCursor with the thread's
+// (row, column) given by the caller.
+struct RowCursor {
+  const float* p;
+  const float* last;
+  long step;
+  int last_tile;
+};
+__device__ __forceinline__ RowCursor row_cursor(const float* __restrict__ base, long ss, int n_rows, int lrow, int col) {
+  RowCursor c;
+  c.last_tile = (n_rows - 1) / kTile;
+  int row = c.last_tile * kTile + lrow;
+  row = row < n_rows ? row : n_rows - 1;
+  c.last = base + static_cast<long>(row) * ss + col;
+  c.p = base + static_cast<long>(lrow) * ss + col;
+  c.step = kTile * ss;
+  return c;
+}
+__device__ __forceinline__ const float* row_next(RowCursor& c, int tile) {
+  const float* p = tile == c.last_tile ? c.last : c.p;
+  c.p += c.step;
+  return p;
+}
+
+// K: thread = (key 8 wave + lane % 8, dimensions 8 c .. 8 c + 7 with c = lane / 8): the 8 lanes of a write group put 128
+// consecutive bytes.  V: thread = (keys 2 kp, 2 kp + 1 with kp = tid / 16, dimensions 4 dq .. + 3 with dq = tid % 16).
+struct X6Regs {
+  f32x4 k[2], v[2];
+};
+
+template <bool HAS_BIAS, bool STORE_S>
+__global__ __launch_bounds__(kBlock, 2) void attn_fwd_x6_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                                const float* __restrict__ v,
+                                                                const float* __restrict__ bias, float* __restrict__ o,
+                                                                float* __restrict__ lse, float* __restrict__ scores,
+                                                                AttnDims d, const int* __restrict__ key_hole) {
+  __shared__ __attribute__((aligned(16))) char Kimg[2][kX6Tile];
+  __shared__ __attribute__((aligned(16))) char Vimg[2][kX6Tile];
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const int r = lane & 31, h = lane >> 5;
+  const BlockCoord bc = block_coord((d.Sq + 127) / 128, d.B, d.H);
+  const int b = bc.b, head = bc.head;
+  const int q0 = bc.blk * 128 + wave * kTile;
+  const bool active = q0 < d.Sq;                           // a wave past the last query only helps staging the tiles
+  const int qi = q0 + r;                                   // this lane's query
+  const int ql = qi < d.Sq ? qi : d.Sq - 1;                // clamped for loads
+  const float* qp = q + b * d.q_sb + head * d.q_sh + static_cast<long>(ql) * d.q_ss + 32 * h;
+  const float* kb = k + b * d.k_sb + head * d.k_sh;
+  const float* vb = v + b * d.v_sb + head * d.v_sh;
+  const float* bp = HAS_BIAS ? bias + b * d.bias_sb + head * d.bias_sh + static_cast<long>(ql) * d.bias_sr + 4 * h
+                             : nullptr;
+  float* scp = STORE_S ? scores + (static_cast<long>(b) * d.H + head) * sc_rows(d.Sq) * sc_pitch(d.Sk) +
+                             (q0 / kTile) * sc_pitch(d.Sk) * kTile + 4 * lane
+                       : nullptr;
+  bf16x8 qs[3][4];                                         // planes of Q[query][32 h + 8 s ..] * scale: the B operand of S^T
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const f32x4 lo = *reinterpret_cast<const f32x4*>(qp + 8 * s) * d.scale;
+    const f32x4 hi = *reinterpret_cast<const f32x4*>(qp + 8 * s + 4) * d.scale;
+    split8<false>(lo, hi, qs[0][s], qs[1][s], qs[2][s]);
+  }
+  f32x16 o0 = {0}, o1 = {0};                               // O^T[dim (+32)][query]
+  float m = -INFINITY, mc = 0.0f, l = 0.0f;                // running max, the same times log2 e (0 while -inf), row sum
+  const int n_tiles = (d.Sk + kTile - 1) / kTile;
+  const int hole_lo = key_hole ? key_hole[2 * b] : 0, hole_hi = key_hole ? key_hole[2 * b + 1] : 0;
+  f32x16 bcur = {0};
+  if (HAS_BIAS && active) bcur = load_bias_tile(bp, 0);
+  // staging roles of this thread and where its pieces go in a tile's images
+  const int kc = lane >> 3;
+  RowCursor ck = row_cursor(kb, d.k_ss, d.Sk, 8 * wave + (lane & 7), 8 * kc);
+  const int k_off = ((kc & 3) * 3 * 64 + 32 * (kc >> 2) + 8 * wave + (lane & 7)) * 16;
+  const int kp = threadIdx.x >> 4, dq = threadIdx.x & 15;
+  RowCursor cv0 = row_cursor(vb, d.v_ss, d.Sk, 2 * kp, 4 * dq), cv1 = row_cursor(vb, d.v_ss, d.Sk, 2 * kp + 1, 4 * dq);
+  int v_off[4];                                            // keys 2 kp, 2 kp + 1: k-step kp / 8, lane half (kp / 2) % 2,
+#pragma unroll                                             // elements j, j + 1 with j / 2 = 2 ((kp / 4) % 2) + kp % 2
+  for (int e = 0; e < 4; ++e) {
+    const int slot = 32 * ((kp >> 1) & 1) + 4 * (dq & 7) + e;
+    v_off[e] = (((dq >> 3) * 2 + (kp >> 3)) * 3 * 64 + (slot ^ ((slot >> 3) & 3))) * 16 + 4 * (2 * ((kp >> 2) & 1) + (kp & 1));
+  }
+  auto fetch = [&](int tile) {
+    X6Regs t;
+    const float* pk = row_next(ck, tile);
+    t.k[0] = *reinterpret_cast<const f32x4*>(pk);
+    t.k[1] = *reinterpret_cast<const f32x4*>(pk + 4);
+    t.v[0] = *reinterpret_cast<const f32x4*>(row_next(cv0, tile));
+    t.v[1] = *reinterpret_cast<const f32x4*>(row_next(cv1, tile));
+    return t;
+  };
+  auto publish = [&](int buf, const X6Regs& t) {
+    bf16x8 p0, p1, p2;
+    split8<false>(t.k[0], t.k[1], p0, p1, p2);
+    char* kd = Kimg[buf] + k_off;
+    *reinterpret_cast<bf16x8*>(kd) = p0;
+    *reinterpret_cast<bf16x8*>(kd + kX6Plane) = p1;
+    *reinterpret_cast<bf16x8*>(kd + 2 * kX6Plane) = p2;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      bf16x2 h0, h1, h2;
+      split2<false>(f32x2{t.v[0][e], t.v[1][e]}, h0, h1, h2);
+      char* vd = Vimg[buf] + v_off[e];
+      *reinterpret_cast<bf16x2*>(vd) = h0;
+      *reinterpret_cast<bf16x2*>(vd + kX6Plane) = h1;
+      *reinterpret_cast<bf16x2*>(vd + 2 * kX6Plane) = h2;
+    }
+  };
+  publish(0, fetch(0));
+  __syncthreads();
+  const int v_slot = lane ^ ((lane >> 3) & 3);
+  for (int kt = 0; kt < n_tiles; ++kt) {
+    const int k0 = kt * kTile;
+    const bf16x8* Kf = reinterpret_cast<const bf16x8*>(Kimg[kt & 1]) + lane;
+    const bf16x8* Vf = reinterpret_cast<const bf16x8*>(Vimg[kt & 1]) + v_slot;
+    const bool more = kt + 1 < n_tiles;
+    X6Regs tn;
+    if (more) tn = fetch(kt + 1);                // in flight while this tile is computed
+    f32x16 sraw;                                 // the tile's raw scores (live waves of a STORE_S kernel only)
+    if (active) {
+      f32x16 bnext = {0};
+      if (HAS_BIAS && more) bnext = load_bias_tile(bp, k0 + kTile);
+      __builtin_amdgcn_sched_barrier(0);         // keep every load ahead of the MFMA chain that hides its latency
+      // S^T = K . (scale Q)^T, key on the accumulator row; the bias is added once, after the chain (see attn_fwd_kernel)
+      f32x16 st = {0};
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const bf16x8 kf0 = Kf[(3 * s) * 64], kf1 = Kf[(3 * s + 1) * 64], kf2 = Kf[(3 * s + 2) * 64];
+        st = mfma_bf16(kf2, qs[0][s], st);
+        st = mfma_bf16(kf1, qs[1][s], st);
+        st = mfma_bf16(kf0, qs[2][s], st);
+        st = mfma_bf16(kf1, qs[0][s], st);
+        st = mfma_bf16(kf0, qs[1][s], st);
+        st = mfma_bf16(kf0, qs[0][s], st);
+      }
+      if (HAS_BIAS) st += bcur;
+      if (k0 < hole_hi && k0 + kTile > hole_lo) {   // a tile that overlaps the hole: -inf, and the saved scores carry it
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int key = k0 + acc_row(i, h);
+          st[i] = (key >= hole_lo && key < hole_hi) ? -INFINITY : st[i];
+        }
+      }
+      if (STORE_S) sraw = st;                    // stored at the end of the tile
+      if (k0 + kTile > d.Sk) {                   // last, partial tile: keys beyond Sk never win the softmax
+#pragma unroll
+        for (int i = 0; i < 16; ++i) st[i] = k0 + acc_row(i, h) < d.Sk ? st[i] : -INFINITY;
+      }
+      float mx = st[0];
+#pragma unroll
+      for (int i = 1; i < 16; ++i) mx = fmaxf(mx, st[i]);
+      mx = halves_max(mx);
+      const bool grow = mx > m + kLazyMax;       // m = -inf: any finite score starts the row
+      if (__builtin_amdgcn_ballot_w64(grow) != 0) {
+        const float m_new = grow ? mx : m;
+        const float mc_new = m_new * kLog2e;     // m_new is finite wherever it changed
+        const float alpha = m == -INFINITY ? 0.0f : __builtin_amdgcn_exp2f(mc - mc_new);   // exactly 1 if unchanged
+        m = m_new;
+        mc = grow ? mc_new : mc;
+        l *= alpha;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          o0[i] *= alpha;
+          o1[i] *= alpha;
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        st[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(st[i], kLog2e, -mc));
+        l += st[i];
+      }
+      // O^T += V^T . P^T: registers 8 s .. 8 s + 7 of P are the B fragment of k-step s, V's image is in their key order
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        bf16x8 p0, p1, p2;
+        split8<false>(f32x4{st[8 * s], st[8 * s + 1], st[8 * s + 2], st[8 * s + 3]},
+                      f32x4{st[8 * s + 4], st[8 * s + 5], st[8 * s + 6], st[8 * s + 7]}, p0, p1, p2);
+        const bf16x8 va0 = Vf[(3 * s) * 64], va1 = Vf[(3 * s + 1) * 64], va2 = Vf[(3 * s + 2) * 64];
+        const bf16x8 vb0 = Vf[(3 * (2 + s)) * 64], vb1 = Vf[(3 * (2 + s) + 1) * 64], vb2 = Vf[(3 * (2 + s) + 2) * 64];
+        o0 = mfma_bf16(va2, p0, o0);
+        o1 = mfma_bf16(vb2, p0, o1);
+        o0 = mfma_bf16(va1, p1, o0);
+        o1 = mfma_bf16(vb1, p1, o1);
+        o0 = mfma_bf16(va0, p2, o0);
+        o1 = mfma_bf16(vb0, p2, o1);
+        o0 = mfma_bf16(va1, p0, o0);
+        o1 = mfma_bf16(vb1, p0, o1);
+        o0 = mfma_bf16(va0, p1, o0);
+        o1 = mfma_bf16(vb0, p1, o1);
+        o0 = mfma_bf16(va0, p0, o0);
+        o1 = mfma_bf16(vb0, p0, o1);
+      }
+      bcur = bnext;
+    }
+    if (more) publish((kt + 1) & 1, tn);         // the other buffer was last read one tile ago (barrier in between)
+    // the score stores leave behind the publish, as in attn_fwd_kernel: nothing inside the tile waits for them
+    if (STORE_S && active) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        *reinterpret_cast<f32x4*>(scp + static_cast<long>(kt) * kBlockFloats + 256 * g) =
+            f32x4{sraw[4 * g], sraw[4 * g + 1], sraw[4 * g + 2], sraw[4 * g + 3]};
+    }
+    __syncthreads();
   }
   if (qi < d.Sq) {
     l = halves_sum(l);
@@ -1053,22 +1299,32 @@ static int check_split(int nsplit, const float* split_ws, int tiles, long wgs) {
   return VQA_OK;
 }
 
-int vqa_attn_fwd(const float* q, const float* k, const float* v, const float* bias, float* o, float* lse, float* scores,
-                 int B, int H, int Sq, int Sk, const long* strides, const long* bias_strides, float scale,
-                 const int* key_hole, int nsplit, float* split_ws, vqa_stream_t stream) {
-  clear_stale_error();
+// The forward entries' arguments -> AttnDims, checked.
+static int fwd_dims(const float* q, const float* k, const float* v, const float* bias, const float* o, const float* lse,
+                    const float* scores, int B, int H, int Sq, int Sk, const long* strides, const long* bias_strides,
+                    float scale, AttnDims& d) {
   if (!strides || !o || !lse || (bias && !bias_strides)) return VQA_ERR_NULL;
-  AttnDims d{B, H, Sq, Sk, strides[0], strides[1], strides[2], strides[3], strides[4], strides[5], strides[6],
-             strides[7], strides[8], strides[9], strides[10], strides[11], 0, 0, 0, scale};
+  d = AttnDims{B, H, Sq, Sk, strides[0], strides[1], strides[2], strides[3], strides[4], strides[5], strides[6],
+               strides[7], strides[8], strides[9], strides[10], strides[11], 0, 0, 0, scale};
   if (bias) {
     d.bias_sb = bias_strides[0];
     d.bias_sh = bias_strides[1];
     d.bias_sr = bias_strides[2];
     if (((d.bias_sb | d.bias_sh | d.bias_sr) & 3) || !aligned16(bias)) return VQA_ERR_ALIGN;
   }
-  int rc = check_attn(q, k, v, d);
+  const int rc = check_attn(q, k, v, d);
   if (rc != VQA_OK) return rc;
   if (!aligned16(o) || !aligned16(scores)) return VQA_ERR_ALIGN;
+  return VQA_OK;
+}
+
+int vqa_attn_fwd(const float* q, const float* k, const float* v, const float* bias, float* o, float* lse, float* scores,
+                 int B, int H, int Sq, int Sk, const long* strides, const long* bias_strides, float scale,
+                 const int* key_hole, int nsplit, float* split_ws, vqa_stream_t stream) {
+  clear_stale_error();
+  AttnDims d;
+  int rc = fwd_dims(q, k, v, bias, o, lse, scores, B, H, Sq, Sk, strides, bias_strides, scale, d);
+  if (rc != VQA_OK) return rc;
   const long wgs = ((Sq + 127L) / 128) * H * B;
   rc = check_split(nsplit, split_ws, (Sk + kTile - 1) / kTile, wgs);
   if (rc != VQA_OK) return rc;
@@ -1090,6 +1346,25 @@ int vqa_attn_fwd(const float* q, const float* k, const float* v, const float* bi
   else if (bias) attn_fwd_kernel<true, false><<<grid, kBlock, 0, st>>>(q, k, v, bias, o, lse, scores, d, key_hole, sp);
   else if (scores) attn_fwd_kernel<false, true><<<grid, kBlock, 0, st>>>(q, k, v, bias, o, lse, scores, d, key_hole, sp);
   else attn_fwd_kernel<false, false><<<grid, kBlock, 0, st>>>(q, k, v, bias, o, lse, scores, d, key_hole, sp);
+  return launch_status();
+}
+
+int vqa_attn_fwd_x6(const float* q, const float* k, const float* v, const float* bias, float* o, float* lse,
+                    float* scores, int B, int H, int Sq, int Sk, const long* strides, const long* bias_strides,
+                    float scale, const int* key_hole, int nsplit, float* split_ws, vqa_stream_t stream) {
+  clear_stale_error();
+  (void)split_ws;
+  if (nsplit != 1) return VQA_ERR_SHAPE;         // the loop-split forms are fp32 only: vqa_attn_fwd
+  AttnDims d;
+  const int rc = fwd_dims(q, k, v, bias, o, lse, scores, B, H, Sq, Sk, strides, bias_strides, scale, d);
+  if (rc != VQA_OK) return rc;
+  if (B == 0) return VQA_OK;
+  const dim3 grid(static_cast<unsigned>(((Sq + 127L) / 128) * H * B));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (bias && scores) attn_fwd_x6_kernel<true, true><<<grid, kBlock, 0, st>>>(q, k, v, bias, o, lse, scores, d, key_hole);
+  else if (bias) attn_fwd_x6_kernel<true, false><<<grid, kBlock, 0, st>>>(q, k, v, bias, o, lse, scores, d, key_hole);
+  else if (scores) attn_fwd_x6_kernel<false, true><<<grid, kBlock, 0, st>>>(q, k, v, bias, o, lse, scores, d, key_hole);
+  else attn_fwd_x6_kernel<false, false><<<grid, kBlock, 0, st>>>(q, k, v, bias, o, lse, scores, d, key_hole);
   return launch_status();
 }
 

@@ -61,6 +61,41 @@ struct StepOp {   // FGM update + projection on the eps-ball around x0
   }
 };
 
+// The exact three-way bf16 split of an fp32 value (the bf16x6 products of gemm.hip and of the attention forward):
+// a = a0 + a1 + a2 with a0 = bf16(a), a1 = bf16(a - a0), a2 = bf16(a - a0 - a1), both subtractions exact in fp32.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// a -> (a0, a1, a2), exact for finite a whose bf16 rounding is finite.  Plain RNE casts (v_cvt_pk_bf16_f32).
+// CHECKED: a0 = +-inf / NaN (a non-finite, or |a| at the top of the range rounding up) gets no correction terms, so
+// that inf / NaN propagate through a product as in fp32 (the GEMMs).  Unchecked, such an element's a1 and a2 are NaN:
+// for callers whose values are finite by construction or whose contract lets a non-finite input come out as NaN.
+template <bool CHECKED = true>
+__device__ __forceinline__ void split2(f32x2 a, bf16x2& h0, bf16x2& h1, bf16x2& h2) {
+  h0 = __builtin_convertvector(a, bf16x2);
+  f32x2 r = a - __builtin_convertvector(h0, f32x2);
+  if (CHECKED) {
+    r.x = __builtin_isfinite(r.x) ? r.x : 0.0f;
+    r.y = __builtin_isfinite(r.y) ? r.y : 0.0f;
+  }
+  h1 = __builtin_convertvector(r, bf16x2);
+  h2 = __builtin_convertvector(r - __builtin_convertvector(h1, f32x2), bf16x2);
+}
+
+template <bool CHECKED = true>
+__device__ __forceinline__ void split8(const f32x4& lo, const f32x4& hi, bf16x8& p0, bf16x8& p1, bf16x8& p2) {
+  bf16x2 a[4], b[4], c[4];
+  split2<CHECKED>(f32x2{lo.x, lo.y}, a[0], b[0], c[0]);
+  split2<CHECKED>(f32x2{lo.z, lo.w}, a[1], b[1], c[1]);
+  split2<CHECKED>(f32x2{hi.x, hi.y}, a[2], b[2], c[2]);
+  split2<CHECKED>(f32x2{hi.z, hi.w}, a[3], b[3], c[3]);
+  p0 = bf16x8{a[0].x, a[0].y, a[1].x, a[1].y, a[2].x, a[2].y, a[3].x, a[3].y};
+  p1 = bf16x8{b[0].x, b[0].y, b[1].x, b[1].y, b[2].x, b[2].y, b[3].x, b[3].y};
+  p2 = bf16x8{c[0].x, c[0].y, c[1].x, c[1].y, c[2].x, c[2].y, c[3].x, c[3].y};
+}
+
 // Cross-lane reductions on the DPP path (v_add_f32_dpp / v_max_f32_dpp: one VALU op per step, no LDS crossbar
 // traffic and no lgkmcnt wait, unlike __shfl_xor which lowers to ds_bpermute_b32 on gfx9): two quad permutes, the
 // two row mirrors, then row_bcast:15 / row_bcast:31 funnel the four 16-lane rows into lane 63, which is broadcast

@@ -61,8 +61,6 @@
 
 namespace vqa {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kGemmBM = 256, kGemmBN = 128, kGemmBK = 32;
@@ -75,27 +73,7 @@ constexpr int kGemmStage = kGemmABytes + kGemmBBytes;                  // 72 KiB
 constexpr int kGemmBPieces = kGemmBBytes / 16 / kGemmThreads;          // 3 x 16 B of B per thread and k-step
 constexpr int kWideLoadPair = 12;                                      // MFMAs behind each pair of global loads of the next step
 
-// a -> (a0, a1, a2), exact for finite a whose bf16 rounding is finite.  Plain RNE casts (v_cvt_pk_bf16_f32).
-__device__ __forceinline__ void split2(f32x2 a, bf16x2& h0, bf16x2& h1, bf16x2& h2) {
-  h0 = __builtin_convertvector(a, bf16x2);
-  f32x2 r = a - __builtin_convertvector(h0, f32x2);
-  // a0 = +-inf / NaN (a non-finite, or |a| at the top of the range rounding up): no correction terms
-  r.x = __builtin_isfinite(r.x) ? r.x : 0.0f;
-  r.y = __builtin_isfinite(r.y) ? r.y : 0.0f;
-  h1 = __builtin_convertvector(r, bf16x2);
-  h2 = __builtin_convertvector(r - __builtin_convertvector(h1, f32x2), bf16x2);
-}
-
-__device__ __forceinline__ void split8(const f32x4& lo, const f32x4& hi, bf16x8& p0, bf16x8& p1, bf16x8& p2) {
-  bf16x2 a[4], b[4], c[4];
-  split2(f32x2{lo.x, lo.y}, a[0], b[0], c[0]);
-  split2(f32x2{lo.z, lo.w}, a[1], b[1], c[1]);
-  split2(f32x2{hi.x, hi.y}, a[2], b[2], c[2]);
-  split2(f32x2{hi.z, hi.w}, a[3], b[3], c[3]);
-  p0 = bf16x8{a[0].x, a[0].y, a[1].x, a[1].y, a[2].x, a[2].y, a[3].x, a[3].y};
-  p1 = bf16x8{b[0].x, b[0].y, b[1].x, b[1].y, b[2].x, b[2].y, b[3].x, b[3].y};
-  p2 = bf16x8{c[0].x, c[0].y, c[1].x, c[1].y, c[2].x, c[2].y, c[3].x, c[3].y};
-}
+// split2 / split8 (a -> its three bf16 planes) live in common.hpp: the attention forward splits with the same body.
 
 // 16 bytes per lane from global memory straight into LDS (global_load_lds_dwordx4): the wave's 64 pieces land at
 // lds + lane * 16, lds wave-uniform.  A pending LDS write on the vector-memory counter until stage_b_wait().
