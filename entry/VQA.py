@@ -53,6 +53,8 @@ def parse(argv=None):
                     help="sentence-similarity floor of a substitution (adv_attack.py:303)")
     ap.add_argument("--decay_factor", default=None, type=float,
                     help="MI-FGSM momentum decay of the image attack (Dong et al. 2017); absent: plain PGD")
+    ap.add_argument("--ti_kernel", default=None, type=int,
+                    help="TI-FGSM Gaussian kernel length of the image attack (Dong et al. 2019; odd, 1..31); absent: off")
     ap.add_argument("--mlm_checkpoint", default="", help="BertForMaskedLM state dict -> candidate proposer (adv_attack.py:110)")
     ap.add_argument("--answer_list", default=None,
                     help="ALBEF answer_list json (configs: answer_list): the victim ranks it and acc_vqa compares answer "
@@ -124,7 +126,8 @@ def main():
                     rank, world, joint=not args.image_only, save_dir=out_dir, seed=args.seed,
                     max_words=4 if args.tiny else 12, dual_every=args.dual_every, mixed=args.mixed,
                     force_collective=dist.is_initialized(), source=source, mlm_logits_fn=proposer, banned_ids=banned,
-                    config=AttackConfig(sim_threshold=args.sim_threshold, decay_factor=args.decay_factor),
+                    config=AttackConfig(sim_threshold=args.sim_threshold, decay_factor=args.decay_factor,
+                                        ti_kernel=args.ti_kernel),
                     scoring=scoring)
     finish(rank, world, res, os.path.join(args.output_dir, "adv_txt.json") if args.output_dir else None,
            os.path.join(args.output_dir, "adv_txt_dict_albef.txt") if args.output_dir and scoring else None)

@@ -64,7 +64,8 @@ const char* vqa_error_string(int code);
  *   option 10: block-glue kernels, bit0 = non-temporal loads of the activation streams, bit1 = non-temporal stores of GELU
  *             results larger than the Infinity Cache (default 3)
  *   option 13: momentum kernels: 16-byte tiles in flight per lane and stream (2 or 4), + 8 = a momentum tensor larger
- *             than the Infinity Cache is loaded and stored non-temporally (default 2 + 8 = 10) */
+ *             than the Infinity Cache is loaded and stored non-temporally (default 2 + 8 = 10)
+ *   option 14: output tile height of the TI smoothing kernels (32 or 64 rows of 64; default 32) */
 int vqa_set_option(int option, int value);
 #endif
 
@@ -175,6 +176,36 @@ int vqa_momentum_accumulate(const float* g, const float* sumabs, float* m, int b
 int vqa_linf_momentum_step(const float* x, const float* g, const float* sumabs, const float* x0, float* m, float* out,
                            int batch, size_t n_per_sample, float decay, float eps_iter, float eps, float cmin,
                            float cmax, unsigned mode, int* flag, vqa_stream_t stream);
+
+/* ---------------------------------------------------------------- translation-invariant smoothing (TI-FGSM, Dong et al. 2019)
+ * The reference tree has no TI in any framework; this definition is the contract.  For a gradient g of `planes` row-major
+ * (height, width) planes and K = ktaps taps w[0..K-1] (K odd, 1 <= K <= 31, r = K / 2), per plane:
+ *   t[y, x]    = sum_{j=0..K-1} w[j] * g[y, x + j - r]       (row pass)
+ *   ghat[y, x] = sum_{j=0..K-1} w[j] * t[y + j - r, x]       (column pass)
+ * Each accumulator starts at +0.0f, terms are taken in ascending j, each term is one fp32 multiply followed by one fp32
+ * add (no contraction), planes are zero padded (a term whose source lies outside the plane adds w * 0) and never see
+ * their neighbour planes.  K = 1, w = {1} gives g back with -0 as +0.  The paper's 2-D Gaussian kernel is the outer
+ * product of its normalised 1-D taps, so the separable form is the same operator.
+ * taps_host is a HOST pointer to K floats; they travel by value in the kernel arguments (no device allocation, no copy,
+ * no sync: capture-safe like every other entry point).  One workgroup per 64 x 32 tile stages the tile and its halo in
+ * LDS and runs both passes there.
+ * Return codes, all before the first HIP call: a NULL g / out / x / taps_host, or VQA_CHECK_RANGE without flag,
+ * VQA_ERR_NULL; ktaps even or outside 1..31, a negative extent, planes * tiles beyond the 2^31 - 1 workgroups of one
+ * launch, or g == out, VQA_ERR_SHAPE; a pointer not 4-byte aligned VQA_ERR_ALIGN; any zero extent VQA_OK, no launch.
+ * Pointers need 4-byte alignment only and width need not be a multiple of 4 (16-byte accesses are used where both allow).
+ */
+
+/* out = ghat.  8 B/element plus the halo re-reads of g (1.75 x at K = 15, mostly from L2).  g must not alias out. */
+int vqa_ti_smooth(const float* g, float* out, int planes, int height, int width, const float* taps_host, int ktaps,
+                  vqa_stream_t stream);
+
+/* The smoothing above and the L-infinity update in ONE pass: out = vqa_linf_step(x, ghat, x0), or, for x0 == NULL,
+ * out = vqa_linf_fgm(x, ghat) -- bit for bit what vqa_ti_smooth followed by that launch gives; ghat never goes to memory.
+ * 16 B/element (12 without x0) plus the halo re-reads, against 24 for the two launches.  `out` may alias `x` (each
+ * element of x is read only by the thread that writes it); g must not alias out.  mode / flag as in vqa_linf_step. */
+int vqa_linf_ti_step(const float* x, const float* g, const float* x0, float* out, int planes, int height, int width,
+                     const float* taps_host, int ktaps, float eps_iter, float eps, float cmin, float cmax, unsigned mode,
+                     int* flag, vqa_stream_t stream);
 
 /* ---------------------------------------------------------------- cross-modal loss reduction
  * Rows of D contiguous floats, addressed as row(o, i) = base + o*stride0 + i*stride1 (strides in ELEMENTS) for

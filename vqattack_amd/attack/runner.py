@@ -44,12 +44,17 @@ class AttackConfig:
     patch_layout: bool = False         # keep the PGD state patch-major (layout.py); measured neutral end to end, see DESIGN
     live_mlm_rows: bool = True         # dual loss: MLM head + cross entropy at the live label rows only (False: dense B x L)
     decay_factor: Optional[float] = None   # not None: MI-FGSM, one momentum buffer per attack (attacks.projected_gradient_descent)
+    ti_kernel: object = None               # not None: TI-FGSM smoothing of every image gradient (odd kernel length 1..31 or taps)
 
     def __post_init__(self):
         attacks._validate_decay(self.decay_factor)
         if self.decay_factor is not None and self.patch_layout:
             # the per-sample sum of |grad| is folded in memory order: a patch-major image would round it differently
             raise ValueError("decay_factor and patch_layout=True cannot be combined")
+        attacks._validate_ti(self.ti_kernel)
+        if self.ti_kernel is not None and self.patch_layout:
+            # the stencil runs over row-major (H, W) planes: a patch-major image has none
+            raise ValueError("ti_kernel and patch_layout=True cannot be combined")
 
 
 @dataclass
@@ -118,7 +123,8 @@ class BatchedVQAttack:
     def _pgd_block(self, adv, clean, targets, steps, time, dual, mlm_labels, init_eta=None, momentum=None):
         c = self.cfg
         common = dict(clip_min=c.clip_min, clip_max=c.clip_max, time=time, ori_x=clean,
-                      sanity_checks=c.sanity_checks, init_eta=init_eta, decay_factor=c.decay_factor, momentum=momentum)
+                      sanity_checks=c.sanity_checks, init_eta=init_eta, decay_factor=c.decay_factor, momentum=momentum,
+                      ti_kernel=c.ti_kernel)
         a = self.adapters
         if not dual:
             return self.pgd(a.pgd_attack, adv, c.eps, c.eps_iter, steps, c.norm, y=self._y_feature(targets), ls=1,
@@ -228,7 +234,7 @@ class BatchedVQAttack:
                                                  1, c.norm, clip_min=c.clip_min, clip_max=c.clip_max,
                                                  y=self._y_feature(targets), time=1, ori_x=images, ls=1,
                                                  attack_mask=positions, sanity_checks=c.sanity_checks,
-                                                 decay_factor=c.decay_factor, momentum=mom)
+                                                 decay_factor=c.decay_factor, momentum=mom, ti_kernel=c.ti_kernel)
                 res.gradient_steps += 1
                 if plan is not None:
                     scores = text_update.score_plan(self.tables, e_ori, text_grad, plan)
@@ -364,6 +370,8 @@ class BatchedVQAttack:
             eta = torch.empty_like(images, memory_format=torch.contiguous_format).uniform_(-c.eps, c.eps)
         cur = ops.linf_init(images.contiguous(), eta, c.eps, c.clip_min, c.clip_max, flag=flag)
         mom = self._new_momentum(images)          # in the sorted order of `images`; only the active prefix is updated
+        # TI-FGSM: the taps and (with momentum) ONE smoothed-gradient scratch for the whole call
+        ti = attacks._smoother(attacks._validate_ti(c.ti_kernel), cur, np.inf, c.decay_factor)
         losses = torch.zeros(max(total), dtype=torch.float32, device=dev)
         ws = ops.Workspace()
         res = BatchResult(adv_images=cur, adv_text_ids=adv_ids)
@@ -422,7 +430,7 @@ class BatchedVQAttack:
             else:
                 attacks._loss_and_grad(a.pgd_attack_vl, [leaf_img, leaf_txt], [leaf_img, leaf_txt], list(y), 1,
                                        self.flavor, False, slot, vl=True, ws=ws)
-            self._update_runs(cur, attacks._grad_of(leaf_img), images, now, mom)
+            self._update_runs(cur, attacks._grad_of(leaf_img), images, now, mom, ti)
             firing = [s for s in range(n_act) if kinds[s][t][1]]
             if firing:
                 sub = plan.restricted_to(firing)
@@ -483,20 +491,27 @@ class BatchedVQAttack:
                 labels[s, j, :len(row)] = torch.tensor(row)
         return tasks, text_ids, text_masks, attackable, mlm_ids, mlm_mask, (labels[:, 0] if k == 1 else labels).to(dev)
 
-    def _update_runs(self, cur, grad, images, now, mom=None):
+    def _update_runs(self, cur, grad, images, now, mom=None, ti=None):
         """The fused image update of one global step, in place on the active prefix of ``cur``: one launch per run of
         consecutive samples of one kind -- ``vqa_linf_fgm`` for ``N`` (first half of a dual iteration: no projection in
         between, projected_gradient_descent.py:155-188), ``vqa_linf_step`` otherwise.  Finished samples stay untouched.
         ``mom`` (MI-FGSM): ``vqa_linf_momentum_step`` instead, without ``x0`` for ``N`` runs; a run accumulates into its own
-        rows of the momentum, so a finished sample's momentum stays as it was."""
+        rows of the momentum, so a finished sample's momentum stays as it was.
+        ``ti`` (TI-FGSM): ``vqa_linf_ti_step`` instead of the two plain kernels; with momentum the run's gradient is smoothed
+        into its rows of the call's scratch first and the momentum step takes that."""
         c, lo, n_act = self.cfg, 0, len(now)
         while lo < n_act:
             hi = lo + 1
             while hi < n_act and (now[hi] == "N") == (now[lo] == "N"):
                 hi += 1
+            x0 = None if now[lo] == "N" else images[lo:hi]
             if mom is not None:
-                ops.linf_momentum_step(cur[lo:hi], grad[lo:hi], None if now[lo] == "N" else images[lo:hi], mom[lo:hi],
-                                       c.decay_factor, c.eps_iter, c.eps, c.clip_min, c.clip_max, out=cur[lo:hi])
+                g = grad[lo:hi] if ti is None else ops.ti_smooth(grad[lo:hi], ti.taps, out=ti.ghat[lo:hi])
+                ops.linf_momentum_step(cur[lo:hi], g, x0, mom[lo:hi], c.decay_factor, c.eps_iter, c.eps, c.clip_min,
+                                       c.clip_max, out=cur[lo:hi])
+            elif ti is not None:
+                ops.linf_ti_step(cur[lo:hi], grad[lo:hi], x0, ti.taps, c.eps_iter, c.eps, c.clip_min, c.clip_max,
+                                 out=cur[lo:hi])
             elif now[lo] == "N":
                 ops.linf_fgm(cur[lo:hi], grad[lo:hi], c.eps_iter, c.clip_min, c.clip_max, out=cur[lo:hi])
             else:

@@ -83,6 +83,31 @@ def _validate_decay(decay_factor):
     return decay
 
 
+def _validate_ti(ti_kernel):
+    """None (TI smoothing off) or the taps as a numpy float32 array: an odd int ``kernlen`` in 1..31 selects the TI
+    paper's Gaussian taps (nsig = 3), a 1-D sequence of an odd number <= 31 of finite floats is used as the taps.
+    Raised before any tensor is looked at, like the other arguments."""
+    if ti_kernel is None:
+        return None
+    if isinstance(ti_kernel, (bool, np.bool_)):
+        raise ValueError("ti_kernel must be None, an odd int in 1..31 or a 1-D sequence of taps, got {!r}".format(ti_kernel))
+    if isinstance(ti_kernel, (int, np.integer)):
+        k = int(ti_kernel)
+        if k < 1 or k > ops.TI_MAX_TAPS or k % 2 == 0:
+            raise ValueError("ti_kernel must be an odd kernel length in 1..{}, got {}".format(ops.TI_MAX_TAPS, k))
+        return ops.ti_gaussian_taps(k, 3.0)
+    try:
+        taps = np.asarray(ti_kernel, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError("ti_kernel must be None, an odd int in 1..31 or a 1-D sequence of taps, got {!r}".format(ti_kernel))
+    if taps.ndim != 1 or taps.size < 1 or taps.size > ops.TI_MAX_TAPS or taps.size % 2 == 0:
+        raise ValueError("ti_kernel taps must be 1-D with an odd length in 1..{}, got shape {}".format(
+            ops.TI_MAX_TAPS, taps.shape))
+    if not np.all(np.isfinite(taps)):
+        raise ValueError("ti_kernel taps must be finite")
+    return taps
+
+
 def _two_sided(clip_min, clip_max):
     if (clip_min is not None or clip_max is not None) and (clip_min is None or clip_max is None):
         raise ValueError("One of clip_min and clip_max is None but we don't currently support one-sided clipping")
@@ -335,10 +360,40 @@ class _Momentum:
         return ops.sumabs_per_sample(grad, out=self.sumabs, ws=self.ws)
 
 
-def _fgm_update(x, grad, eps, norm, clip_min, clip_max, flag=None, out=None, check_range=True, mom=None):
+class _Smoother:
+    """The TI-FGSM state of one operator call: the taps and -- allocated once, so that a captured iteration finds it at a
+    static address -- one tensor for the smoothed gradient.  ``scratch=False``: the caller only runs the fused L-inf step
+    (``ops.linf_ti_step``), which keeps the smoothed gradient in registers."""
+
+    def __init__(self, taps, like, scratch=True):
+        self.taps = taps
+        self.ghat = torch.empty_like(like, memory_format=torch.contiguous_format) if scratch else None
+
+    def smooth(self, grad):
+        return ops.ti_smooth(grad, self.taps, out=self.ghat)
+
+
+def _smoother(taps, like, norm, decay):
+    """None without TI; the scratch is needed by every update but the plain L-inf one."""
+    if taps is None:
+        return None
+    if like.dim() != 4:
+        raise ValueError("ti_kernel needs a (B, C, H, W) image: the stencil runs over its (H, W) planes, got shape {}".format(
+            tuple(like.shape)))
+    return _Smoother(taps, like, scratch=decay is not None or norm != np.inf)
+
+
+def _fgm_update(x, grad, eps, norm, clip_min, clip_max, flag=None, out=None, check_range=True, mom=None, ti=None):
     """``flag``: range violations of ``x`` (``check_range``) and, for the L2 / L1 updates, the degenerate-gradient bit
     that stands for the self-check asserts of the reference's ``optimize_linear`` (utils.py:101-104, :110-116).
-    ``mom``: accumulate ``grad`` into the momentum first and step along the momentum instead."""
+    ``mom``: accumulate ``grad`` into the momentum first and step along the momentum instead.
+    ``ti``: smooth ``grad`` first (TI-FGSM; with momentum the smoothed gradient is what gets normalised and accumulated,
+    TI-MI-FGSM); the plain L-inf update does both in one launch."""
+    if ti is not None:
+        if mom is None and norm == np.inf:
+            return ops.linf_ti_step(x, grad, None, ti.taps, eps, 0.0, clip_min, clip_max,
+                                    flag=flag if check_range else None, out=out)
+        grad = ti.smooth(grad)
     if mom is not None and norm == np.inf:
         return ops.linf_momentum_step(x, grad, None, mom.m, mom.decay, eps, 0.0, clip_min, clip_max,
                                       flag=flag if check_range else None, out=out, sumabs=mom.sums(grad))
@@ -351,7 +406,11 @@ def _fgm_update(x, grad, eps, norm, clip_min, clip_max, flag=None, out=None, che
     return ops.l1_fgm(x, grad, eps, clip_min, clip_max, flag=flag, out=out, check_range=check_range)
 
 
-def _fgm_then_project(x, grad, x0, eps_iter, eps, norm, clip_min, clip_max, out, flag=None, mom=None):
+def _fgm_then_project(x, grad, x0, eps_iter, eps, norm, clip_min, clip_max, out, flag=None, mom=None, ti=None):
+    if ti is not None:
+        if mom is None and norm == np.inf:
+            return ops.linf_ti_step(x, grad, x0, ti.taps, eps_iter, eps, clip_min, clip_max, out=out)
+        grad = ti.smooth(grad)
     if mom is not None and norm == np.inf:
         return ops.linf_momentum_step(x, grad, x0, mom.m, mom.decay, eps_iter, eps, clip_min, clip_max, out=out,
                                       sumabs=mom.sums(grad))
@@ -393,11 +452,14 @@ def _grad_of(leaf):
 
 # ----------------------------------------------------------------------------------------- FGM
 def fast_gradient_method(model_fn, x, eps, norm, ori_x, clip_min=None, clip_max=None, y=None, targeted=False,
-                         sanity_checks=False, ls=None, bkp=None, bkp_y=None, *, flavor=ALBEF, per_sample=False):
+                         sanity_checks=False, ls=None, bkp=None, bkp_y=None, *, flavor=ALBEF, per_sample=False,
+                         ti_kernel=None):
     """One FGM step; returns ``(adv_x, loss)`` (``loss`` is a 0-d device tensor), bare ``x`` when ``eps == 0``.
+    ``ti_kernel`` (extension, keyword-only): TI-FGSM smoothing of the gradient, as in ``projected_gradient_descent``.
     Reference: A fast_gradient_method.py:30-165, V :36-152 (the VLMO copy has no ``bkp``/``bkp_y``)."""
     _check_flavor(flavor)
     _validate_fgm(norm, eps, clip_min, clip_max)
+    taps = _validate_ti(ti_kernel)
     if eps == 0:
         return x
     xin = _as_image(x)
@@ -408,18 +470,21 @@ def fast_gradient_method(model_fn, x, eps, norm, ori_x, clip_min=None, clip_max=
     _loss_and_grad(model_fn, [leaf], leaf, y, ls, flavor, targeted, _LossSlot(loss_buf, 0), bkp=bkp, bkp_y=bkp_y,
                    flag=flag, per_sample=per_sample)
     _two_sided(clip_min, clip_max)
-    adv = _fgm_update(xin, _grad_of(leaf), eps, norm, clip_min, clip_max, flag=flag, check_range=check_range)
+    adv = _fgm_update(xin, _grad_of(leaf), eps, norm, clip_min, clip_max, flag=flag, check_range=check_range,
+                      ti=_smoother(taps, xin, norm, None))
     assert _check_flag(flag, norm, sanity_checks), "input x is outside [clip_min, clip_max]"
     return adv, loss_buf[0]
 
 
 def fast_gradient_method_vl(model_fn, x, eps, norm, ori_x, clip_min=None, clip_max=None, y=None, targeted=False,
-                            sanity_checks=False, ls=None, text_emb_pick=None, *, flavor=ALBEF):
+                            sanity_checks=False, ls=None, text_emb_pick=None, *, flavor=ALBEF, ti_kernel=None):
     """FGM on ``x = [image, text_embeds]``; returns ``(adv_image, text_grad[:, text_emb_pick])``.
+    ``ti_kernel`` (extension, keyword-only): TI-FGSM smoothing of the IMAGE gradient, as in ``projected_gradient_descent``.
     Like the reference it replaces ``x[0]``/``x[1]`` of the caller's list by the leaf tensors.
     Reference: A fast_gradient_method_vl.py:30-130, V :34-141."""
     _check_flavor(flavor)
     _validate_fgm(norm, eps, clip_min, clip_max)
+    taps = _validate_ti(ti_kernel)
     if eps == 0:
         return x
     img = _as_image(x[0], "x[0]")
@@ -432,7 +497,8 @@ def fast_gradient_method_vl(model_fn, x, eps, norm, ori_x, clip_min=None, clip_m
     _loss_and_grad(model_fn, [x[0], x[1]], [x[0], x[1]], y, ls, flavor, targeted, _LossSlot(loss_buf, 0), vl=True)
     text_grad = ops.gather_rows(_grad_of(x[1]), text_emb_pick)
     _two_sided(clip_min, clip_max)
-    adv = _fgm_update(img, _grad_of(x[0]), eps, norm, clip_min, clip_max, flag=flag, check_range=check_range)
+    adv = _fgm_update(img, _grad_of(x[0]), eps, norm, clip_min, clip_max, flag=flag, check_range=check_range,
+                      ti=_smoother(taps, img, norm, None))
     assert _check_flag(flag, norm, sanity_checks), "input x is outside [clip_min, clip_max]"
     return adv, text_grad
 
@@ -466,7 +532,7 @@ def _finish(flag, eps, eps_iter, norm, clip_min, clip_max, sanity_checks):
 
 
 def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, clip_min, clip_max, nb_iter, loss_buf,
-                       mom=None):
+                       mom=None, ti=None):
     """``nb_iter`` feature-loss L-inf iterations with iterations 1.. replayed from ONE captured hipGraph.
 
     For the launch-bound regime (the reference's own batch 1: ~10^3 kernels of a few microseconds per iteration):
@@ -478,6 +544,8 @@ def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, cl
     is not; use ``mlm_probability=0`` or eager mode there).
     ``mom``: the |grad| reduction and the fused momentum step take the place of the step inside the captured iteration;
     the momentum, the per-sample sums and the reduction's workspace were allocated before capture.
+    ``ti``: the fused TI step (or smoothing + reduction + momentum step) is what the iteration captures; the taps travel in
+    the kernel arguments and the smoothed-gradient scratch was allocated before capture.
     """
     word = torch.zeros(1, dtype=torch.float32, device=cur.device)
 
@@ -485,7 +553,7 @@ def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, cl
         leaf = cur.detach().requires_grad_(True)
         _loss_and_grad(model_fn, [leaf], leaf, y, 1, flavor, targeted, _LossSlot(word, 0))
         _fgm_then_project(cur, _grad_of(leaf), x0, eps_iter, eps, np.inf, clip_min, clip_max, cur,   # in place: static
-                          mom=mom)                                                                    # address
+                          mom=mom, ti=ti)                                                             # address
 
     main = torch.cuda.current_stream(cur.device)
     side = torch.cuda.Stream(device=cur.device)
@@ -507,7 +575,7 @@ def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, cl
 def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_min=None, clip_max=None, y=None,
                                ori_x=None, time=None, targeted=False, rand_init=True, rand_minmax=None,
                                sanity_checks=True, ls=None, *, flavor=ALBEF, init_eta=None, graph=None,
-                               per_sample=False, decay_factor=None, momentum=None):
+                               per_sample=False, decay_factor=None, momentum=None, ti_kernel=None):
     """PGD over a frozen white box; returns ``(adv_x, loss_list)``, bare ``x`` when eps or eps_iter is 0.
 
     ``ls == 1``: feature loss, ``model_fn`` a callable.  Otherwise the dual-loss loop: ``model_fn = [feature_fn,
@@ -528,11 +596,19 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
     loop accumulates twice per iteration into the same ``m`` (feature gradient, then MLM gradient).  ``momentum``: the
     fp32 device tensor of ``x``'s shape that holds ``m``; it is updated in place, so a driver can carry it over several
     calls (None: zeros for this call).  With ``decay_factor=None`` (default) nothing changes and ``momentum`` is ignored.
+    ``ti_kernel`` (extension, keyword-only): not None turns every update into TI-FGSM's (Dong et al. 2019; the reference
+    tree has it in no framework): each image gradient is convolved per (H, W) plane with a separable kernel, zero padded,
+    before the update -- an odd int ``kernlen`` in 1..31 selects the paper's Gaussian (``ops.ti_gaussian_taps(kernlen,
+    3)``), a 1-D sequence of an odd number <= 31 of finite floats is used as the taps.  The L-inf update does it in one
+    launch (``ops.linf_ti_step``); with ``decay_factor`` the smoothed gradient is what is normalised and accumulated
+    (TI-MI-FGSM); L2 smooths in front of the existing update; the dual loop smooths both gradients.  ``x`` must be
+    ``(B, C, H, W)``.  With ``ti_kernel=None`` (default) nothing changes.
     Reference: A projected_gradient_descent.py:10-199, V :10-196.
     """
     _check_flavor(flavor)
     unchanged = _validate_pgd(norm, eps, eps_iter, clip_min, clip_max)
     decay = _validate_decay(decay_factor)
+    taps = _validate_ti(ti_kernel)
     if unchanged:
         return x
     xin = _as_image(x)
@@ -550,6 +626,7 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
     loss_buf = torch.zeros(max(nb_iter, 1) * (2 if dual else 1), dtype=torch.float32, device=xin.device)
     n_loss = 0
     mom = None if decay is None else _Momentum(decay, xin, momentum)
+    ti = _smoother(taps, xin, norm, decay)
     ws = ops.Workspace()       # loss-gradient / CE scratch buffers live for the whole call, not per iteration
     bad_flag = flag if flag is not None else (
         ops.new_flag(xin.device) if ((dual and sanity_checks) or norm != np.inf) else None)
@@ -560,7 +637,7 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
             raise ValueError("graph=True supports the feature-loss (ls == 1) L-inf loop only")
         _two_sided(clip_min, clip_max)
         adv = _graphed_linf_loop(model_fn, adv, x0, y, flavor, targeted, eps_iter, eps, clip_min, clip_max, nb_iter,
-                                 loss_buf, mom=mom)
+                                 loss_buf, mom=mom, ti=ti)
         n_loss, nb_iter = nb_iter, 0
     for _ in range(nb_iter):
         if not dual:
@@ -570,7 +647,7 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
             n_loss += 1
             _two_sided(clip_min, clip_max)
             adv = _fgm_then_project(adv, _grad_of(leaf), x0, eps_iter, eps, norm, clip_min, clip_max, buf[1 - cur],
-                                    flag=bad_flag, mom=mom)
+                                    flag=bad_flag, mom=mom, ti=ti)
         else:
             if flavor == ALBEF:      # A :163,177-181 slices y; V :162,175 passes it whole
                 y_feat, y_mlm, extra = [y[1], y[2]], [y[0]], dict(bkp=model_fn[0], bkp_y=[y[1], y[2]])
@@ -582,13 +659,13 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
             n_loss += 1
             _two_sided(clip_min, clip_max)
             mid = _fgm_update(adv, _grad_of(leaf), eps_iter, norm, clip_min, clip_max, out=buf[1 - cur], flag=bad_flag,
-                              check_range=False, mom=mom)
+                              check_range=False, mom=mom, ti=ti)
             leaf = mid.detach().requires_grad_(True)
             _loss_and_grad(model_fn[1], [leaf], leaf, y_mlm, 0, flavor, targeted, _LossSlot(loss_buf, n_loss), ws=ws,
                            flag=bad_flag, per_sample=per_sample, **extra)
             n_loss += 1
             adv = _fgm_then_project(mid, _grad_of(leaf), x0, eps_iter, eps, norm, clip_min, clip_max, buf[cur],
-                                    flag=bad_flag, mom=mom)
+                                    flag=bad_flag, mom=mom, ti=ti)
             cur = 1 - cur            # result sits in buf[cur] again after the flip below
         cur = 1 - cur
         del leaf
@@ -600,15 +677,17 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
 def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, clip_min=None, clip_max=None, y=None,
                                   ori_x=None, time=None, targeted=False, rand_init=True, rand_minmax=None,
                                   sanity_checks=True, ls=None, attack_mask=None, *, flavor=ALBEF, init_eta=None,
-                                  decay_factor=None, momentum=None):
+                                  decay_factor=None, momentum=None, ti_kernel=None):
     """PGD on ``x = [image, text_embeds]`` (only the image moves); returns ``(adv_image, text_embed_gradient)`` of
     the last iteration.  Only ``ls == 1`` is supported (``ValueError`` otherwise), as in the reference.
     ``decay_factor`` / ``momentum`` (extensions, keyword-only): MI-FGSM on the image, as in
-    ``projected_gradient_descent``; ``momentum`` has the image's shape.
+    ``projected_gradient_descent``; ``momentum`` has the image's shape.  ``ti_kernel`` (extension, keyword-only):
+    TI-FGSM smoothing of the image gradient, as there.
     Reference: A projected_gradient_descent_vl.py:10-168, V :10-164."""
     _check_flavor(flavor)
     unchanged = _validate_pgd(norm, eps, eps_iter, clip_min, clip_max)
     decay = _validate_decay(decay_factor)
+    taps = _validate_ti(ti_kernel)
     if unchanged:
         return x
     img = _as_image(x[0], "x[0]")
@@ -627,6 +706,7 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
     loss_buf = torch.zeros(max(nb_iter, 1), dtype=torch.float32, device=img.device)
     ws = ops.Workspace()
     mom = None if decay is None else _Momentum(decay, img, momentum)
+    ti = _smoother(taps, img, norm, decay)
     if attack_mask is not None and not isinstance(attack_mask, ops.RowIndex):   # validated + uploaded once per call
         attack_mask = ops.RowIndex(attack_mask, emb.shape[1], emb.device)
     for it in range(nb_iter):
@@ -637,7 +717,7 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
         text_grad = ops.gather_rows(_grad_of(leaf_txt), attack_mask)
         _two_sided(clip_min, clip_max)
         adv = _fgm_then_project(adv, _grad_of(leaf_img), x0, eps_iter, eps, norm, clip_min, clip_max, buf[1 - cur],
-                                flag=flag, mom=mom)
+                                flag=flag, mom=mom, ti=ti)
         cur = 1 - cur
         del leaf_img, leaf_txt
     _finish(flag, eps, eps_iter, norm, clip_min, clip_max, sanity_checks)
@@ -647,7 +727,7 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
 # ----------------------------------------------------------------------------------------- MI-FGSM
 def momentum_iterative_method(model_fn, x, eps, eps_iter, nb_iter, norm, clip_min=None, clip_max=None, y=None,
                               ori_x=None, targeted=False, decay_factor=1.0, sanity_checks=True, ls=1, *, flavor=ALBEF,
-                              graph=None, momentum=None):
+                              graph=None, momentum=None, ti_kernel=None):
     """The momentum iterative method (Dong et al. 2017) on this project's losses; returns ``(adv_x, loss_list)`` like
     ``projected_gradient_descent``, so a driver can swap one for the other.
 
@@ -655,11 +735,11 @@ def momentum_iterative_method(model_fn, x, eps, eps_iter, nb_iter, norm, clip_mi
     it to the torch operators its drivers call.  As there, the loop starts at ``x`` itself (no random start, :80-81),
     ``norm == 1`` is refused first (:54-60) and every iteration normalises the gradient by its per-sample mean absolute
     value, adds it to ``decay_factor`` times the momentum (:88-95) and steps along the momentum (:97-103).  ``ori_x``
-    (centre of the eps-ball) defaults to ``x``; ``ls``, ``flavor``, ``graph`` and ``momentum`` as in
-    ``projected_gradient_descent``, which runs the loop."""
+    (centre of the eps-ball) defaults to ``x``; ``ls``, ``flavor``, ``graph``, ``momentum`` and ``ti_kernel``
+    (TI-MI-FGSM, the combination the TI paper recommends) as in ``projected_gradient_descent``, which runs the loop."""
     if norm != 1 and decay_factor is None:
         raise ValueError("decay_factor must be a number (use projected_gradient_descent for the attack without momentum)")
     return projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_min=clip_min, clip_max=clip_max,
                                       y=y, ori_x=x if ori_x is None else ori_x, time=None, targeted=targeted,
                                       sanity_checks=sanity_checks, ls=ls, flavor=flavor, graph=graph,
-                                      decay_factor=decay_factor, momentum=momentum)
+                                      decay_factor=decay_factor, momentum=momentum, ti_kernel=ti_kernel)

@@ -241,6 +241,7 @@ int vqa_loss_set_option(int which, int value);   // loss.hip
 int vqa_attn_set_option(int value);              // attn.hip
 int vqa_block_set_option(int value);             // block.hip
 int vqa_momentum_set_option(int value);          // lnorm.hip
+int vqa_ti_set_option(int value);                // ti.hip
 
 int vqa_set_option(int option, int value) {
   switch (option) {
@@ -274,6 +275,8 @@ int vqa_set_option(int option, int value) {
       return vqa_loss_set_option(option, value);
     case 13:
       return vqa_momentum_set_option(value);
+    case 14:
+      return vqa_ti_set_option(value);
     default:
       return VQA_ERR_SHAPE;
   }

@@ -6,6 +6,7 @@ Every function launches on the current HIP stream of its tensors' device and ret
 import contextlib
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _hip
@@ -345,6 +346,76 @@ def linf_momentum_step(x, g, x0, m, decay, eps_iter, eps, clip_min, clip_max, fl
         check(lib().vqa_linf_momentum_step(ptr(x), ptr(g), ptr(sumabs), ptr(x0), ptr(m), ptr(out), batch, n_per, float(decay),
                                            eps_iter, eps, lo, hi, mode, ptr(flag), stream_for(x)),
               "vqa_linf_momentum_step")
+    return out
+
+
+# ----------------------------------------------------------------------------------------- TI smoothing (TI-FGSM)
+TI_MAX_TAPS = 31
+
+
+def ti_gaussian_taps(kernlen=15, nsig=3.0):
+    """The 1-D taps of the TI paper's ``gkern(kernlen, nsig)`` (Dong et al. 2019): the normal density at
+    ``linspace(-nsig, nsig, kernlen)``, normalised in float64, as a numpy float32 array.  The paper's 2-D kernel is the
+    outer product of these taps."""
+    kernlen = int(kernlen)
+    if kernlen < 1:
+        raise ValueError("kernlen must be at least 1, got {}".format(kernlen))
+    x = np.linspace(-float(nsig), float(nsig), kernlen)
+    k = np.exp(-0.5 * x * x)
+    return (k / k.sum()).astype(np.float32)
+
+
+def _ti_taps(taps):
+    """(ctypes float array, K) of a host tap sequence: what the kernels take by value in their arguments."""
+    w = np.ascontiguousarray(taps, dtype=np.float32)
+    if w.ndim != 1 or w.size < 1 or w.size > TI_MAX_TAPS or w.size % 2 == 0:
+        raise ValueError("taps must be a 1-d sequence of an odd number (1..{}) of floats, got shape {}".format(
+            TI_MAX_TAPS, w.shape))
+    return (ctypes.c_float * w.size)(*w.tolist()), int(w.size)
+
+
+def _ti_planes(g):
+    dev_f32(g, "grad", contiguous=False)
+    if g.dim() != 4 or not g.is_contiguous():
+        raise ValueError("grad must be a contiguous (B, C, H, W) tensor: the stencil runs over row-major planes")
+    return g.shape[0] * g.shape[1], g.shape[2], g.shape[3]
+
+
+def ti_smooth(g, taps, out=None):
+    """``out = ghat``: every (H, W) plane of ``g`` convolved with the separable ``taps`` (rows, then columns), zero
+    padded; the bit-level contract is in ``include/vqattack_hip.h``.  ``out`` is used as given and must not be ``g``."""
+    planes, h, w = _ti_planes(g)
+    same_device(g, out)
+    buf, k = _ti_taps(taps)
+    out = _out_like(g, out)
+    if g.numel() == 0:
+        return out
+    with _on(g):
+        check(lib().vqa_ti_smooth(ptr(g), ptr(out), planes, h, w, buf, k, stream_for(g)), "vqa_ti_smooth")
+    return out
+
+
+def linf_ti_step(x, g, x0, taps, eps_iter, eps, clip_min, clip_max, flag=None, out=None):
+    """``ti_smooth`` and ``linf_step`` on the smoothed gradient in one pass, 16 B/element; ``x0=None``: and ``linf_fgm``
+    (no projection), 12 B/element.  The smoothed gradient never reaches memory; ``out`` may be ``x``."""
+    dev_f32(x, "x")
+    if x0 is not None:
+        dev_f32(x0, "ori_x")
+    planes, h, w = _ti_planes(g)
+    if g.shape != x.shape or (x0 is not None and x0.shape != x.shape):
+        raise ValueError("shape mismatch: x {}, grad {}, ori_x {}".format(
+            tuple(x.shape), tuple(g.shape), None if x0 is None else tuple(x0.shape)))
+    same_device(x, g, x0, out, flag)
+    buf, k = _ti_taps(taps)
+    out = _out_like(x, out)
+    mode, lo, hi = _clip_args(clip_min, clip_max)
+    if flag is not None and mode:
+        mode |= VQA_CHECK_RANGE
+    if x.numel() == 0:
+        return out
+    with _on(x):
+        check(lib().vqa_linf_ti_step(ptr(x), ptr(g), ptr(x0), ptr(out), planes, h, w, buf, k, eps_iter, eps, lo, hi, mode,
+                                     ptr(flag), stream_for(x)), "vqa_linf_ti_step")
     return out
 
 
