@@ -55,6 +55,11 @@ def parse(argv=None):
                     help="MI-FGSM momentum decay of the image attack (Dong et al. 2017); absent: plain PGD")
     ap.add_argument("--ti_kernel", default=None, type=int,
                     help="TI-FGSM Gaussian kernel length of the image attack (Dong et al. 2019; odd, 1..31); absent: off")
+    ap.add_argument("--diversity_prob", default=None, type=float,
+                    help="DI-FGSM probability of the random shrink-and-pad transform of the image attack (Xie et al. 2019; "
+                         "the reference's input_diversity); absent: off")
+    ap.add_argument("--di_shrink", default=32, type=int, help="DI-FGSM: new_h is drawn from [H - di_shrink, H)")
+    ap.add_argument("--di_seed", default=None, type=int, help="DI-FGSM: seed of the geometry draws; absent: unseeded")
     ap.add_argument("--mlm_checkpoint", default="", help="BertForMaskedLM state dict -> candidate proposer (adv_attack.py:110)")
     ap.add_argument("--answer_list", default=None,
                     help="ALBEF answer_list json (configs: answer_list): the victim ranks it and acc_vqa compares answer "
@@ -127,7 +132,8 @@ def main():
                     max_words=4 if args.tiny else 12, dual_every=args.dual_every, mixed=args.mixed,
                     force_collective=dist.is_initialized(), source=source, mlm_logits_fn=proposer, banned_ids=banned,
                     config=AttackConfig(sim_threshold=args.sim_threshold, decay_factor=args.decay_factor,
-                                        ti_kernel=args.ti_kernel),
+                                        ti_kernel=args.ti_kernel, diversity_prob=args.diversity_prob,
+                                        di_shrink=args.di_shrink, di_seed=args.di_seed),
                     scoring=scoring)
     finish(rank, world, res, os.path.join(args.output_dir, "adv_txt.json") if args.output_dir else None,
            os.path.join(args.output_dir, "adv_txt_dict_albef.txt") if args.output_dir and scoring else None)

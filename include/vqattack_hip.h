@@ -207,6 +207,63 @@ int vqa_linf_ti_step(const float* x, const float* g, const float* x0, float* out
                      const float* taps_host, int ktaps, float eps_iter, float eps, float cmin, float cmax, unsigned mode,
                      int* flag, vqa_stream_t stream);
 
+/* ---------------------------------------------------------------- input diversity (DI-FGSM, Xie et al. 2019)
+ * The reference defines the transform for torch (cleverhans/fgsm_copy.py:9-31, `input_diversity`: a bilinear shrink to
+ * (new_h, new_w) and zero padding back to (H, W) at a random offset) and never calls it.  Here it acts per sample on
+ * every row-major (height, width) plane of a contiguous (batch, channels, height, width) tensor.  geom is a DEVICE
+ * table of int32 rows [new_h, new_w, top, left], one per sample, with 1 <= new_h <= height, 1 <= new_w <= width,
+ * 0 <= top <= height - new_h, 0 <= left <= width - new_w (a downscale only); it is read by the kernel, so a captured
+ * launch sees whatever the table holds at replay.  A row outside these ranges is taken as the identity row
+ * [height, width, 0, 0]; no flag is raised for it and no address outside the plane is formed, whatever the table holds.
+ *
+ * Per axis (full -> new), all in fp32, for destination coordinate d in 0 .. new - 1:
+ *   scale = (float)full / (float)new;   src = scale * ((float)d + 0.5f) - 0.5f;
+ *   i0 = floor(src);  i1 = i0 + 1;  l1 = src - (float)i0;  l0 = 1.0f - l1
+ * (each operation rounded once, no contraction).  For new < full no clamp is needed: src >= 0, i1 <= full - 1 and i0 is
+ * strictly increasing in d.  An axis with new == full is the identity on that axis: the single term i0 = d with weight
+ * 1, and no term with a zero weight (so nothing at d + 1 is read).
+ *
+ * Forward, D = T(x): inside the new_h x new_w window at (top, left),
+ *   D[top + dy, left + dx] = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * c + lx1 * d),
+ *   a = x[y0, x0], b = x[y0, x1], c = x[y1, x0], d = x[y1, x1],
+ * one fp32 multiply per product and one fp32 add per sum; on an identity axis the blend of that axis is its first
+ * operand itself (x identity: a and c in place of the inner sums; y identity: the upper inner sum).  +0.0f outside the
+ * window.  A source pixel that no destination references is not read into the result.
+ *
+ * Adjoint, g = T^T(gD), as a gather (deterministic, no atomics):
+ *   t[dy, sx] = sum over the dx with i0(dx) == sx or i1(dx) == sx, in ascending dx, of wx * gD[top + dy, left + dx]
+ *   g[sy, sx] = sum over the dy with i0(dy) == sy or i1(dy) == sy, in ascending dy, of wy * t[dy, sx]
+ * where wx / wy is the l0 or l1 that the forward gives that pair (1 on an identity axis); each sum starts at +0.0f and
+ * takes one fp32 multiply and one fp32 add per term.  A source coordinate has at most two contributors per axis (i0 is
+ * strictly increasing); one with none gets +0.0f.  gD outside the window is never read into the result.  With the
+ * identity row the adjoint returns gD with -0 as +0, the forward returns x bit for bit.
+ *
+ * One workgroup per 64 x 32 tile of one plane; the adjoint builds the per-axis (destination, weight) tables of its tile
+ * in LDS from the forward's own arithmetic, stages the window rows it needs there and runs both passes on chip.
+ * Return codes, all before the first HIP call: a NULL x / gD / geom / out, or VQA_CHECK_RANGE without flag,
+ * VQA_ERR_NULL; a negative extent, batch * channels * tiles beyond the 2^31 - 1 workgroups of one launch, or the input
+ * of the transform or of the adjoint being `out`, VQA_ERR_SHAPE; a pointer (geom included) not 4-byte aligned
+ * VQA_ERR_ALIGN; any zero extent VQA_OK, no launch.  16-byte accesses are used where width % 4 == 0 and the pointers
+ * allow.  No allocation, no copy, no sync: capture-safe.
+ */
+
+/* out = T(x).  8 B/element (the 2 x 2 gathers of x hit L1 / L2).  x must not alias out. */
+int vqa_di_transform(const float* x, const int* geom, float* out, int batch, int channels, int height, int width,
+                     vqa_stream_t stream);
+
+/* out = T^T(gD): in front of vqa_ti_smooth, the momentum kernels and the L2 / L1 updates.  gD must not alias out. */
+int vqa_di_adjoint(const float* gD, const int* geom, float* out, int batch, int channels, int height, int width,
+                   vqa_stream_t stream);
+
+/* The adjoint above and the L-infinity update in ONE pass: out = vqa_linf_step(x, T^T(gD), x0), or, for x0 == NULL,
+ * out = vqa_linf_fgm(x, T^T(gD)) -- bit for bit what vqa_di_adjoint followed by that launch gives; the image gradient
+ * never goes to memory.  At most 16 B/element (12 without x0; gD is read inside the window only), against 24 for the
+ * two launches.  `out` may alias `x` (each element of x is read only by the thread that writes it); gD must not alias
+ * out.  mode / flag as in vqa_linf_step. */
+int vqa_linf_di_step(const float* x, const float* gD, const float* x0, const int* geom, float* out, int batch,
+                     int channels, int height, int width, float eps_iter, float eps, float cmin, float cmax,
+                     unsigned mode, int* flag, vqa_stream_t stream);
+
 /* ---------------------------------------------------------------- cross-modal loss reduction
  * Rows of D contiguous floats, addressed as row(o, i) = base + o*stride0 + i*stride1 (strides in ELEMENTS) for
  * o < rows0, i < rows1 -- this is how the reference's `out[k][:, :feat_len, :]` truncation views are consumed

@@ -53,6 +53,9 @@ SIGNATURES = {
     "vqa_linf_momentum_step": (_i, [_p, _p, _p, _p, _p, _p, _i, _sz, _f, _f, _f, _f, _f, _u, _p, _p]),
     "vqa_ti_smooth": (_i, [_p, _p, _i, _i, _i, _p, _i, _p]),
     "vqa_linf_ti_step": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _i, _f, _f, _f, _f, _u, _p, _p]),
+    "vqa_di_transform": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "vqa_di_adjoint": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "vqa_linf_di_step": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _f, _u, _p, _p]),
     "vqa_neg_cos_partials": (_i, []),
     "vqa_neg_cos_rows": (_i, [_p, _p, _p, _p, _p, _l, _l, _l, _i, _l, _l, _l, _l, _l, _l, _f, _f, _p, _i, _p]),
     "vqa_neg_cos_max_layers": (_i, []),

@@ -45,6 +45,9 @@ class AttackConfig:
     live_mlm_rows: bool = True         # dual loss: MLM head + cross entropy at the live label rows only (False: dense B x L)
     decay_factor: Optional[float] = None   # not None: MI-FGSM, one momentum buffer per attack (attacks.projected_gradient_descent)
     ti_kernel: object = None               # not None: TI-FGSM smoothing of every image gradient (odd kernel length 1..31 or taps)
+    diversity_prob: Optional[float] = None # not None: DI-FGSM, every gradient is taken at a randomly shrunk and padded image
+    di_shrink: int = 32                    # DI: new_h is drawn from [H - di_shrink, H) (the reference's 32)
+    di_seed: Optional[int] = None          # DI: seed of the np.random.RandomState each attack call draws its rows from
 
     def __post_init__(self):
         attacks._validate_decay(self.decay_factor)
@@ -55,6 +58,13 @@ class AttackConfig:
         if self.ti_kernel is not None and self.patch_layout:
             # the stencil runs over row-major (H, W) planes: a patch-major image has none
             raise ValueError("ti_kernel and patch_layout=True cannot be combined")
+        attacks._validate_di(self.diversity_prob, self.di_shrink)
+        if self.di_seed is not None and (isinstance(self.di_seed, bool) or not isinstance(self.di_seed, (int, np.integer))
+                                         or not 0 <= int(self.di_seed) < 2 ** 32):
+            raise ValueError("di_seed must be None or an int in [0, 2^32), got {!r}".format(self.di_seed))
+        if self.diversity_prob is not None and self.patch_layout:
+            # the transform resamples row-major (H, W) planes: a patch-major image has none
+            raise ValueError("diversity_prob and patch_layout=True cannot be combined")
 
 
 @dataclass
@@ -102,6 +112,18 @@ class BatchedVQAttack:
         ns = dropin.load(flavor)
         self.pgd = ns.projected_gradient_descent.projected_gradient_descent
         self.pgd_vl = ns.projected_gradient_descent_vl.projected_gradient_descent
+        self.di_rng = None        # DI: set to anything with .uniform to draw from it instead of RandomState(cfg.di_seed)
+        self._di_draws = None     # the generator of the attack call that is running
+
+    def _start_di(self):
+        """DI-FGSM: one generator per attack_batch / attack_mixed call; every operator call inside draws its rows from
+        it in turn (4 draws per sample and gradient evaluation, ops.di_draw)."""
+        c = self.cfg
+        if c.diversity_prob is None:
+            self._di_draws = None
+        else:
+            self._di_draws = self.di_rng if self.di_rng is not None else np.random.RandomState(c.di_seed)
+        return self._di_draws
 
     # the y lists the reference passes (adv_attack.py:609,637; vlmo_module.py:1948,1975)
     def _y_feature(self, targets):
@@ -124,7 +146,8 @@ class BatchedVQAttack:
         c = self.cfg
         common = dict(clip_min=c.clip_min, clip_max=c.clip_max, time=time, ori_x=clean,
                       sanity_checks=c.sanity_checks, init_eta=init_eta, decay_factor=c.decay_factor, momentum=momentum,
-                      ti_kernel=c.ti_kernel)
+                      ti_kernel=c.ti_kernel, diversity_prob=c.diversity_prob, di_shrink=c.di_shrink,
+                      di_rng=self._di_draws)
         a = self.adapters
         if not dual:
             return self.pgd(a.pgd_attack, adv, c.eps, c.eps_iter, steps, c.norm, y=self._y_feature(targets), ls=1,
@@ -197,6 +220,7 @@ class BatchedVQAttack:
                 a.set_mlm_rows(None)
         targets = a.gen_ori_feats(images)
         mom = self._new_momentum(images)         # carried through every PGD block and every probe of this attack
+        self._start_di()                         # DI-FGSM: one generator for every operator call of this attack
         res = BatchResult(adv_images=adv, adv_text_ids=adv_ids)
         first_time = 0 if c.random_start else 1
         rounds = []
@@ -234,7 +258,9 @@ class BatchedVQAttack:
                                                  1, c.norm, clip_min=c.clip_min, clip_max=c.clip_max,
                                                  y=self._y_feature(targets), time=1, ori_x=images, ls=1,
                                                  attack_mask=positions, sanity_checks=c.sanity_checks,
-                                                 decay_factor=c.decay_factor, momentum=mom, ti_kernel=c.ti_kernel)
+                                                 decay_factor=c.decay_factor, momentum=mom, ti_kernel=c.ti_kernel,
+                                                 diversity_prob=c.diversity_prob, di_shrink=c.di_shrink,
+                                                 di_rng=self._di_draws)
                 res.gradient_steps += 1
                 if plan is not None:
                     scores = text_update.score_plan(self.tables, e_ori, text_grad, plan)
@@ -372,6 +398,9 @@ class BatchedVQAttack:
         mom = self._new_momentum(images)          # in the sorted order of `images`; only the active prefix is updated
         # TI-FGSM: the taps and (with momentum) ONE smoothed-gradient scratch for the whole call
         ti = attacks._smoother(attacks._validate_ti(c.ti_kernel), cur, np.inf, c.decay_factor)
+        # DI-FGSM: the rows of every global step for every sample, drawn and uploaded once; step t uses the active prefix
+        di = attacks._diversity(attacks._validate_di(c.diversity_prob, c.di_shrink, self._start_di()), cur, max(total),
+                                np.inf, c.decay_factor, ti)
         losses = torch.zeros(max(total), dtype=torch.float32, device=dev)
         ws = ops.Workspace()
         res = BatchResult(adv_images=cur, adv_text_ids=adv_ids)
@@ -408,7 +437,11 @@ class BatchedVQAttack:
                 y = [v.rows(n_act) if isinstance(v, LayerFeatures) else (None if v is None else v[:n_act])
                      for v in self._y_feature(targets)]
                 text_key = key
-            leaf_img = cur[:n_act].detach().requires_grad_(True)
+            if di is None:
+                leaf_img = cur[:n_act].detach().requires_grad_(True)
+            else:
+                di.geom = di.table[t][:n_act]
+                leaf_img = ops.di_transform(cur[:n_act], di.geom, out=di.image[:n_act]).detach().requires_grad_(True)
             probing = [s for s in range(n_act) if kinds[s][t][1]] if masker is not None else []
             emb_t = adv_emb[:n_act]
             if masker is None or probing:            # (a masked step without probing samples re-embeds every row below)
@@ -430,7 +463,7 @@ class BatchedVQAttack:
             else:
                 attacks._loss_and_grad(a.pgd_attack_vl, [leaf_img, leaf_txt], [leaf_img, leaf_txt], list(y), 1,
                                        self.flavor, False, slot, vl=True, ws=ws)
-            self._update_runs(cur, attacks._grad_of(leaf_img), images, now, mom, ti)
+            self._update_runs(cur, attacks._grad_of(leaf_img), images, now, mom, ti, di)
             firing = [s for s in range(n_act) if kinds[s][t][1]]
             if firing:
                 sub = plan.restricted_to(firing)
@@ -491,26 +524,37 @@ class BatchedVQAttack:
                 labels[s, j, :len(row)] = torch.tensor(row)
         return tasks, text_ids, text_masks, attackable, mlm_ids, mlm_mask, (labels[:, 0] if k == 1 else labels).to(dev)
 
-    def _update_runs(self, cur, grad, images, now, mom=None, ti=None):
+    def _update_runs(self, cur, grad, images, now, mom=None, ti=None, di=None):
         """The fused image update of one global step, in place on the active prefix of ``cur``: one launch per run of
         consecutive samples of one kind -- ``vqa_linf_fgm`` for ``N`` (first half of a dual iteration: no projection in
         between, projected_gradient_descent.py:155-188), ``vqa_linf_step`` otherwise.  Finished samples stay untouched.
         ``mom`` (MI-FGSM): ``vqa_linf_momentum_step`` instead, without ``x0`` for ``N`` runs; a run accumulates into its own
         rows of the momentum, so a finished sample's momentum stays as it was.
         ``ti`` (TI-FGSM): ``vqa_linf_ti_step`` instead of the two plain kernels; with momentum the run's gradient is smoothed
-        into its rows of the call's scratch first and the momentum step takes that."""
+        into its rows of the call's scratch first and the momentum step takes that.
+        ``di`` (DI-FGSM): ``grad`` is the gradient at the transformed images; ``vqa_linf_di_step`` applies the adjoint and
+        the update in one launch, with TI or momentum the run's adjoint goes into its rows of the call's scratch first."""
         c, lo, n_act = self.cfg, 0, len(now)
         while lo < n_act:
             hi = lo + 1
             while hi < n_act and (now[hi] == "N") == (now[lo] == "N"):
                 hi += 1
             x0 = None if now[lo] == "N" else images[lo:hi]
+            if di is not None:
+                if mom is None and ti is None:
+                    ops.linf_di_step(cur[lo:hi], grad[lo:hi], x0, di.geom[lo:hi], c.eps_iter, c.eps, c.clip_min, c.clip_max,
+                                     out=cur[lo:hi])
+                    lo = hi
+                    continue
+                grad_run = ops.di_adjoint(grad[lo:hi], di.geom[lo:hi], out=di.grad[lo:hi])
+            else:
+                grad_run = grad[lo:hi]
             if mom is not None:
-                g = grad[lo:hi] if ti is None else ops.ti_smooth(grad[lo:hi], ti.taps, out=ti.ghat[lo:hi])
+                g = grad_run if ti is None else ops.ti_smooth(grad_run, ti.taps, out=ti.ghat[lo:hi])
                 ops.linf_momentum_step(cur[lo:hi], g, x0, mom[lo:hi], c.decay_factor, c.eps_iter, c.eps, c.clip_min,
                                        c.clip_max, out=cur[lo:hi])
             elif ti is not None:
-                ops.linf_ti_step(cur[lo:hi], grad[lo:hi], x0, ti.taps, c.eps_iter, c.eps, c.clip_min, c.clip_max,
+                ops.linf_ti_step(cur[lo:hi], grad_run, x0, ti.taps, c.eps_iter, c.eps, c.clip_min, c.clip_max,
                                  out=cur[lo:hi])
             elif now[lo] == "N":
                 ops.linf_fgm(cur[lo:hi], grad[lo:hi], c.eps_iter, c.clip_min, c.clip_max, out=cur[lo:hi])

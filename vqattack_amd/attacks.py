@@ -108,6 +108,26 @@ def _validate_ti(ti_kernel):
     return taps
 
 
+def _validate_di(diversity_prob, di_shrink=32, di_rng=None):
+    """None (input diversity off; the other two keys are then ignored) or ``(prob, shrink, rng)``: ``diversity_prob`` a
+    real number in [0, 1], ``di_shrink`` an int >= 1 (the reference's 32), ``di_rng`` None (``np.random``, what the
+    reference's ``input_diversity`` draws from) or anything with a callable ``.uniform``.  Raised before any tensor is
+    looked at, like the other arguments."""
+    if diversity_prob is None:
+        return None
+    if isinstance(diversity_prob, (bool, np.bool_)) or not isinstance(diversity_prob, (int, float, np.integer, np.floating)):
+        raise ValueError("diversity_prob must be None or a number in [0, 1], got {!r}".format(diversity_prob))
+    prob = float(diversity_prob)
+    if not 0.0 <= prob <= 1.0:        # False for NaN too
+        raise ValueError("diversity_prob must be in [0, 1], got {!r}".format(diversity_prob))
+    if isinstance(di_shrink, (bool, np.bool_)) or not isinstance(di_shrink, (int, np.integer)) or int(di_shrink) < 1:
+        raise ValueError("di_shrink must be an int >= 1, got {!r}".format(di_shrink))
+    if di_rng is not None and not callable(getattr(di_rng, "uniform", None)):
+        raise ValueError("di_rng must be None or have a .uniform method (np.random, a RandomState, a Generator), got {!r}".format(
+            di_rng))
+    return prob, int(di_shrink), (np.random if di_rng is None else di_rng)
+
+
 def _two_sided(clip_min, clip_max):
     if (clip_min is not None or clip_max is not None) and (clip_min is None or clip_max is None):
         raise ValueError("One of clip_min and clip_max is None but we don't currently support one-sided clipping")
@@ -383,12 +403,65 @@ def _smoother(taps, like, norm, decay):
     return _Smoother(taps, like, scratch=decay is not None or norm != np.inf)
 
 
-def _fgm_update(x, grad, eps, norm, clip_min, clip_max, flag=None, out=None, check_range=True, mom=None, ti=None):
+class _Diversity:
+    """The DI-FGSM state of one operator call: the geometry rows of ALL its gradient evaluations, drawn once on the host
+    and uploaded in one copy (``(n_evals, B, 4)``), one static ``(B, 4)`` row for a captured iteration, the transformed
+    image and -- unless the caller only runs the fused L-inf step (``ops.linf_di_step``) -- the adjoint's result."""
+
+    def __init__(self, spec, like, n_evals, scratch=True):
+        prob, shrink, rng = spec
+        b, _, h, w = like.shape
+        self.table = ops.di_geometry(ops.di_draw(rng, b, n_evals, h, w, shrink, prob), h, w, like.device)
+        self.row = torch.empty((b, 4), dtype=torch.int32, device=like.device)
+        self.image = torch.empty_like(like, memory_format=torch.contiguous_format)
+        self.grad = torch.empty_like(like, memory_format=torch.contiguous_format) if scratch else None
+        self.geom, self.n = None, 0
+
+    def use(self, i, static=False):
+        """Make evaluation ``i``'s rows current: in place in the table, or (``static``) copied into the static row."""
+        if static:
+            self.row.copy_(self.table[i])
+        self.geom = self.row if static else self.table[i]
+
+    def leaf(self, adv, advance=True):
+        """The leaf the model sees: the transformed image (the next evaluation's rows unless ``advance=False``)."""
+        if advance:
+            self.use(self.n)
+            self.n += 1
+        return ops.di_transform(adv, self.geom, out=self.image).detach().requires_grad_(True)
+
+    def adjoint(self, gd):
+        return ops.di_adjoint(gd, self.geom, out=self.grad)
+
+
+def _diversity(spec, like, n_evals, norm, decay, taps):
+    """None without DI; the adjoint scratch is needed by every update but the plain L-inf one."""
+    if spec is None:
+        return None
+    if like.dim() != 4:
+        raise ValueError("diversity_prob needs a (B, C, H, W) image: the transform runs over its (H, W) planes, got shape "
+                         "{}".format(tuple(like.shape)))
+    return _Diversity(spec, like, n_evals, scratch=decay is not None or taps is not None or norm != np.inf)
+
+
+def _leaf(adv, di):
+    return adv.detach().requires_grad_(True) if di is None else di.leaf(adv)
+
+
+def _fgm_update(x, grad, eps, norm, clip_min, clip_max, flag=None, out=None, check_range=True, mom=None, ti=None,
+                di=None):
     """``flag``: range violations of ``x`` (``check_range``) and, for the L2 / L1 updates, the degenerate-gradient bit
     that stands for the self-check asserts of the reference's ``optimize_linear`` (utils.py:101-104, :110-116).
     ``mom``: accumulate ``grad`` into the momentum first and step along the momentum instead.
     ``ti``: smooth ``grad`` first (TI-FGSM; with momentum the smoothed gradient is what gets normalised and accumulated,
-    TI-MI-FGSM); the plain L-inf update does both in one launch."""
+    TI-MI-FGSM); the plain L-inf update does both in one launch.
+    ``di``: ``grad`` is the gradient at the TRANSFORMED image (DI-FGSM): the transform's adjoint takes it back to ``x``
+    first, in the same launch for the plain L-inf update, in front of smoothing / momentum / L2 otherwise."""
+    if di is not None:
+        if ti is None and mom is None and norm == np.inf:
+            return ops.linf_di_step(x, grad, None, di.geom, eps, 0.0, clip_min, clip_max,
+                                    flag=flag if check_range else None, out=out)
+        grad = di.adjoint(grad)
     if ti is not None:
         if mom is None and norm == np.inf:
             return ops.linf_ti_step(x, grad, None, ti.taps, eps, 0.0, clip_min, clip_max,
@@ -406,7 +479,12 @@ def _fgm_update(x, grad, eps, norm, clip_min, clip_max, flag=None, out=None, che
     return ops.l1_fgm(x, grad, eps, clip_min, clip_max, flag=flag, out=out, check_range=check_range)
 
 
-def _fgm_then_project(x, grad, x0, eps_iter, eps, norm, clip_min, clip_max, out, flag=None, mom=None, ti=None):
+def _fgm_then_project(x, grad, x0, eps_iter, eps, norm, clip_min, clip_max, out, flag=None, mom=None, ti=None,
+                      di=None):
+    if di is not None:
+        if ti is None and mom is None and norm == np.inf:
+            return ops.linf_di_step(x, grad, x0, di.geom, eps_iter, eps, clip_min, clip_max, out=out)
+        grad = di.adjoint(grad)
     if ti is not None:
         if mom is None and norm == np.inf:
             return ops.linf_ti_step(x, grad, x0, ti.taps, eps_iter, eps, clip_min, clip_max, out=out)
@@ -453,52 +531,60 @@ def _grad_of(leaf):
 # ----------------------------------------------------------------------------------------- FGM
 def fast_gradient_method(model_fn, x, eps, norm, ori_x, clip_min=None, clip_max=None, y=None, targeted=False,
                          sanity_checks=False, ls=None, bkp=None, bkp_y=None, *, flavor=ALBEF, per_sample=False,
-                         ti_kernel=None):
+                         ti_kernel=None, diversity_prob=None, di_shrink=32, di_rng=None):
     """One FGM step; returns ``(adv_x, loss)`` (``loss`` is a 0-d device tensor), bare ``x`` when ``eps == 0``.
     ``ti_kernel`` (extension, keyword-only): TI-FGSM smoothing of the gradient, as in ``projected_gradient_descent``.
+    ``diversity_prob`` / ``di_shrink`` / ``di_rng`` (extensions, keyword-only): DI-FGSM, as there (one evaluation).
     Reference: A fast_gradient_method.py:30-165, V :36-152 (the VLMO copy has no ``bkp``/``bkp_y``)."""
     _check_flavor(flavor)
     _validate_fgm(norm, eps, clip_min, clip_max)
     taps = _validate_ti(ti_kernel)
+    spec = _validate_di(diversity_prob, di_shrink, di_rng)
     if eps == 0:
         return x
     xin = _as_image(x)
     check_range = sanity_checks and (clip_min is not None or clip_max is not None)
     flag = ops.new_flag(xin.device) if (check_range or norm != np.inf) else None
-    leaf = xin.detach().requires_grad_(True)           # shares storage with x: nothing is written in place
+    di = _diversity(spec, xin, 1, norm, None, taps)
+    leaf = _leaf(xin, di)                              # without DI it shares storage with x: nothing is written in place
     loss_buf = torch.zeros(1, dtype=torch.float32, device=xin.device)
     _loss_and_grad(model_fn, [leaf], leaf, y, ls, flavor, targeted, _LossSlot(loss_buf, 0), bkp=bkp, bkp_y=bkp_y,
                    flag=flag, per_sample=per_sample)
     _two_sided(clip_min, clip_max)
     adv = _fgm_update(xin, _grad_of(leaf), eps, norm, clip_min, clip_max, flag=flag, check_range=check_range,
-                      ti=_smoother(taps, xin, norm, None))
+                      ti=_smoother(taps, xin, norm, None), di=di)
     assert _check_flag(flag, norm, sanity_checks), "input x is outside [clip_min, clip_max]"
     return adv, loss_buf[0]
 
 
 def fast_gradient_method_vl(model_fn, x, eps, norm, ori_x, clip_min=None, clip_max=None, y=None, targeted=False,
-                            sanity_checks=False, ls=None, text_emb_pick=None, *, flavor=ALBEF, ti_kernel=None):
+                            sanity_checks=False, ls=None, text_emb_pick=None, *, flavor=ALBEF, ti_kernel=None,
+                            diversity_prob=None, di_shrink=32, di_rng=None):
     """FGM on ``x = [image, text_embeds]``; returns ``(adv_image, text_grad[:, text_emb_pick])``.
     ``ti_kernel`` (extension, keyword-only): TI-FGSM smoothing of the IMAGE gradient, as in ``projected_gradient_descent``.
+    ``diversity_prob`` / ``di_shrink`` / ``di_rng`` (extensions, keyword-only): DI-FGSM on the IMAGE, as there; ``x[0]`` of
+    the caller's list is then the transformed leaf the model saw.
     Like the reference it replaces ``x[0]``/``x[1]`` of the caller's list by the leaf tensors.
     Reference: A fast_gradient_method_vl.py:30-130, V :34-141."""
     _check_flavor(flavor)
     _validate_fgm(norm, eps, clip_min, clip_max)
     taps = _validate_ti(ti_kernel)
+    spec = _validate_di(diversity_prob, di_shrink, di_rng)
     if eps == 0:
         return x
     img = _as_image(x[0], "x[0]")
     emb = _as_image(x[1], "x[1]")
     check_range = sanity_checks and (clip_min is not None or clip_max is not None)
     flag = ops.new_flag(img.device) if (check_range or norm != np.inf) else None
-    x[0] = img.detach().requires_grad_(True)
+    di = _diversity(spec, img, 1, norm, None, taps)
+    x[0] = _leaf(img, di)
     x[1] = emb.detach().requires_grad_(True)
     loss_buf = torch.zeros(1, dtype=torch.float32, device=img.device)
     _loss_and_grad(model_fn, [x[0], x[1]], [x[0], x[1]], y, ls, flavor, targeted, _LossSlot(loss_buf, 0), vl=True)
     text_grad = ops.gather_rows(_grad_of(x[1]), text_emb_pick)
     _two_sided(clip_min, clip_max)
     adv = _fgm_update(img, _grad_of(x[0]), eps, norm, clip_min, clip_max, flag=flag, check_range=check_range,
-                      ti=_smoother(taps, img, norm, None))
+                      ti=_smoother(taps, img, norm, None), di=di)
     assert _check_flag(flag, norm, sanity_checks), "input x is outside [clip_min, clip_max]"
     return adv, text_grad
 
@@ -532,7 +618,7 @@ def _finish(flag, eps, eps_iter, norm, clip_min, clip_max, sanity_checks):
 
 
 def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, clip_min, clip_max, nb_iter, loss_buf,
-                       mom=None, ti=None):
+                       mom=None, ti=None, di=None):
     """``nb_iter`` feature-loss L-inf iterations with iterations 1.. replayed from ONE captured hipGraph.
 
     For the launch-bound regime (the reference's own batch 1: ~10^3 kernels of a few microseconds per iteration):
@@ -546,19 +632,23 @@ def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, cl
     the momentum, the per-sample sums and the reduction's workspace were allocated before capture.
     ``ti``: the fused TI step (or smoothing + reduction + momentum step) is what the iteration captures; the taps travel in
     the kernel arguments and the smoothed-gradient scratch was allocated before capture.
+    ``di``: the transform and the fused DI step (or the adjoint in front of the rest) are captured against the static
+    geometry row; a device-to-device copy of the iteration's rows into it precedes each replay (eager, like the loss word).
     """
     word = torch.zeros(1, dtype=torch.float32, device=cur.device)
 
     def iteration():
-        leaf = cur.detach().requires_grad_(True)
+        leaf = cur.detach().requires_grad_(True) if di is None else di.leaf(cur, advance=False)
         _loss_and_grad(model_fn, [leaf], leaf, y, 1, flavor, targeted, _LossSlot(word, 0))
         _fgm_then_project(cur, _grad_of(leaf), x0, eps_iter, eps, np.inf, clip_min, clip_max, cur,   # in place: static
-                          mom=mom, ti=ti)                                                             # address
+                          mom=mom, ti=ti, di=di)                                                      # address
 
     main = torch.cuda.current_stream(cur.device)
     side = torch.cuda.Stream(device=cur.device)
     side.wait_stream(main)
     with torch.cuda.stream(side):
+        if di is not None:
+            di.use(0, static=True)
         iteration()
         loss_buf[0:1].copy_(word)
     main.wait_stream(side)
@@ -567,6 +657,8 @@ def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, cl
         with torch.cuda.graph(graph):
             iteration()
         for i in range(1, nb_iter):
+            if di is not None:
+                di.use(i, static=True)
             graph.replay()
             loss_buf[i:i + 1].copy_(word)
     return cur
@@ -575,7 +667,8 @@ def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, cl
 def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_min=None, clip_max=None, y=None,
                                ori_x=None, time=None, targeted=False, rand_init=True, rand_minmax=None,
                                sanity_checks=True, ls=None, *, flavor=ALBEF, init_eta=None, graph=None,
-                               per_sample=False, decay_factor=None, momentum=None, ti_kernel=None):
+                               per_sample=False, decay_factor=None, momentum=None, ti_kernel=None,
+                               diversity_prob=None, di_shrink=32, di_rng=None):
     """PGD over a frozen white box; returns ``(adv_x, loss_list)``, bare ``x`` when eps or eps_iter is 0.
 
     ``ls == 1``: feature loss, ``model_fn`` a callable.  Otherwise the dual-loss loop: ``model_fn = [feature_fn,
@@ -603,12 +696,24 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
     launch (``ops.linf_ti_step``); with ``decay_factor`` the smoothed gradient is what is normalised and accumulated
     (TI-MI-FGSM); L2 smooths in front of the existing update; the dual loop smooths both gradients.  ``x`` must be
     ``(B, C, H, W)``.  With ``ti_kernel=None`` (default) nothing changes.
+    ``diversity_prob`` (extension, keyword-only): not None turns every gradient evaluation into DI-FGSM's (Xie et al.
+    2019; the reference defines ``input_diversity`` for torch, cleverhans/fgsm_copy.py:9-31, and leaves its call
+    commented out at :133): the model sees ``T(adv)``, each sample shrunk bilinearly to a random ``(new_h, new_w)`` with
+    ``H - di_shrink <= new_h < H`` and zero padded back at a random offset, with probability ``diversity_prob`` (else
+    the sample is left as it is); the update then runs on ``T``'s adjoint of the gradient at ``T(adv)`` -- what autograd
+    through ``interpolate`` + ``pad`` gives, here one launch for the whole batch.  All rows of the call are drawn once,
+    before the loop, from ``di_rng`` (anything with ``.uniform``; None: ``np.random``, as in the reference), four draws
+    per sample and evaluation (``ops.di_draw``).  The plain L-inf update applies the adjoint in the same launch
+    (``ops.linf_di_step``); with ``ti_kernel`` / ``decay_factor`` / L2 the adjoint (``ops.di_adjoint``) feeds those paths
+    unchanged (DI + TI, DI + MI, all three).  ``x`` must be ``(B, C, H, W)``.  With ``diversity_prob=None`` (default)
+    nothing changes and no random number is drawn.
     Reference: A projected_gradient_descent.py:10-199, V :10-196.
     """
     _check_flavor(flavor)
     unchanged = _validate_pgd(norm, eps, eps_iter, clip_min, clip_max)
     decay = _validate_decay(decay_factor)
     taps = _validate_ti(ti_kernel)
+    spec = _validate_di(diversity_prob, di_shrink, di_rng)
     if unchanged:
         return x
     xin = _as_image(x)
@@ -627,6 +732,7 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
     n_loss = 0
     mom = None if decay is None else _Momentum(decay, xin, momentum)
     ti = _smoother(taps, xin, norm, decay)
+    di = _diversity(spec, xin, nb_iter * (2 if dual else 1), norm, decay, taps)
     ws = ops.Workspace()       # loss-gradient / CE scratch buffers live for the whole call, not per iteration
     bad_flag = flag if flag is not None else (
         ops.new_flag(xin.device) if ((dual and sanity_checks) or norm != np.inf) else None)
@@ -637,35 +743,35 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
             raise ValueError("graph=True supports the feature-loss (ls == 1) L-inf loop only")
         _two_sided(clip_min, clip_max)
         adv = _graphed_linf_loop(model_fn, adv, x0, y, flavor, targeted, eps_iter, eps, clip_min, clip_max, nb_iter,
-                                 loss_buf, mom=mom, ti=ti)
+                                 loss_buf, mom=mom, ti=ti, di=di)
         n_loss, nb_iter = nb_iter, 0
     for _ in range(nb_iter):
         if not dual:
-            leaf = adv.detach().requires_grad_(True)
+            leaf = _leaf(adv, di)
             _loss_and_grad(model_fn, [leaf], leaf, y, ls, flavor, targeted, _LossSlot(loss_buf, n_loss), ws=ws,
                            flag=bad_flag)
             n_loss += 1
             _two_sided(clip_min, clip_max)
             adv = _fgm_then_project(adv, _grad_of(leaf), x0, eps_iter, eps, norm, clip_min, clip_max, buf[1 - cur],
-                                    flag=bad_flag, mom=mom, ti=ti)
+                                    flag=bad_flag, mom=mom, ti=ti, di=di)
         else:
             if flavor == ALBEF:      # A :163,177-181 slices y; V :162,175 passes it whole
                 y_feat, y_mlm, extra = [y[1], y[2]], [y[0]], dict(bkp=model_fn[0], bkp_y=[y[1], y[2]])
             else:
                 y_feat, y_mlm, extra = y, y, {}
-            leaf = adv.detach().requires_grad_(True)
+            leaf = _leaf(adv, di)
             _loss_and_grad(model_fn[0], [leaf], leaf, y_feat, 1, flavor, targeted, _LossSlot(loss_buf, n_loss), ws=ws,
                            flag=bad_flag)
             n_loss += 1
             _two_sided(clip_min, clip_max)
             mid = _fgm_update(adv, _grad_of(leaf), eps_iter, norm, clip_min, clip_max, out=buf[1 - cur], flag=bad_flag,
-                              check_range=False, mom=mom, ti=ti)
-            leaf = mid.detach().requires_grad_(True)
+                              check_range=False, mom=mom, ti=ti, di=di)
+            leaf = _leaf(mid, di)
             _loss_and_grad(model_fn[1], [leaf], leaf, y_mlm, 0, flavor, targeted, _LossSlot(loss_buf, n_loss), ws=ws,
                            flag=bad_flag, per_sample=per_sample, **extra)
             n_loss += 1
             adv = _fgm_then_project(mid, _grad_of(leaf), x0, eps_iter, eps, norm, clip_min, clip_max, buf[cur],
-                                    flag=bad_flag, mom=mom, ti=ti)
+                                    flag=bad_flag, mom=mom, ti=ti, di=di)
             cur = 1 - cur            # result sits in buf[cur] again after the flip below
         cur = 1 - cur
         del leaf
@@ -677,17 +783,20 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
 def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, clip_min=None, clip_max=None, y=None,
                                   ori_x=None, time=None, targeted=False, rand_init=True, rand_minmax=None,
                                   sanity_checks=True, ls=None, attack_mask=None, *, flavor=ALBEF, init_eta=None,
-                                  decay_factor=None, momentum=None, ti_kernel=None):
+                                  decay_factor=None, momentum=None, ti_kernel=None, diversity_prob=None, di_shrink=32,
+                                  di_rng=None):
     """PGD on ``x = [image, text_embeds]`` (only the image moves); returns ``(adv_image, text_embed_gradient)`` of
     the last iteration.  Only ``ls == 1`` is supported (``ValueError`` otherwise), as in the reference.
     ``decay_factor`` / ``momentum`` (extensions, keyword-only): MI-FGSM on the image, as in
     ``projected_gradient_descent``; ``momentum`` has the image's shape.  ``ti_kernel`` (extension, keyword-only):
-    TI-FGSM smoothing of the image gradient, as there.
+    TI-FGSM smoothing of the image gradient, as there.  ``diversity_prob`` / ``di_shrink`` / ``di_rng`` (extensions,
+    keyword-only): DI-FGSM, as there; only the image is transformed.
     Reference: A projected_gradient_descent_vl.py:10-168, V :10-164."""
     _check_flavor(flavor)
     unchanged = _validate_pgd(norm, eps, eps_iter, clip_min, clip_max)
     decay = _validate_decay(decay_factor)
     taps = _validate_ti(ti_kernel)
+    spec = _validate_di(diversity_prob, di_shrink, di_rng)
     if unchanged:
         return x
     img = _as_image(x[0], "x[0]")
@@ -707,17 +816,18 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
     ws = ops.Workspace()
     mom = None if decay is None else _Momentum(decay, img, momentum)
     ti = _smoother(taps, img, norm, decay)
+    di = _diversity(spec, img, nb_iter, norm, decay, taps)
     if attack_mask is not None and not isinstance(attack_mask, ops.RowIndex):   # validated + uploaded once per call
         attack_mask = ops.RowIndex(attack_mask, emb.shape[1], emb.device)
     for it in range(nb_iter):
-        leaf_img = adv.detach().requires_grad_(True)
+        leaf_img = _leaf(adv, di)
         leaf_txt = emb.detach().requires_grad_(True)
         _loss_and_grad(model_fn, [leaf_img, leaf_txt], [leaf_img, leaf_txt], y, ls, flavor, targeted,
                        _LossSlot(loss_buf, it), vl=True, ws=ws, flag=flag)
         text_grad = ops.gather_rows(_grad_of(leaf_txt), attack_mask)
         _two_sided(clip_min, clip_max)
         adv = _fgm_then_project(adv, _grad_of(leaf_img), x0, eps_iter, eps, norm, clip_min, clip_max, buf[1 - cur],
-                                flag=flag, mom=mom, ti=ti)
+                                flag=flag, mom=mom, ti=ti, di=di)
         cur = 1 - cur
         del leaf_img, leaf_txt
     _finish(flag, eps, eps_iter, norm, clip_min, clip_max, sanity_checks)
@@ -727,7 +837,8 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
 # ----------------------------------------------------------------------------------------- MI-FGSM
 def momentum_iterative_method(model_fn, x, eps, eps_iter, nb_iter, norm, clip_min=None, clip_max=None, y=None,
                               ori_x=None, targeted=False, decay_factor=1.0, sanity_checks=True, ls=1, *, flavor=ALBEF,
-                              graph=None, momentum=None, ti_kernel=None):
+                              graph=None, momentum=None, ti_kernel=None, diversity_prob=None, di_shrink=32,
+                              di_rng=None):
     """The momentum iterative method (Dong et al. 2017) on this project's losses; returns ``(adv_x, loss_list)`` like
     ``projected_gradient_descent``, so a driver can swap one for the other.
 
@@ -736,10 +847,12 @@ def momentum_iterative_method(model_fn, x, eps, eps_iter, nb_iter, norm, clip_mi
     ``norm == 1`` is refused first (:54-60) and every iteration normalises the gradient by its per-sample mean absolute
     value, adds it to ``decay_factor`` times the momentum (:88-95) and steps along the momentum (:97-103).  ``ori_x``
     (centre of the eps-ball) defaults to ``x``; ``ls``, ``flavor``, ``graph``, ``momentum`` and ``ti_kernel``
-    (TI-MI-FGSM, the combination the TI paper recommends) as in ``projected_gradient_descent``, which runs the loop."""
+    (TI-MI-FGSM, the combination the TI paper recommends) as in ``projected_gradient_descent``, which runs the loop;
+    ``diversity_prob`` / ``di_shrink`` / ``di_rng`` as there too (M-DI2-FGSM; with ``ti_kernel`` TI-DIM)."""
     if norm != 1 and decay_factor is None:
         raise ValueError("decay_factor must be a number (use projected_gradient_descent for the attack without momentum)")
     return projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_min=clip_min, clip_max=clip_max,
                                       y=y, ori_x=x if ori_x is None else ori_x, time=None, targeted=targeted,
                                       sanity_checks=sanity_checks, ls=ls, flavor=flavor, graph=graph,
-                                      decay_factor=decay_factor, momentum=momentum, ti_kernel=ti_kernel)
+                                      decay_factor=decay_factor, momentum=momentum, ti_kernel=ti_kernel,
+                                      diversity_prob=diversity_prob, di_shrink=di_shrink, di_rng=di_rng)

@@ -419,6 +419,116 @@ def linf_ti_step(x, g, x0, taps, eps_iter, eps, clip_min, clip_max, flag=None, o
     return out
 
 
+# ----------------------------------------------------------------------------------------- input diversity (DI-FGSM)
+def di_draw(rng, batch, steps, height, width, shrink=32, prob=1.0):
+    """The geometry rows ``[new_h, new_w, top, left]`` of ``steps`` x ``batch`` DI transforms as an int32 numpy array
+    ``(steps, batch, 4)``.  ``rng`` is anything with ``.uniform`` (``np.random``, a ``RandomState``, a ``Generator``).
+    Per step and sample, in this order, the three draws of the reference's ``input_diversity``
+    (cleverhans/fgsm_copy.py:9-31, ``shrink`` in place of its 32) and one ``uniform()`` draw ``u``; with ``u >= prob``
+    the row becomes the identity row ``[height, width, 0, 0]``.  All four draws are always taken, so the stream does not
+    depend on ``prob``."""
+    batch, steps, height, width, shrink = int(batch), int(steps), int(height), int(width), int(shrink)
+    if batch < 0 or steps < 0 or height < 1 or width < 1 or shrink < 0:
+        raise ValueError("di_draw: batch / steps must be >= 0, height / width >= 1, shrink >= 0")
+    if height - shrink < 1:
+        raise ValueError("di_draw: height - shrink must be at least 1, got height {} and shrink {}".format(height, shrink))
+    table = np.empty((steps, batch, 4), dtype=np.int32)
+    for s in range(steps):
+        for b in range(batch):
+            newh = int(rng.uniform(height - shrink, height))
+            neww = int((newh / height) * width)
+            top = int(rng.uniform(0, height - newh))
+            left = int(rng.uniform(0, width - neww))
+            u = rng.uniform()
+            if neww < 1:
+                raise ValueError("di_draw: new_w = {} for new_h = {} of ({}, {}): the image is too narrow for this "
+                                 "shrink".format(neww, newh, height, width))
+            table[s, b] = (newh, neww, top, left) if u < prob else (height, width, 0, 0)
+    return table
+
+
+def di_check_table(table, height, width):
+    """``table`` as a C-contiguous int32 numpy array ``(..., 4)`` with every row inside the ranges of the contract."""
+    t = np.asarray(table)
+    if t.dtype.kind not in "iu" or t.ndim < 1 or t.shape[-1] != 4:
+        raise ValueError("a DI geometry table is an integer array (..., 4) of [new_h, new_w, top, left] rows, got "
+                         "dtype {} shape {}".format(t.dtype, t.shape))
+    t = t.astype(np.int64)
+    nh, nw, top, left = t[..., 0], t[..., 1], t[..., 2], t[..., 3]
+    bad = (nh < 1) | (nh > height) | (nw < 1) | (nw > width) | (top < 0) | (top > height - nh) | (left < 0) | \
+        (left > width - nw)
+    if bad.any():
+        row = t.reshape(-1, 4)[int(np.flatnonzero(bad.reshape(-1))[0])]
+        raise ValueError("DI geometry row {} is outside its ranges for a ({}, {}) plane".format(row.tolist(), height, width))
+    return np.ascontiguousarray(t.astype(np.int32))
+
+
+def di_geometry(table, height, width, device):
+    """Validate a geometry table against ``(height, width)`` and upload it in one copy: an int32 device tensor of the
+    table's shape.  The kernels read one ``(B, 4)`` slice of it per launch."""
+    return torch.from_numpy(di_check_table(table, height, width)).to(device)
+
+
+def _di_args(x, geom, name):
+    dev_f32(x, name, contiguous=False)
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError("{} must be a contiguous (B, C, H, W) tensor: the transform runs over row-major planes".format(name))
+    if not isinstance(geom, torch.Tensor) or not geom.is_cuda or geom.dtype != torch.int32 or not geom.is_contiguous() \
+            or geom.dim() != 2 or geom.shape[0] != x.shape[0] or geom.shape[1] != 4:
+        raise ValueError("geom must be a contiguous int32 device tensor ({}, 4) (ops.di_geometry), got {}".format(
+            x.shape[0], (geom.dtype, tuple(geom.shape), str(geom.device)) if isinstance(geom, torch.Tensor) else type(geom)))
+    return x.shape
+
+
+def di_transform(x, geom, out=None):
+    """``out = T(x)``: per sample, every (H, W) plane shrunk bilinearly to ``(new_h, new_w)`` and zero padded back at
+    ``(top, left)``; the bit-level contract is in ``include/vqattack_hip.h``.  ``out`` must not be ``x``."""
+    b, c, h, w = _di_args(x, geom, "x")
+    same_device(x, geom, out)
+    out = _out_like(x, out)
+    if x.numel() == 0:
+        return out
+    with _on(x):
+        check(lib().vqa_di_transform(ptr(x), ptr(geom), ptr(out), b, c, h, w, stream_for(x)), "vqa_di_transform")
+    return out
+
+
+def di_adjoint(gd, geom, out=None):
+    """``out = T^T(gD)``: the gradient with respect to ``x`` of a loss whose gradient at ``di_transform(x, geom)`` is
+    ``gd``; a deterministic gather.  ``out`` must not be ``gd``."""
+    b, c, h, w = _di_args(gd, geom, "grad")
+    same_device(gd, geom, out)
+    out = _out_like(gd, out)
+    if gd.numel() == 0:
+        return out
+    with _on(gd):
+        check(lib().vqa_di_adjoint(ptr(gd), ptr(geom), ptr(out), b, c, h, w, stream_for(gd)), "vqa_di_adjoint")
+    return out
+
+
+def linf_di_step(x, gd, x0, geom, eps_iter, eps, clip_min, clip_max, flag=None, out=None):
+    """``di_adjoint`` and ``linf_step`` on its result in one pass, at most 16 B/element; ``x0=None``: and ``linf_fgm`` (no
+    projection).  The image gradient never reaches memory; ``out`` may be ``x``."""
+    dev_f32(x, "x")
+    if x0 is not None:
+        dev_f32(x0, "ori_x")
+    b, c, h, w = _di_args(gd, geom, "grad")
+    if gd.shape != x.shape or (x0 is not None and x0.shape != x.shape):
+        raise ValueError("shape mismatch: x {}, grad {}, ori_x {}".format(
+            tuple(x.shape), tuple(gd.shape), None if x0 is None else tuple(x0.shape)))
+    same_device(x, gd, x0, geom, out, flag)
+    out = _out_like(x, out)
+    mode, lo, hi = _clip_args(clip_min, clip_max)
+    if flag is not None and mode:
+        mode |= VQA_CHECK_RANGE
+    if x.numel() == 0:
+        return out
+    with _on(x):
+        check(lib().vqa_linf_di_step(ptr(x), ptr(gd), ptr(x0), ptr(geom), ptr(out), b, c, h, w, eps_iter, eps, lo, hi,
+                                     mode, ptr(flag), stream_for(x)), "vqa_linf_di_step")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- loss
 _COS_EPS = 1e-6  # nn.CosineSimilarity(eps=1e-6) in the reference
 _partials = {}
