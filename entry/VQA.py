@@ -60,6 +60,10 @@ def parse(argv=None):
                          "the reference's input_diversity); absent: off")
     ap.add_argument("--di_shrink", default=32, type=int, help="DI-FGSM: new_h is drawn from [H - di_shrink, H)")
     ap.add_argument("--di_seed", default=None, type=int, help="DI-FGSM: seed of the geometry draws; absent: unseeded")
+    ap.add_argument("--si_copies", default=None, type=int,
+                    help="SI-FGSM number of scale copies 1, 1/2, ... of the image attack (Lin et al. 2020; 1..8); absent: off")
+    ap.add_argument("--nesterov", action="store_true",
+                    help="NI-FGSM: take gradients at the Nesterov look-ahead point (needs --decay_factor)")
     ap.add_argument("--mlm_checkpoint", default="", help="BertForMaskedLM state dict -> candidate proposer (adv_attack.py:110)")
     ap.add_argument("--answer_list", default=None,
                     help="ALBEF answer_list json (configs: answer_list): the victim ranks it and acc_vqa compares answer "
@@ -133,7 +137,8 @@ def main():
                     force_collective=dist.is_initialized(), source=source, mlm_logits_fn=proposer, banned_ids=banned,
                     config=AttackConfig(sim_threshold=args.sim_threshold, decay_factor=args.decay_factor,
                                         ti_kernel=args.ti_kernel, diversity_prob=args.diversity_prob,
-                                        di_shrink=args.di_shrink, di_seed=args.di_seed),
+                                        di_shrink=args.di_shrink, di_seed=args.di_seed, si_copies=args.si_copies,
+                                        nesterov=args.nesterov),
                     scoring=scoring)
     finish(rank, world, res, os.path.join(args.output_dir, "adv_txt.json") if args.output_dir else None,
            os.path.join(args.output_dir, "adv_txt_dict_albef.txt") if args.output_dir and scoring else None)

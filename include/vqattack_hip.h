@@ -264,6 +264,42 @@ int vqa_linf_di_step(const float* x, const float* gD, const float* x0, const int
                      int channels, int height, int width, float eps_iter, float eps, float cmin, float cmax,
                      unsigned mode, int* flag, vqa_stream_t stream);
 
+/* ---------------------------------------------------------------- scale copies and Nesterov look-ahead (SI-NI-FGSM, Lin et al. 2020)
+ * The reference tree has neither in any framework; this definition is the contract.  Per gradient evaluation the model
+ * sees `copies` scaled images s_i * (x [+ lookahead * m]) (the paper: s_i = 2^-i, lookahead = eps_iter * decay, m the
+ * momentum; no clamp and no projection, the authors' code looks ahead unclipped) and the image gradient is
+ *   ghat = sum_i w_i * g_i,   w_i = s_i / copies  (the paper's average and the chain rule through the scaling),
+ * all in fp32 with one rounding per operation (no contraction).  At most VQA_SI_MAX_COPIES copies.  Scales, weights
+ * and the list of gradient pointers are HOST arrays that travel by value in the kernel arguments (no device allocation,
+ * no copy, no sync: capture-safe; the gradient addresses are then fixed in a captured launch).  16-byte accesses are
+ * used when n % 4 == 0 (and copy_stride % 4 == 0) and every pointer, each gradient included, is 16-byte aligned.
+ * Return codes, all before the first HIP call: a NULL required pointer, a NULL entry of grads_host, or VQA_CHECK_RANGE
+ * without flag, VQA_ERR_NULL; copies outside 1..VQA_SI_MAX_COPIES, copy_stride < n, or a forbidden overlap or alias,
+ * VQA_ERR_SHAPE; a pointer not 4-byte aligned VQA_ERR_ALIGN; n == 0 VQA_OK, no launch.
+ */
+#define VQA_SI_MAX_COPIES 8
+int vqa_si_max_copies(void);
+
+/* out[i * copy_stride + e] = s_i * x[e] for m == NULL, else s_i * (x[e] + lookahead * m[e]) (multiply, add, multiply),
+ * i < copies, e < n.  s = 1 with m == NULL is a bit copy of x.  One launch reads x (and m) once and writes every copy:
+ * 4 (+ 4) + 4 * copies B/element.  copy_stride >= n; out must not overlap x or m. */
+int vqa_si_copies(const float* x, const float* m, float* out, size_t n, size_t copy_stride, const float* scales_host,
+                  int copies, float lookahead, vqa_stream_t stream);
+
+/* out[e] = acc, acc = w_0 * g_0[e], then acc = acc + w_i * g_i[e] for i = 1 .. copies - 1 ascending.  The accumulator
+ * starts from the first product, not from +0: copies = 1, w = {1} is the exact identity, signed zeros included.
+ * grads_host is a HOST array of `copies` DEVICE pointers.  4 * copies + 4 B/element.  out may alias no gradient. */
+int vqa_si_combine(const float* const* grads_host, const float* weights_host, int copies, float* out, size_t n,
+                   vqa_stream_t stream);
+
+/* The combination above and the L-infinity update in ONE pass: out = vqa_linf_step(x, ghat, x0), or, for x0 == NULL,
+ * out = vqa_linf_fgm(x, ghat) -- bit for bit what vqa_si_combine followed by that launch gives; ghat never goes to
+ * memory.  4 * copies + 12 B/element (8 without x0) against (4 * copies + 4) + 16 for the two launches.  `out` may be
+ * exactly `x` (in place) and must not otherwise overlap x, x0 or a gradient.  mode / flag as in vqa_linf_step. */
+int vqa_linf_si_step(const float* x, const float* const* grads_host, const float* weights_host, int copies,
+                     const float* x0, float* out, size_t n, float eps_iter, float eps, float cmin, float cmax,
+                     unsigned mode, int* flag, vqa_stream_t stream);
+
 /* ---------------------------------------------------------------- cross-modal loss reduction
  * Rows of D contiguous floats, addressed as row(o, i) = base + o*stride0 + i*stride1 (strides in ELEMENTS) for
  * o < rows0, i < rows1 -- this is how the reference's `out[k][:, :feat_len, :]` truncation views are consumed

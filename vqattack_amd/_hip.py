@@ -56,6 +56,10 @@ SIGNATURES = {
     "vqa_di_transform": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "vqa_di_adjoint": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "vqa_linf_di_step": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _f, _u, _p, _p]),
+    "vqa_si_max_copies": (_i, []),
+    "vqa_si_copies": (_i, [_p, _p, _p, _sz, _sz, _p, _i, _f, _p]),
+    "vqa_si_combine": (_i, [_p, _p, _i, _p, _sz, _p]),
+    "vqa_linf_si_step": (_i, [_p, _p, _p, _i, _p, _p, _sz, _f, _f, _f, _f, _u, _p, _p]),
     "vqa_neg_cos_partials": (_i, []),
     "vqa_neg_cos_rows": (_i, [_p, _p, _p, _p, _p, _l, _l, _l, _i, _l, _l, _l, _l, _l, _l, _f, _f, _p, _i, _p]),
     "vqa_neg_cos_max_layers": (_i, []),

@@ -17,6 +17,7 @@ Attack hyper-parameters default to the reference's hard-coded literals (adv_atta
 L-inf, clip [-1, 1]).
 """
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 from typing import Optional
 
 import numpy as np
@@ -48,6 +49,8 @@ class AttackConfig:
     diversity_prob: Optional[float] = None # not None: DI-FGSM, every gradient is taken at a randomly shrunk and padded image
     di_shrink: int = 32                    # DI: new_h is drawn from [H - di_shrink, H) (the reference's 32)
     di_seed: Optional[int] = None          # DI: seed of the np.random.RandomState each attack call draws its rows from
+    si_copies: object = None               # not None: SI-FGSM, every gradient is the weighted sum over scaled copies (1..8 or scales)
+    nesterov: bool = False                 # NI-FGSM: gradients are taken at adv + eps_iter * decay_factor * momentum
 
     def __post_init__(self):
         attacks._validate_decay(self.decay_factor)
@@ -65,6 +68,10 @@ class AttackConfig:
         if self.diversity_prob is not None and self.patch_layout:
             # the transform resamples row-major (H, W) planes: a patch-major image has none
             raise ValueError("diversity_prob and patch_layout=True cannot be combined")
+        attacks._validate_si(self.si_copies, self.nesterov, self.decay_factor)
+        if self.si_copies is not None and self.patch_layout:
+            # like the other three keys: the patch-major path is not exercised with any transfer method
+            raise ValueError("si_copies and patch_layout=True cannot be combined")
 
 
 @dataclass
@@ -147,7 +154,7 @@ class BatchedVQAttack:
         common = dict(clip_min=c.clip_min, clip_max=c.clip_max, time=time, ori_x=clean,
                       sanity_checks=c.sanity_checks, init_eta=init_eta, decay_factor=c.decay_factor, momentum=momentum,
                       ti_kernel=c.ti_kernel, diversity_prob=c.diversity_prob, di_shrink=c.di_shrink,
-                      di_rng=self._di_draws)
+                      di_rng=self._di_draws, si_copies=c.si_copies, nesterov=c.nesterov)
         a = self.adapters
         if not dual:
             return self.pgd(a.pgd_attack, adv, c.eps, c.eps_iter, steps, c.norm, y=self._y_feature(targets), ls=1,
@@ -260,7 +267,7 @@ class BatchedVQAttack:
                                                  attack_mask=positions, sanity_checks=c.sanity_checks,
                                                  decay_factor=c.decay_factor, momentum=mom, ti_kernel=c.ti_kernel,
                                                  diversity_prob=c.diversity_prob, di_shrink=c.di_shrink,
-                                                 di_rng=self._di_draws)
+                                                 di_rng=self._di_draws, si_copies=c.si_copies, nesterov=c.nesterov)
                 res.gradient_steps += 1
                 if plan is not None:
                     scores = text_update.score_plan(self.tables, e_ori, text_grad, plan)
@@ -401,6 +408,9 @@ class BatchedVQAttack:
         # DI-FGSM: the rows of every global step for every sample, drawn and uploaded once; step t uses the active prefix
         di = attacks._diversity(attacks._validate_di(c.diversity_prob, c.di_shrink, self._start_di()), cur, max(total),
                                 np.inf, c.decay_factor, ti)
+        # SI-NI-FGSM: the copies of every sample (step t fills the active prefix of each), the combined-gradient scratch
+        si = attacks._scales(attacks._validate_si(c.si_copies, c.nesterov, c.decay_factor), cur, c.eps_iter, np.inf,
+                             None if mom is None else SimpleNamespace(decay=float(c.decay_factor), m=mom), ti, di)
         losses = torch.zeros(max(total), dtype=torch.float32, device=dev)
         ws = ops.Workspace()
         res = BatchResult(adv_images=cur, adv_text_ids=adv_ids)
@@ -437,11 +447,19 @@ class BatchedVQAttack:
                 y = [v.rows(n_act) if isinstance(v, LayerFeatures) else (None if v is None else v[:n_act])
                      for v in self._y_feature(targets)]
                 text_key = key
-            if di is None:
-                leaf_img = cur[:n_act].detach().requires_grad_(True)
-            else:
+            if di is not None:
                 di.geom = di.table[t][:n_act]
-                leaf_img = ops.di_transform(cur[:n_act], di.geom, out=di.image[:n_act]).detach().requires_grad_(True)
+            if si is not None:
+                # one launch for every copy of the active prefix, looking ahead with the active prefix of the momentum
+                seen = ops.si_copies(cur[:n_act], si.scales, m=None if si.mom is None else mom[:n_act],
+                                     lookahead=si.lookahead, out=si.images[:, :n_act])
+                if di is not None:                   # all copies of a step share the step's rows
+                    seen = [ops.di_transform(seen[i], di.geom, out=si.transformed[i, :n_act]) for i in range(len(seen))]
+                leaves = [seen[i].detach().requires_grad_(True) for i in range(len(seen))]
+            elif di is None:
+                leaves = [cur[:n_act].detach().requires_grad_(True)]
+            else:
+                leaves = [ops.di_transform(cur[:n_act], di.geom, out=di.image[:n_act]).detach().requires_grad_(True)]
             probing = [s for s in range(n_act) if kinds[s][t][1]] if masker is not None else []
             emb_t = adv_emb[:n_act]
             if masker is None or probing:            # (a masked step without probing samples re-embeds every row below)
@@ -455,15 +473,20 @@ class BatchedVQAttack:
                     emb_m[idx] = emb_t[idx]
                 emb_t = emb_m
             leaf_txt = emb_t.detach().requires_grad_(True)
-            slot = attacks._LossSlot(losses, t)
-            if use_mixed_closure:
-                attacks._mixed_loss_and_grad(a.pgd_attack_mixed, [leaf_img, leaf_txt], [leaf_img, leaf_txt], list(y),
-                                             self.flavor, slot, ws=ws, flag=flag,
-                                             mlm_labels=labels_live[sel] if at_mlm else None)
-            else:
-                attacks._loss_and_grad(a.pgd_attack_vl, [leaf_img, leaf_txt], [leaf_img, leaf_txt], list(y), 1,
-                                       self.flavor, False, slot, vl=True, ws=ws)
-            self._update_runs(cur, attacks._grad_of(leaf_img), images, now, mom, ti, di)
+            # one white-box pass per copy; copy 0 carries the text leaf and the step's loss slot, the others see the same
+            # text embeddings detached (one masking draw per step, above) and leave their loss in a scratch word
+            for i, leaf_img in enumerate(leaves):
+                wrt = [leaf_img, leaf_txt] if i == 0 else [leaf_img]
+                seen_by_model = [leaf_img, leaf_txt if i == 0 else emb_t.detach()]
+                slot = attacks._LossSlot(losses, t) if i == 0 else si.slot
+                if use_mixed_closure:
+                    attacks._mixed_loss_and_grad(a.pgd_attack_mixed, wrt, seen_by_model, list(y), self.flavor, slot, ws=ws,
+                                                 flag=flag, mlm_labels=labels_live[sel] if at_mlm else None)
+                else:
+                    attacks._loss_and_grad(a.pgd_attack_vl, wrt, seen_by_model, list(y), 1, self.flavor, False, slot,
+                                           vl=True, ws=ws)
+            grads = [attacks._grad_of(leaf) for leaf in leaves]
+            self._update_runs(cur, grads[0] if si is None else grads, images, now, mom, ti, di, si)
             firing = [s for s in range(n_act) if kinds[s][t][1]]
             if firing:
                 sub = plan.restricted_to(firing)
@@ -524,7 +547,7 @@ class BatchedVQAttack:
                 labels[s, j, :len(row)] = torch.tensor(row)
         return tasks, text_ids, text_masks, attackable, mlm_ids, mlm_mask, (labels[:, 0] if k == 1 else labels).to(dev)
 
-    def _update_runs(self, cur, grad, images, now, mom=None, ti=None, di=None):
+    def _update_runs(self, cur, grad, images, now, mom=None, ti=None, di=None, si=None):
         """The fused image update of one global step, in place on the active prefix of ``cur``: one launch per run of
         consecutive samples of one kind -- ``vqa_linf_fgm`` for ``N`` (first half of a dual iteration: no projection in
         between, projected_gradient_descent.py:155-188), ``vqa_linf_step`` otherwise.  Finished samples stay untouched.
@@ -533,22 +556,35 @@ class BatchedVQAttack:
         ``ti`` (TI-FGSM): ``vqa_linf_ti_step`` instead of the two plain kernels; with momentum the run's gradient is smoothed
         into its rows of the call's scratch first and the momentum step takes that.
         ``di`` (DI-FGSM): ``grad`` is the gradient at the transformed images; ``vqa_linf_di_step`` applies the adjoint and
-        the update in one launch, with TI or momentum the run's adjoint goes into its rows of the call's scratch first."""
+        the update in one launch, with TI or momentum the run's adjoint goes into its rows of the call's scratch first.
+        ``si`` (SI-NI-FGSM): ``grad`` is the LIST of the copies' gradients, every one sliced per run; ``vqa_linf_si_step``
+        combines and updates in one launch, with DI, TI or momentum the run's combination goes into its rows of the call's
+        scratch first and the rest of the chain takes that."""
         c, lo, n_act = self.cfg, 0, len(now)
         while lo < n_act:
             hi = lo + 1
             while hi < n_act and (now[hi] == "N") == (now[lo] == "N"):
                 hi += 1
             x0 = None if now[lo] == "N" else images[lo:hi]
-            if di is not None:
-                if mom is None and ti is None:
-                    ops.linf_di_step(cur[lo:hi], grad[lo:hi], x0, di.geom[lo:hi], c.eps_iter, c.eps, c.clip_min, c.clip_max,
+            if si is not None:
+                per_copy = [g[lo:hi] for g in grad]
+                if di is None and mom is None and ti is None:
+                    ops.linf_si_step(cur[lo:hi], per_copy, x0, si.weights, c.eps_iter, c.eps, c.clip_min, c.clip_max,
                                      out=cur[lo:hi])
                     lo = hi
                     continue
-                grad_run = ops.di_adjoint(grad[lo:hi], di.geom[lo:hi], out=di.grad[lo:hi])
+                grad_in = ops.si_combine(per_copy, si.weights, out=si.ghat[lo:hi])
             else:
-                grad_run = grad[lo:hi]
+                grad_in = grad[lo:hi]
+            if di is not None:
+                if mom is None and ti is None:
+                    ops.linf_di_step(cur[lo:hi], grad_in, x0, di.geom[lo:hi], c.eps_iter, c.eps, c.clip_min, c.clip_max,
+                                     out=cur[lo:hi])
+                    lo = hi
+                    continue
+                grad_run = ops.di_adjoint(grad_in, di.geom[lo:hi], out=di.grad[lo:hi])
+            else:
+                grad_run = grad_in
             if mom is not None:
                 g = grad_run if ti is None else ops.ti_smooth(grad_run, ti.taps, out=ti.ghat[lo:hi])
                 ops.linf_momentum_step(cur[lo:hi], g, x0, mom[lo:hi], c.decay_factor, c.eps_iter, c.eps, c.clip_min,
@@ -557,9 +593,9 @@ class BatchedVQAttack:
                 ops.linf_ti_step(cur[lo:hi], grad_run, x0, ti.taps, c.eps_iter, c.eps, c.clip_min, c.clip_max,
                                  out=cur[lo:hi])
             elif now[lo] == "N":
-                ops.linf_fgm(cur[lo:hi], grad[lo:hi], c.eps_iter, c.clip_min, c.clip_max, out=cur[lo:hi])
+                ops.linf_fgm(cur[lo:hi], grad_run, c.eps_iter, c.clip_min, c.clip_max, out=cur[lo:hi])
             else:
-                ops.linf_step(cur[lo:hi], grad[lo:hi], images[lo:hi], c.eps_iter, c.eps, c.clip_min, c.clip_max,
+                ops.linf_step(cur[lo:hi], grad_run, images[lo:hi], c.eps_iter, c.eps, c.clip_min, c.clip_max,
                               out=cur[lo:hi])
             lo = hi
 

@@ -128,6 +128,36 @@ def _validate_di(diversity_prob, di_shrink=32, di_rng=None):
     return prob, int(di_shrink), (np.random if di_rng is None else di_rng)
 
 
+def _validate_si(si_copies, nesterov=False, decay_factor=None):
+    """None (no scale copies, no look-ahead) or ``(scales, nesterov)``: ``si_copies`` an int n in 1..8 selects the SI
+    paper's scales ``1, 1/2, ..., 2^-(n-1)``, a 1-D sequence of 1..8 finite positive floats is used as the scales;
+    ``nesterov`` needs a decay factor (the look-ahead is ``eps_iter * decay_factor * m``) and, alone, means one copy at
+    scale 1.  Raised before any tensor is looked at, like the other arguments."""
+    if not isinstance(nesterov, (bool, np.bool_)):
+        raise ValueError("nesterov must be a bool, got {!r}".format(nesterov))
+    if nesterov and decay_factor is None:
+        raise ValueError("nesterov=True needs decay_factor: the look-ahead is taken along the momentum")
+    if si_copies is None:
+        return (ops.si_scales(1), True) if nesterov else None
+    what = "si_copies must be None, an int in 1..{} or a 1-D sequence of 1..{} finite positive scales, got {!r}".format(
+        ops.SI_MAX_COPIES, ops.SI_MAX_COPIES, si_copies)
+    if isinstance(si_copies, (bool, np.bool_)):
+        raise ValueError(what)
+    if isinstance(si_copies, (int, np.integer)):
+        if int(si_copies) < 1 or int(si_copies) > ops.SI_MAX_COPIES:
+            raise ValueError(what)
+        return ops.si_scales(int(si_copies)), bool(nesterov)
+    try:
+        scales = np.asarray(si_copies, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError(what)
+    if scales.ndim != 1 or scales.size < 1 or scales.size > ops.SI_MAX_COPIES:
+        raise ValueError(what)
+    if not np.all(np.isfinite(scales)) or not np.all(scales > 0):
+        raise ValueError(what)
+    return scales, bool(nesterov)
+
+
 def _two_sided(clip_min, clip_max):
     if (clip_min is not None or clip_max is not None) and (clip_min is None or clip_max is None):
         raise ValueError("One of clip_min and clip_max is None but we don't currently support one-sided clipping")
@@ -423,12 +453,12 @@ class _Diversity:
             self.row.copy_(self.table[i])
         self.geom = self.row if static else self.table[i]
 
-    def leaf(self, adv, advance=True):
+    def leaf(self, adv, advance=True, out=None):
         """The leaf the model sees: the transformed image (the next evaluation's rows unless ``advance=False``)."""
         if advance:
             self.use(self.n)
             self.n += 1
-        return ops.di_transform(adv, self.geom, out=self.image).detach().requires_grad_(True)
+        return ops.di_transform(adv, self.geom, out=self.image if out is None else out).detach().requires_grad_(True)
 
     def adjoint(self, gd):
         return ops.di_adjoint(gd, self.geom, out=self.grad)
@@ -444,19 +474,79 @@ def _diversity(spec, like, n_evals, norm, decay, taps):
     return _Diversity(spec, like, n_evals, scratch=decay is not None or taps is not None or norm != np.inf)
 
 
-def _leaf(adv, di):
-    return adv.detach().requires_grad_(True) if di is None else di.leaf(adv)
+class _Scales:
+    """The SI-NI-FGSM state of one operator call: scales and weights on the host and -- allocated once, so that a
+    captured iteration finds them at static addresses -- the scaled copies the model sees, their DI transforms when
+    there is input diversity, one word for the losses of the copies after the first and, unless the caller only runs the
+    fused L-inf step (``ops.linf_si_step``), the combined gradient.  ``mom``: look ahead along its momentum (Nesterov)."""
+
+    def __init__(self, spec, like, eps_iter, mom, di, scratch=True):
+        scales, nesterov = spec
+        self.scales, self.weights = scales, ops.si_weights(scales)
+        self.mom = mom if nesterov else None
+        self.lookahead = float(eps_iter) * mom.decay if nesterov else 0.0
+        shape = (len(scales),) + tuple(like.shape)
+        self.images = torch.empty(shape, dtype=torch.float32, device=like.device)
+        self.transformed = torch.empty(shape, dtype=torch.float32, device=like.device) if di is not None else None
+        self.ghat = torch.empty_like(like, memory_format=torch.contiguous_format) if scratch else None
+        self.slot = _LossSlot(torch.zeros(1, dtype=torch.float32, device=like.device), 0)
+
+    def copies(self, adv):
+        return ops.si_copies(adv, self.scales, m=None if self.mom is None else self.mom.m, lookahead=self.lookahead,
+                             out=self.images)
+
+    def combine(self, grads):
+        return ops.si_combine(grads, self.weights, out=self.ghat)
+
+
+def _scales(spec, like, eps_iter, norm, mom, ti, di):
+    """None without SI / NI; the combined-gradient scratch is needed by every update but the plain L-inf one."""
+    if spec is None:
+        return None
+    return _Scales(spec, like, eps_iter, mom, di,
+                   scratch=mom is not None or ti is not None or di is not None or norm != np.inf)
+
+
+def _evaluate(adv, si, di, call, advance=True):
+    """One gradient evaluation at ``adv``.  ``call(leaf, first)`` runs the white box and the loss on one leaf and leaves
+    the gradient in ``leaf.grad``.  Without ``si``: one call on ``adv`` (or its DI transform).  With it: the copies in one
+    launch, then one call per copy in ascending order, each on a leaf of its own; all copies of the evaluation share its
+    DI rows, so the adjoint is linear over them and the combination may precede it.
+    Returns ``(first leaf, gradient)``; with ``si`` the gradient is the list of the copies' gradients."""
+    if si is None:
+        leaf = adv.detach().requires_grad_(True) if di is None else di.leaf(adv, advance=advance)
+        call(leaf, True)
+        return leaf, _grad_of(leaf)
+    images = si.copies(adv)
+    first, grads = None, []
+    for i in range(images.shape[0]):
+        if di is None:
+            leaf = images[i].detach().requires_grad_(True)
+        else:
+            leaf = di.leaf(images[i], advance=advance and i == 0, out=si.transformed[i])
+        call(leaf, i == 0)
+        grads.append(_grad_of(leaf))
+        if i == 0:
+            first = leaf
+    return first, grads
 
 
 def _fgm_update(x, grad, eps, norm, clip_min, clip_max, flag=None, out=None, check_range=True, mom=None, ti=None,
-                di=None):
+                di=None, si=None):
     """``flag``: range violations of ``x`` (``check_range``) and, for the L2 / L1 updates, the degenerate-gradient bit
     that stands for the self-check asserts of the reference's ``optimize_linear`` (utils.py:101-104, :110-116).
     ``mom``: accumulate ``grad`` into the momentum first and step along the momentum instead.
     ``ti``: smooth ``grad`` first (TI-FGSM; with momentum the smoothed gradient is what gets normalised and accumulated,
     TI-MI-FGSM); the plain L-inf update does both in one launch.
     ``di``: ``grad`` is the gradient at the TRANSFORMED image (DI-FGSM): the transform's adjoint takes it back to ``x``
-    first, in the same launch for the plain L-inf update, in front of smoothing / momentum / L2 otherwise."""
+    first, in the same launch for the plain L-inf update, in front of smoothing / momentum / L2 otherwise.
+    ``si``: ``grad`` is the LIST of the scale copies' gradients (SI-NI-FGSM): their weighted sum comes first of all, in
+    the same launch for the plain L-inf update, into a scratch in front of the rest of the chain otherwise."""
+    if si is not None:
+        if di is None and ti is None and mom is None and norm == np.inf:
+            return ops.linf_si_step(x, grad, None, si.weights, eps, 0.0, clip_min, clip_max,
+                                    flag=flag if check_range else None, out=out)
+        grad = si.combine(grad)
     if di is not None:
         if ti is None and mom is None and norm == np.inf:
             return ops.linf_di_step(x, grad, None, di.geom, eps, 0.0, clip_min, clip_max,
@@ -480,7 +570,11 @@ def _fgm_update(x, grad, eps, norm, clip_min, clip_max, flag=None, out=None, che
 
 
 def _fgm_then_project(x, grad, x0, eps_iter, eps, norm, clip_min, clip_max, out, flag=None, mom=None, ti=None,
-                      di=None):
+                      di=None, si=None):
+    if si is not None:
+        if di is None and ti is None and mom is None and norm == np.inf:
+            return ops.linf_si_step(x, grad, x0, si.weights, eps_iter, eps, clip_min, clip_max, out=out)
+        grad = si.combine(grad)
     if di is not None:
         if ti is None and mom is None and norm == np.inf:
             return ops.linf_di_step(x, grad, x0, di.geom, eps_iter, eps, clip_min, clip_max, out=out)
@@ -531,36 +625,44 @@ def _grad_of(leaf):
 # ----------------------------------------------------------------------------------------- FGM
 def fast_gradient_method(model_fn, x, eps, norm, ori_x, clip_min=None, clip_max=None, y=None, targeted=False,
                          sanity_checks=False, ls=None, bkp=None, bkp_y=None, *, flavor=ALBEF, per_sample=False,
-                         ti_kernel=None, diversity_prob=None, di_shrink=32, di_rng=None):
+                         ti_kernel=None, diversity_prob=None, di_shrink=32, di_rng=None, si_copies=None):
     """One FGM step; returns ``(adv_x, loss)`` (``loss`` is a 0-d device tensor), bare ``x`` when ``eps == 0``.
     ``ti_kernel`` (extension, keyword-only): TI-FGSM smoothing of the gradient, as in ``projected_gradient_descent``.
     ``diversity_prob`` / ``di_shrink`` / ``di_rng`` (extensions, keyword-only): DI-FGSM, as there (one evaluation).
+    ``si_copies`` (extension, keyword-only): SI-FGSM scale copies, as there; ``loss`` is copy 0's.
     Reference: A fast_gradient_method.py:30-165, V :36-152 (the VLMO copy has no ``bkp``/``bkp_y``)."""
     _check_flavor(flavor)
     _validate_fgm(norm, eps, clip_min, clip_max)
     taps = _validate_ti(ti_kernel)
     spec = _validate_di(diversity_prob, di_shrink, di_rng)
+    sspec = _validate_si(si_copies)
     if eps == 0:
         return x
     xin = _as_image(x)
     check_range = sanity_checks and (clip_min is not None or clip_max is not None)
     flag = ops.new_flag(xin.device) if (check_range or norm != np.inf) else None
     di = _diversity(spec, xin, 1, norm, None, taps)
-    leaf = _leaf(xin, di)                              # without DI it shares storage with x: nothing is written in place
+    ti = _smoother(taps, xin, norm, None)
+    si = _scales(sspec, xin, eps, norm, None, ti, di)
     loss_buf = torch.zeros(1, dtype=torch.float32, device=xin.device)
-    _loss_and_grad(model_fn, [leaf], leaf, y, ls, flavor, targeted, _LossSlot(loss_buf, 0), bkp=bkp, bkp_y=bkp_y,
-                   flag=flag, per_sample=per_sample)
+
+    def call(leaf, first):      # without DI / SI the leaf shares storage with x: nothing is written in place
+        _loss_and_grad(model_fn, [leaf], leaf, y, ls, flavor, targeted, _LossSlot(loss_buf, 0) if first else si.slot,
+                       bkp=bkp, bkp_y=bkp_y, flag=flag, per_sample=per_sample)
+
+    _, grad = _evaluate(xin, si, di, call)
     _two_sided(clip_min, clip_max)
-    adv = _fgm_update(xin, _grad_of(leaf), eps, norm, clip_min, clip_max, flag=flag, check_range=check_range,
-                      ti=_smoother(taps, xin, norm, None), di=di)
+    adv = _fgm_update(xin, grad, eps, norm, clip_min, clip_max, flag=flag, check_range=check_range, ti=ti, di=di, si=si)
     assert _check_flag(flag, norm, sanity_checks), "input x is outside [clip_min, clip_max]"
     return adv, loss_buf[0]
 
 
 def fast_gradient_method_vl(model_fn, x, eps, norm, ori_x, clip_min=None, clip_max=None, y=None, targeted=False,
                             sanity_checks=False, ls=None, text_emb_pick=None, *, flavor=ALBEF, ti_kernel=None,
-                            diversity_prob=None, di_shrink=32, di_rng=None):
+                            diversity_prob=None, di_shrink=32, di_rng=None, si_copies=None):
     """FGM on ``x = [image, text_embeds]``; returns ``(adv_image, text_grad[:, text_emb_pick])``.
+    ``si_copies`` (extension, keyword-only): SI-FGSM scale copies of the IMAGE, as in ``projected_gradient_descent``;
+    ``x[0]`` is then copy 0's leaf, the text gradient is copy 0's and the other copies see the text embeddings detached.
     ``ti_kernel`` (extension, keyword-only): TI-FGSM smoothing of the IMAGE gradient, as in ``projected_gradient_descent``.
     ``diversity_prob`` / ``di_shrink`` / ``di_rng`` (extensions, keyword-only): DI-FGSM on the IMAGE, as there; ``x[0]`` of
     the caller's list is then the transformed leaf the model saw.
@@ -570,6 +672,7 @@ def fast_gradient_method_vl(model_fn, x, eps, norm, ori_x, clip_min=None, clip_m
     _validate_fgm(norm, eps, clip_min, clip_max)
     taps = _validate_ti(ti_kernel)
     spec = _validate_di(diversity_prob, di_shrink, di_rng)
+    sspec = _validate_si(si_copies)
     if eps == 0:
         return x
     img = _as_image(x[0], "x[0]")
@@ -577,14 +680,22 @@ def fast_gradient_method_vl(model_fn, x, eps, norm, ori_x, clip_min=None, clip_m
     check_range = sanity_checks and (clip_min is not None or clip_max is not None)
     flag = ops.new_flag(img.device) if (check_range or norm != np.inf) else None
     di = _diversity(spec, img, 1, norm, None, taps)
-    x[0] = _leaf(img, di)
+    ti = _smoother(taps, img, norm, None)
+    si = _scales(sspec, img, eps, norm, None, ti, di)
     x[1] = emb.detach().requires_grad_(True)
     loss_buf = torch.zeros(1, dtype=torch.float32, device=img.device)
-    _loss_and_grad(model_fn, [x[0], x[1]], [x[0], x[1]], y, ls, flavor, targeted, _LossSlot(loss_buf, 0), vl=True)
+
+    def call(leaf, first):
+        if first:
+            x[0] = leaf
+            _loss_and_grad(model_fn, [leaf, x[1]], [leaf, x[1]], y, ls, flavor, targeted, _LossSlot(loss_buf, 0), vl=True)
+        else:
+            _loss_and_grad(model_fn, [leaf], [leaf, emb.detach()], y, ls, flavor, targeted, si.slot, vl=True)
+
+    _, grad = _evaluate(img, si, di, call)
     text_grad = ops.gather_rows(_grad_of(x[1]), text_emb_pick)
     _two_sided(clip_min, clip_max)
-    adv = _fgm_update(img, _grad_of(x[0]), eps, norm, clip_min, clip_max, flag=flag, check_range=check_range,
-                      ti=_smoother(taps, img, norm, None), di=di)
+    adv = _fgm_update(img, grad, eps, norm, clip_min, clip_max, flag=flag, check_range=check_range, ti=ti, di=di, si=si)
     assert _check_flag(flag, norm, sanity_checks), "input x is outside [clip_min, clip_max]"
     return adv, text_grad
 
@@ -618,7 +729,7 @@ def _finish(flag, eps, eps_iter, norm, clip_min, clip_max, sanity_checks):
 
 
 def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, clip_min, clip_max, nb_iter, loss_buf,
-                       mom=None, ti=None, di=None):
+                       mom=None, ti=None, di=None, si=None):
     """``nb_iter`` feature-loss L-inf iterations with iterations 1.. replayed from ONE captured hipGraph.
 
     For the launch-bound regime (the reference's own batch 1: ~10^3 kernels of a few microseconds per iteration):
@@ -634,14 +745,19 @@ def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, cl
     the kernel arguments and the smoothed-gradient scratch was allocated before capture.
     ``di``: the transform and the fused DI step (or the adjoint in front of the rest) are captured against the static
     geometry row; a device-to-device copy of the iteration's rows into it precedes each replay (eager, like the loss word).
+    ``si``: the copies launch, one model call per copy and the combining update are captured; the copies and the scratch
+    were allocated before capture, and the gradients' addresses, which travel by value in the kernel arguments, are the
+    graph's own and the same at every replay.
     """
     word = torch.zeros(1, dtype=torch.float32, device=cur.device)
 
+    def call(leaf, first):
+        _loss_and_grad(model_fn, [leaf], leaf, y, 1, flavor, targeted, _LossSlot(word, 0) if first else si.slot)
+
     def iteration():
-        leaf = cur.detach().requires_grad_(True) if di is None else di.leaf(cur, advance=False)
-        _loss_and_grad(model_fn, [leaf], leaf, y, 1, flavor, targeted, _LossSlot(word, 0))
-        _fgm_then_project(cur, _grad_of(leaf), x0, eps_iter, eps, np.inf, clip_min, clip_max, cur,   # in place: static
-                          mom=mom, ti=ti, di=di)                                                      # address
+        _, grad = _evaluate(cur, si, di, call, advance=False)
+        _fgm_then_project(cur, grad, x0, eps_iter, eps, np.inf, clip_min, clip_max, cur,   # in place: static address
+                          mom=mom, ti=ti, di=di, si=si)
 
     main = torch.cuda.current_stream(cur.device)
     side = torch.cuda.Stream(device=cur.device)
@@ -668,7 +784,7 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
                                ori_x=None, time=None, targeted=False, rand_init=True, rand_minmax=None,
                                sanity_checks=True, ls=None, *, flavor=ALBEF, init_eta=None, graph=None,
                                per_sample=False, decay_factor=None, momentum=None, ti_kernel=None,
-                               diversity_prob=None, di_shrink=32, di_rng=None):
+                               diversity_prob=None, di_shrink=32, di_rng=None, si_copies=None, nesterov=False):
     """PGD over a frozen white box; returns ``(adv_x, loss_list)``, bare ``x`` when eps or eps_iter is 0.
 
     ``ls == 1``: feature loss, ``model_fn`` a callable.  Otherwise the dual-loss loop: ``model_fn = [feature_fn,
@@ -707,6 +823,18 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
     (``ops.linf_di_step``); with ``ti_kernel`` / ``decay_factor`` / L2 the adjoint (``ops.di_adjoint``) feeds those paths
     unchanged (DI + TI, DI + MI, all three).  ``x`` must be ``(B, C, H, W)``.  With ``diversity_prob=None`` (default)
     nothing changes and no random number is drawn.
+    ``si_copies`` / ``nesterov`` (extensions, keyword-only): SI-NI-FGSM (Lin et al. 2020; the reference tree has neither).
+    ``si_copies`` an int n in 1..8 (the paper's scales ``1, 1/2, ..., 2^-(n-1)``) or a sequence of 1..8 finite positive
+    scales: every gradient evaluation calls the model once per scaled copy ``s_i * adv``, in ascending ``i``, and the
+    gradient is ``sum_i (s_i / n) * g_i`` -- the paper's average with the chain rule through the scaling.  ``nesterov``
+    (needs ``decay_factor``): the copies are taken at the look-ahead point ``adv + eps_iter * decay_factor * m``, unclipped
+    as in the authors' code; alone it is one copy at scale 1.  The copies come from one launch (``ops.si_copies``); the
+    plain L-inf update combines the gradients in the same launch (``ops.linf_si_step``), every other path combines into
+    a scratch (``ops.si_combine``) in front of the DI adjoint, the smoothing, the momentum and the update, which run
+    unchanged.  With DI every copy of an evaluation is transformed with that evaluation's rows (the draws are those of
+    the call without ``si_copies``).  The reported loss is copy 0's; a closure that draws random numbers draws once per
+    call.  The dual loop does all of this for both of its evaluations.  With ``si_copies=None, nesterov=False``
+    (default) nothing changes.
     Reference: A projected_gradient_descent.py:10-199, V :10-196.
     """
     _check_flavor(flavor)
@@ -714,6 +842,7 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
     decay = _validate_decay(decay_factor)
     taps = _validate_ti(ti_kernel)
     spec = _validate_di(diversity_prob, di_shrink, di_rng)
+    sspec = _validate_si(si_copies, nesterov, decay_factor)
     if unchanged:
         return x
     xin = _as_image(x)
@@ -733,6 +862,7 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
     mom = None if decay is None else _Momentum(decay, xin, momentum)
     ti = _smoother(taps, xin, norm, decay)
     di = _diversity(spec, xin, nb_iter * (2 if dual else 1), norm, decay, taps)
+    si = _scales(sspec, xin, eps_iter, norm, mom, ti, di)
     ws = ops.Workspace()       # loss-gradient / CE scratch buffers live for the whole call, not per iteration
     bad_flag = flag if flag is not None else (
         ops.new_flag(xin.device) if ((dual and sanity_checks) or norm != np.inf) else None)
@@ -743,38 +873,43 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
             raise ValueError("graph=True supports the feature-loss (ls == 1) L-inf loop only")
         _two_sided(clip_min, clip_max)
         adv = _graphed_linf_loop(model_fn, adv, x0, y, flavor, targeted, eps_iter, eps, clip_min, clip_max, nb_iter,
-                                 loss_buf, mom=mom, ti=ti, di=di)
+                                 loss_buf, mom=mom, ti=ti, di=di, si=si)
         n_loss, nb_iter = nb_iter, 0
+
+    def evaluate(fn, at, y_, ls_, **extra):
+        """One gradient evaluation at ``at`` with the loss of copy 0 in the next slot of the loss buffer."""
+        slot = _LossSlot(loss_buf, n_loss)
+
+        def call(leaf, first):
+            _loss_and_grad(fn, [leaf], leaf, y_, ls_, flavor, targeted, slot if first else si.slot, ws=ws,
+                           flag=bad_flag, **extra)
+
+        return _evaluate(at, si, di, call)[1]
+
     for _ in range(nb_iter):
         if not dual:
-            leaf = _leaf(adv, di)
-            _loss_and_grad(model_fn, [leaf], leaf, y, ls, flavor, targeted, _LossSlot(loss_buf, n_loss), ws=ws,
-                           flag=bad_flag)
+            grad = evaluate(model_fn, adv, y, ls)
             n_loss += 1
             _two_sided(clip_min, clip_max)
-            adv = _fgm_then_project(adv, _grad_of(leaf), x0, eps_iter, eps, norm, clip_min, clip_max, buf[1 - cur],
-                                    flag=bad_flag, mom=mom, ti=ti, di=di)
+            adv = _fgm_then_project(adv, grad, x0, eps_iter, eps, norm, clip_min, clip_max, buf[1 - cur],
+                                    flag=bad_flag, mom=mom, ti=ti, di=di, si=si)
         else:
             if flavor == ALBEF:      # A :163,177-181 slices y; V :162,175 passes it whole
                 y_feat, y_mlm, extra = [y[1], y[2]], [y[0]], dict(bkp=model_fn[0], bkp_y=[y[1], y[2]])
             else:
                 y_feat, y_mlm, extra = y, y, {}
-            leaf = _leaf(adv, di)
-            _loss_and_grad(model_fn[0], [leaf], leaf, y_feat, 1, flavor, targeted, _LossSlot(loss_buf, n_loss), ws=ws,
-                           flag=bad_flag)
+            grad = evaluate(model_fn[0], adv, y_feat, 1)
             n_loss += 1
             _two_sided(clip_min, clip_max)
-            mid = _fgm_update(adv, _grad_of(leaf), eps_iter, norm, clip_min, clip_max, out=buf[1 - cur], flag=bad_flag,
-                              check_range=False, mom=mom, ti=ti, di=di)
-            leaf = _leaf(mid, di)
-            _loss_and_grad(model_fn[1], [leaf], leaf, y_mlm, 0, flavor, targeted, _LossSlot(loss_buf, n_loss), ws=ws,
-                           flag=bad_flag, per_sample=per_sample, **extra)
+            mid = _fgm_update(adv, grad, eps_iter, norm, clip_min, clip_max, out=buf[1 - cur], flag=bad_flag,
+                              check_range=False, mom=mom, ti=ti, di=di, si=si)
+            grad = evaluate(model_fn[1], mid, y_mlm, 0, per_sample=per_sample, **extra)
             n_loss += 1
-            adv = _fgm_then_project(mid, _grad_of(leaf), x0, eps_iter, eps, norm, clip_min, clip_max, buf[cur],
-                                    flag=bad_flag, mom=mom, ti=ti, di=di)
+            adv = _fgm_then_project(mid, grad, x0, eps_iter, eps, norm, clip_min, clip_max, buf[cur],
+                                    flag=bad_flag, mom=mom, ti=ti, di=di, si=si)
             cur = 1 - cur            # result sits in buf[cur] again after the flip below
         cur = 1 - cur
-        del leaf
+        del grad
     _finish(bad_flag, eps, eps_iter, norm, clip_min, clip_max, sanity_checks)
     loss_list = loss_buf[:n_loss].tolist()     # single device->host transfer for the whole loop
     return adv, loss_list
@@ -784,19 +919,22 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
                                   ori_x=None, time=None, targeted=False, rand_init=True, rand_minmax=None,
                                   sanity_checks=True, ls=None, attack_mask=None, *, flavor=ALBEF, init_eta=None,
                                   decay_factor=None, momentum=None, ti_kernel=None, diversity_prob=None, di_shrink=32,
-                                  di_rng=None):
+                                  di_rng=None, si_copies=None, nesterov=False):
     """PGD on ``x = [image, text_embeds]`` (only the image moves); returns ``(adv_image, text_embed_gradient)`` of
     the last iteration.  Only ``ls == 1`` is supported (``ValueError`` otherwise), as in the reference.
     ``decay_factor`` / ``momentum`` (extensions, keyword-only): MI-FGSM on the image, as in
     ``projected_gradient_descent``; ``momentum`` has the image's shape.  ``ti_kernel`` (extension, keyword-only):
     TI-FGSM smoothing of the image gradient, as there.  ``diversity_prob`` / ``di_shrink`` / ``di_rng`` (extensions,
-    keyword-only): DI-FGSM, as there; only the image is transformed.
+    keyword-only): DI-FGSM, as there; only the image is transformed.  ``si_copies`` / ``nesterov`` (extensions,
+    keyword-only): SI-NI-FGSM on the image, as there; the text gradient is copy 0's and the other copies see the text
+    embeddings detached.
     Reference: A projected_gradient_descent_vl.py:10-168, V :10-164."""
     _check_flavor(flavor)
     unchanged = _validate_pgd(norm, eps, eps_iter, clip_min, clip_max)
     decay = _validate_decay(decay_factor)
     taps = _validate_ti(ti_kernel)
     spec = _validate_di(diversity_prob, di_shrink, di_rng)
+    sspec = _validate_si(si_copies, nesterov, decay_factor)
     if unchanged:
         return x
     img = _as_image(x[0], "x[0]")
@@ -817,19 +955,28 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
     mom = None if decay is None else _Momentum(decay, img, momentum)
     ti = _smoother(taps, img, norm, decay)
     di = _diversity(spec, img, nb_iter, norm, decay, taps)
+    si = _scales(sspec, img, eps_iter, norm, mom, ti, di)
     if attack_mask is not None and not isinstance(attack_mask, ops.RowIndex):   # validated + uploaded once per call
         attack_mask = ops.RowIndex(attack_mask, emb.shape[1], emb.device)
     for it in range(nb_iter):
-        leaf_img = _leaf(adv, di)
         leaf_txt = emb.detach().requires_grad_(True)
-        _loss_and_grad(model_fn, [leaf_img, leaf_txt], [leaf_img, leaf_txt], y, ls, flavor, targeted,
-                       _LossSlot(loss_buf, it), vl=True, ws=ws, flag=flag)
+        slot = _LossSlot(loss_buf, it)
+
+        def call(leaf_img, first):
+            if first:
+                _loss_and_grad(model_fn, [leaf_img, leaf_txt], [leaf_img, leaf_txt], y, ls, flavor, targeted, slot,
+                               vl=True, ws=ws, flag=flag)
+            else:
+                _loss_and_grad(model_fn, [leaf_img], [leaf_img, emb.detach()], y, ls, flavor, targeted, si.slot, vl=True,
+                               ws=ws, flag=flag)
+
+        grad = _evaluate(adv, si, di, call)[1]
         text_grad = ops.gather_rows(_grad_of(leaf_txt), attack_mask)
         _two_sided(clip_min, clip_max)
-        adv = _fgm_then_project(adv, _grad_of(leaf_img), x0, eps_iter, eps, norm, clip_min, clip_max, buf[1 - cur],
-                                flag=flag, mom=mom, ti=ti, di=di)
+        adv = _fgm_then_project(adv, grad, x0, eps_iter, eps, norm, clip_min, clip_max, buf[1 - cur],
+                                flag=flag, mom=mom, ti=ti, di=di, si=si)
         cur = 1 - cur
-        del leaf_img, leaf_txt
+        del grad, leaf_txt
     _finish(flag, eps, eps_iter, norm, clip_min, clip_max, sanity_checks)
     return adv, text_grad
 
@@ -838,7 +985,7 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
 def momentum_iterative_method(model_fn, x, eps, eps_iter, nb_iter, norm, clip_min=None, clip_max=None, y=None,
                               ori_x=None, targeted=False, decay_factor=1.0, sanity_checks=True, ls=1, *, flavor=ALBEF,
                               graph=None, momentum=None, ti_kernel=None, diversity_prob=None, di_shrink=32,
-                              di_rng=None):
+                              di_rng=None, si_copies=None, nesterov=False):
     """The momentum iterative method (Dong et al. 2017) on this project's losses; returns ``(adv_x, loss_list)`` like
     ``projected_gradient_descent``, so a driver can swap one for the other.
 
@@ -848,11 +995,13 @@ def momentum_iterative_method(model_fn, x, eps, eps_iter, nb_iter, norm, clip_mi
     value, adds it to ``decay_factor`` times the momentum (:88-95) and steps along the momentum (:97-103).  ``ori_x``
     (centre of the eps-ball) defaults to ``x``; ``ls``, ``flavor``, ``graph``, ``momentum`` and ``ti_kernel``
     (TI-MI-FGSM, the combination the TI paper recommends) as in ``projected_gradient_descent``, which runs the loop;
-    ``diversity_prob`` / ``di_shrink`` / ``di_rng`` as there too (M-DI2-FGSM; with ``ti_kernel`` TI-DIM)."""
+    ``diversity_prob`` / ``di_shrink`` / ``di_rng`` as there too (M-DI2-FGSM; with ``ti_kernel`` TI-DIM), and so are
+    ``si_copies`` / ``nesterov`` (SI-NI-FGSM; with the other keys SI-NI-TI-DIM)."""
     if norm != 1 and decay_factor is None:
         raise ValueError("decay_factor must be a number (use projected_gradient_descent for the attack without momentum)")
     return projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_min=clip_min, clip_max=clip_max,
                                       y=y, ori_x=x if ori_x is None else ori_x, time=None, targeted=targeted,
                                       sanity_checks=sanity_checks, ls=ls, flavor=flavor, graph=graph,
                                       decay_factor=decay_factor, momentum=momentum, ti_kernel=ti_kernel,
-                                      diversity_prob=diversity_prob, di_shrink=di_shrink, di_rng=di_rng)
+                                      diversity_prob=diversity_prob, di_shrink=di_shrink, di_rng=di_rng,
+                                      si_copies=si_copies, nesterov=nesterov)

@@ -529,6 +529,116 @@ def linf_di_step(x, gd, x0, geom, eps_iter, eps, clip_min, clip_max, flag=None, 
     return out
 
 
+# ----------------------------------------------------------------------------------------- scale copies (SI-NI-FGSM)
+SI_MAX_COPIES = 8      # VQA_SI_MAX_COPIES of include/vqattack_hip.h (vqa_si_max_copies())
+
+
+def si_scales(copies):
+    """The paper's scales ``1, 1/2, ..., 2^-(copies - 1)`` (Lin et al. 2020) as a numpy float32 array."""
+    copies = int(copies)
+    if copies < 1 or copies > SI_MAX_COPIES:
+        raise ValueError("copies must be in 1..{}, got {}".format(SI_MAX_COPIES, copies))
+    return np.ldexp(np.float32(1.0), -np.arange(copies)).astype(np.float32)
+
+
+def _si_host(values, name):
+    """(numpy float32 array, ctypes float array) of a host sequence of 1..SI_MAX_COPIES floats."""
+    w = np.ascontiguousarray(values, dtype=np.float32)
+    if w.ndim != 1 or w.size < 1 or w.size > SI_MAX_COPIES:
+        raise ValueError("{} must be a 1-d sequence of 1..{} floats, got shape {}".format(name, SI_MAX_COPIES, w.shape))
+    return w, (ctypes.c_float * w.size)(*w.tolist())
+
+
+def si_weights(scales):
+    """``w_i = float32(s_i) / float32(n)``: the paper's average over the ``n`` copies together with the chain rule through
+    the scaling (the gradient with respect to the image of a loss evaluated at ``s_i * image``)."""
+    s, _ = _si_host(scales, "scales")
+    return (s / np.float32(s.size)).astype(np.float32)
+
+
+def si_copies(x, scales, m=None, lookahead=0.0, out=None):
+    """``out[i] = s_i * x``, or ``s_i * (x + lookahead * m)`` with the momentum ``m``: every copy in one launch, as an
+    ``(n,) + x.shape`` tensor.  No clamp, no projection.  ``out`` must not overlap ``x`` or ``m``; each ``out[i]`` must be
+    contiguous, and the copies may lie further apart than ``x.numel()`` (the batch prefix of a larger buffer)."""
+    s, buf = _si_host(scales, "scales")
+    dev_f32(x, "x")
+    if m is not None:
+        dev_f32(m, "momentum")
+        if m.shape != x.shape:
+            raise ValueError("momentum shape {} != x shape {}".format(tuple(m.shape), tuple(x.shape)))
+    shape = (int(s.size),) + tuple(x.shape)
+    same_device(x, m, out)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        dev_f32(out, "out", contiguous=False)
+        if tuple(out.shape) != shape:
+            raise ValueError("out has shape {}, expected {}".format(tuple(out.shape), shape))
+        if not out[0].is_contiguous() or (s.size > 1 and out.stride(0) < x.numel()):
+            raise ValueError("every out[i] must be contiguous and the copies must not overlap")
+    if x.numel() == 0:
+        return out
+    stride = out.stride(0) if s.size > 1 else x.numel()
+    with _on(x):
+        check(lib().vqa_si_copies(ptr(x), ptr(m), ptr(out), x.numel(), stride, buf, int(s.size), float(lookahead),
+                                  stream_for(x)), "vqa_si_copies")
+    return out
+
+
+def _si_grads(grads, weights):
+    """(ctypes pointer array, ctypes float array, copies) of a list of same-shape gradient tensors and their weights."""
+    if isinstance(grads, torch.Tensor) or not isinstance(grads, (list, tuple)):
+        raise TypeError("grads must be a list or tuple of tensors (autograd hands back one per copy), got {}".format(
+            type(grads)))
+    if len(grads) < 1 or len(grads) > SI_MAX_COPIES:
+        raise ValueError("grads must hold 1..{} tensors, got {}".format(SI_MAX_COPIES, len(grads)))
+    for i, g in enumerate(grads):
+        dev_f32(g, "grads[{}]".format(i))
+        if g.shape != grads[0].shape:
+            raise ValueError("grads[{}] has shape {}, grads[0] {}".format(i, tuple(g.shape), tuple(grads[0].shape)))
+    w, wbuf = _si_host(weights, "weights")
+    if w.size != len(grads):
+        raise ValueError("{} weights for {} gradients".format(w.size, len(grads)))
+    same_device(*grads)
+    return (ctypes.c_void_p * len(grads))(*[g.data_ptr() for g in grads]), wbuf, len(grads)
+
+
+def si_combine(grads, weights, out=None):
+    """``out = w_0 * g_0 + w_1 * g_1 + ...`` (ascending, one rounding per operation, starting from the first product).
+    ``out`` may alias no gradient."""
+    pbuf, wbuf, copies = _si_grads(grads, weights)
+    same_device(grads[0], out)
+    out = _out_like(grads[0], out)
+    if out.numel() == 0:
+        return out
+    with _on(out):
+        check(lib().vqa_si_combine(pbuf, wbuf, copies, ptr(out), out.numel(), stream_for(out)), "vqa_si_combine")
+    return out
+
+
+def linf_si_step(x, grads, x0, weights, eps_iter, eps, clip_min, clip_max, flag=None, out=None):
+    """``si_combine`` and ``linf_step`` on its result in one pass, 4 * copies + 12 B/element; ``x0=None``: and
+    ``linf_fgm`` (no projection).  The combined gradient never reaches memory; ``out`` may be ``x``."""
+    dev_f32(x, "x")
+    if x0 is not None:
+        dev_f32(x0, "ori_x")
+    pbuf, wbuf, copies = _si_grads(grads, weights)
+    if grads[0].shape != x.shape or (x0 is not None and x0.shape != x.shape):
+        raise ValueError("shape mismatch: x {}, grads {}, ori_x {}".format(
+            tuple(x.shape), tuple(grads[0].shape), None if x0 is None else tuple(x0.shape)))
+    same_device(x, grads[0], x0, out, flag)
+    out = _out_like(x, out)
+    mode, lo, hi = _clip_args(clip_min, clip_max)
+    if flag is not None and mode:
+        mode |= VQA_CHECK_RANGE
+    if x.numel() == 0:
+        return out
+    with _on(x):
+        check(lib().vqa_linf_si_step(ptr(x), pbuf, wbuf, copies, ptr(x0), ptr(out), x.numel(), eps_iter, eps, lo, hi,
+                                     mode, ptr(flag), stream_for(x)), "vqa_linf_si_step")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- loss
 _COS_EPS = 1e-6  # nn.CosineSimilarity(eps=1e-6) in the reference
 _partials = {}
