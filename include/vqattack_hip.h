@@ -486,6 +486,18 @@ int vqa_attn_bwd(const float* q, const float* k, const float* v, const float* bi
                  const float* lse, const float* scores, float* delta, float* dq, float* dk, float* dv, float* ds_ws, int B,
                  int H, int Sq, int Sk, const long* strides, const long* bias_strides, const long* grad_strides,
                  float scale, int nsplit, float* split_ws, vqa_stream_t stream);
+/* The saved-scores form of vqa_attn_bwd (scores != NULL, ds_ws != NULL, nsplit == 1) with the three products of its
+ * key-block kernel -- dP = go . v^T, dv = P^T . go, dk = dS^T . q -- on the bf16 matrix pipe as six exact bf16 plane
+ * products each (the arithmetic of vqa_attn_fwd_x6); the delta pre-pass, the dS^T workspace and the dq kernel are
+ * vqa_attn_bwd's.  Same arguments; results are fp32-grade and differ from vqa_attn_bwd's by rounding order.  Returns
+ * VQA_ERR_SHAPE and launches nothing unless scores, ds_ws and nsplit == 1 are all given: every other form is
+ * vqa_attn_bwd's (and so is a q or go whose sequence stride is negative or 2^24 elements and more).  `scores` may come
+ * from either forward.  inf / NaN in go, q, v may come out as NaN.  Additive export:
+ * the ABI version stays. */
+int vqa_attn_bwd_x6(const float* q, const float* k, const float* v, const float* bias, const float* o, const float* go,
+                    const float* lse, const float* scores, float* delta, float* dq, float* dk, float* dv, float* ds_ws,
+                    int B, int H, int Sq, int Sk, const long* strides, const long* bias_strides, const long* grad_strides,
+                    float scale, int nsplit, float* split_ws, vqa_stream_t stream);
 long vqa_attn_bwd_ws_floats(int B, int H, int Sq, int Sk);
 
 /* ---------------------------------------------------------------- input pipeline

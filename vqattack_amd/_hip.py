@@ -77,6 +77,7 @@ SIGNATURES = {
     "vqa_attn_split_ws_floats": (_l, [_i, _i, _i, _i, _i]),
     "vqa_attn_scores_floats": (_l, [_i, _i, _i, _i]),
     "vqa_attn_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _f, _i, _p, _p]),
+    "vqa_attn_bwd_x6": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _f, _i, _p, _p]),
     "vqa_attn_bwd_ws_floats": (_l, [_i, _i, _i, _i]),
     "vqa_ln_fwd": (_i, [_p] * 13 + [_l, _i, _l, _l, _f, _p]),
     "vqa_ln_bwd": (_i, [_p] * 13 + [_l, _i, _l, _l, _p]),

@@ -159,6 +159,25 @@ def forward_grade(nsplit, recomputing_backward=False):
     return want or FORWARD_DEFAULT
 
 
+BACKWARD_DEFAULT = "x6"
+
+
+def backward_grade(nsplit, have_scores, have_workspace):
+    """Which backward a call runs: ``"x6"`` (``vqa_attn_bwd_x6``: the dK / dV kernel's three products as six exact bf16
+    products each) or ``"f32"`` (``vqa_attn_bwd``, fp32 MFMA).  ``VQA_ATTN_BWD=x6`` / ``f32`` pins it (unset:
+    BACKWARD_DEFAULT) for the one form that has an x6 kernel: saved scores, a dS workspace and an unsplit loop.  Every
+    other call -- loop-split, no saved scores, no workspace -- runs fp32 whatever the switch says.  The x6 backward
+    starts from the saved scores and recomputes no q k^T, so it pairs with either forward grade: the lse cancellation
+    that keeps ``forward_grade`` away from the recomputing backward does not arise."""
+    import os
+    want = os.environ.get("VQA_ATTN_BWD")
+    if want and want not in ("x6", "f32"):
+        raise ValueError("VQA_ATTN_BWD must be 'x6' or 'f32', got '{}'".format(want))
+    if nsplit != 1 or not have_scores or not have_workspace:
+        return "f32"
+    return want or BACKWARD_DEFAULT
+
+
 def _forward(q, k, v, bias, bstr, scale, save_scores=False, key_hole=None):
     """Returns (o, lse, scores); ``scores`` is None unless ``save_scores`` and the buffer fits SCORES_LIMIT.
     ``key_hole``: int32 (B, 2) device tensor, see ``KeyHoleBias``."""
@@ -230,6 +249,7 @@ SCORES_LIMIT = 6 << 30
 
 
 def _backward(q, k, v, bias, bstr, o, lse, go, dq, dk, dv, scale, workspace=True, scores=None):
+    """Writes dq, dk, dv; returns the dS^T workspace the kernels used (None without one), for tests."""
     b, sq, h, _ = q.shape
     sk = k.shape[1]
     if go.stride(-1) != 1 or any(s % 4 for s in go.stride()[:-1]) or go.data_ptr() % 16:
@@ -246,12 +266,16 @@ def _backward(q, k, v, bias, bstr, o, lse, go, dq, dk, dv, scale, workspace=True
                    dk.stride(0), dk.stride(1), dk.stride(2), dv.stride(0), dv.stride(1), dv.stride(2)])
     nsplit = loop_split(b, h, sq, sk, q.device) if (ws is not None and scores is not None) else 1
     sws = _split_ws(b, h, sq, sk, nsplit, q.device)
+    # (the x6 kernel addresses a tile of q and go with 32-bit offsets: a row stride of 2^24 elements and more is fp32's)
+    x6 = backward_grade(nsplit, scores is not None, ws is not None) == "x6" and max(q.stride(1), go.stride(1)) < 1 << 24
+    entry = "vqa_attn_bwd_x6" if x6 else "vqa_attn_bwd"
     with torch.cuda.device(q.device):
-        check(lib().vqa_attn_bwd(ptr(q), ptr(k), ptr(v), ptr(bias), ptr(o), ptr(go), ptr(lse),
-                                 ptr(scores if ws is not None else None), ptr(delta), ptr(dq), ptr(dk), ptr(dv), ptr(ws),
-                                 b, h, sq, sk, strides, _longs(bstr) if bstr else None, gstr, scale, nsplit, ptr(sws),
-                                 stream_for(q)),
-              "vqa_attn_bwd")
+        check(getattr(lib(), entry)(ptr(q), ptr(k), ptr(v), ptr(bias), ptr(o), ptr(go), ptr(lse),
+                                    ptr(scores if ws is not None else None), ptr(delta), ptr(dq), ptr(dk), ptr(dv),
+                                    ptr(ws), b, h, sq, sk, strides, _longs(bstr) if bstr else None, gstr, scale, nsplit,
+                                    ptr(sws), stream_for(q)),
+              entry)
+    return ws
 
 
 class _Attention(torch.autograd.Function):

@@ -1246,6 +1246,361 @@ __global__ __launch_bounds__(kBlock, 2) void attn_bwd_dkv_kernel(const float* __
   }
 }
 
+// ------------------------------------------------------------------------------------------------ backward: dK, dV, bf16x6
+// attn_bwd_dkv_x6_kernel is the saved-scores, dS^T-storing, unsplit form of attn_bwd_dkv_kernel (<., true, true, false>,
+// the form a large batch runs) with its three products as six exact bf16 plane products each on
+// v_mfma_f32_32x32x16_bf16: 72 MFMAs of 32 cycles per wave and query tile instead of 96 of 64.  Lane = key, accumulator
+// rows = the tile's queries, P = exp2(fma(S, log2 e, -lse log2 e)) from the score tile staged through LDS, -delta as the
+// initial accumulator of the dP chain, dS = P o dP, the blocked fp32 dS^T store and the epilogue are the fp32 kernel's
+// text; the saved scores include the bias, so the kernel has no bias argument and no HAS_BIAS form, and K is not read.
+//   dP[q][key] += dO[q][.] . V[key][.]: B is the lane's own V row, split once per workgroup (k-step s of lane half h =
+//     dimensions 32 h + 8 s .. + 7, as Q in the x6 forward); A is the dO tile in FRAGMENT ORDER (`Gimg`: the forward's
+//     Kimg with query for key, its slots rotated so that 8-byte writes spread over the banks -- see the staging roles).
+//   dV^T[dim][key] += dO^T . P  and  dK^T[dim][key] += Q^T . dS: registers 8 s .. 8 s + 7 of P / dS, split in registers,
+//     are the B fragment of k-step s (of 2) over the queries 16 s + 8 (j >> 2) + 4 h + (j & 3); the A images of dO^T and
+//     Q^T (`GTimg`, `QTimg`) hold exactly those queries in that order, published as the forward publishes Vimg (same
+//     slot swizzle: every ds_read_b128 of the loop is conflict-free).
+// LDS: the three images (15 + 12 + 12 KiB) and the 17 KiB score tile are SINGLE-buffered, 56.3 KiB: two workgroups per CU
+// (double buffers would be 106 KiB and one workgroup, with nothing to cover its barriers).  The score tile of the next
+// query tile is requested at the top of a tile (HBM), its Q / dO pieces behind the dP chain (L2); they are split into
+// planes BEFORE the end-of-tile barrier -- the split's vector work overlaps the other waves' MFMAs -- then barrier, plane
+// and score stores, the dS^T stores, barrier.  238 VGPRs, no scratch: a spill's reload would wait on vmcnt, that is
+// for the score tile just requested, in every tile.  What keeps it there: one load and one split of dO feed both of its
+// images; addresses are uniform bases + 32-bit lane offsets; the last tile is peeled off the loop, so that the
+// prefetches of the loop's tiles are unconditional and the compiler knows which loads a wait has covered.
+// Non-finite values: the splits are the unchecked form (see the x6 forward).  P in [0, 1] is finite, and dS is finite
+// whenever dO, V and delta are; a masked score (-inf) gives P = 0 and dS = 0 exactly, so a key masked for every query
+// gets dK = dV = 0 exactly.  An inf or NaN in dO or Q has NaN correction planes: it turns dV / dK of EVERY key of its
+// (batch, head) at that dimension -- and, for dO, dS^T of its query row -- into NaN, where the fp32 kernel keeps inf and
+// gives NaN only through inf * 0.  A non-finite V row does the same to its own key's dS column, hence its dK.  Lanes of
+// keys beyond Sk may hold anything: they are B-operand columns and only reach their own, unstored column.
+struct X6BwdRegs {     // a fetched query tile: this thread's two queries x four dimensions of dO and of Q
+  f32x4 g[2], q[2];
+};
+struct X6BwdPlanes {   // the same, split: [dimension][plane], the two queries side by side
+  bf16x2 g[4][3], q[4][3];
+};
+constexpr int kX6RowPlane = 80 * 16;             // Gimg: 64 slots of a (k-step, plane) + room for the rotation by 4 s + h
+constexpr int kX6RowImg = 12 * kX6RowPlane;
+
+__global__ __launch_bounds__(kBlock, 2) void attn_bwd_dkv_x6_kernel(const float* __restrict__ q,
+                                                                    const float* __restrict__ v,
+                                                                    const float* __restrict__ go,
+                                                                    const float* __restrict__ lse,
+                                                                    const float* __restrict__ delta,
+                                                                    float* __restrict__ dk, float* __restrict__ dv,
+                                                                    AttnDims d, long dk_sb, long dk_ss, long dk_sh,
+                                                                    long dv_sb, long dv_ss, long dv_sh, long go_sb,
+                                                                    long go_ss, long go_sh, float* __restrict__ ds,
+                                                                    const float* __restrict__ scores) {
+  __shared__ __attribute__((aligned(16))) char Gimg[kX6RowImg];    // dO: 4 k-steps x 3 planes, lane (query, h)
+  __shared__ __attribute__((aligned(16))) char GTimg[kX6Tile];     // dO^T: 2 dim blocks x 2 k-steps x 3 planes, lane (dim, h)
+  __shared__ __attribute__((aligned(16))) char QTimg[kX6Tile];     // Q^T, likewise
+  __shared__ __attribute__((aligned(16))) float Sbuf[kTile * kDsStride];
+  __shared__ __attribute__((aligned(16))) float LDbuf[2 * kTile];    // -lse log2 e of the 32 queries, then -delta
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const int r = lane & 31, h = lane >> 5;
+  const BlockCoord bc = block_coord((d.Sk + 127) / 128, d.B, d.H);
+  const int b = bc.b, head = bc.head;
+  const int ki = bc.blk * 128 + wave * kTile + r;                     // this lane's key
+  const bool active = bc.blk * 128 + wave * kTile < d.Sk;
+  const bool all_live = bc.blk * 128 + wave * kTile + kTile <= d.Sk;    // wave-uniform
+  const int kl = ki < d.Sk ? ki : d.Sk - 1;
+  const float* vp = v + b * d.v_sb + head * d.v_sh + static_cast<long>(kl) * d.v_ss + 32 * h;
+  const float* qb = q + b * d.q_sb + head * d.q_sh;
+  const float* gb = go + b * go_sb + head * go_sh;
+  const long rows = (static_cast<long>(b) * d.H + head) * d.Sq;
+  // Addresses are a uniform base that moves by one tile + a 32-bit lane offset, here and below: a 64-bit pointer per
+  // lane and stream would cost the registers that keep the kernel at two waves per SIMD without scratch.
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  float* dsp = ds + (static_cast<long>(b) * d.H + head) * ds_rows(d.Sk) * ds_pitch(d.Sq) +
+               (4 * bc.blk + wave_u) * ds_pitch(d.Sq) * kTile;          // + 4 * lane
+  bf16x8 vs[3][4];                                         // planes of V[key][32 h + 8 s ..]: the B operand of dP
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+    split8<false>(*reinterpret_cast<const f32x4*>(vp + 8 * s), *reinterpret_cast<const f32x4*>(vp + 8 * s + 4), vs[0][s],
+                  vs[1][s], vs[2][s]);
+  f32x16 dk0 = {0}, dk1 = {0}, dv0 = {0}, dv1 = {0};
+  const int n_tiles = (d.Sq + kTile - 1) / kTile;
+  // per-query row constants: as in attn_bwd_dkv_kernel (wave 0 fetches them raw, a tile ahead)
+  const bool rc_wave = __builtin_amdgcn_readfirstlane(wave) == 0;
+  auto row_consts = [&](int q0, float& rl, float& rd) {
+    int qq = q0 + r;
+    qq = qq < d.Sq ? qq : d.Sq - 1;
+    rl = (lse + rows)[static_cast<unsigned>(qq)];
+    rd = (delta + rows)[static_cast<unsigned>(qq)];
+  };
+  auto publish_consts = [&](int q0, float rl, float rd) {
+    if (threadIdx.x < kTile) {
+      const bool ok = q0 + static_cast<int>(threadIdx.x) < d.Sq;
+      LDbuf[threadIdx.x] = ok ? -rl * kLog2e : -INFINITY;
+      LDbuf[kTile + threadIdx.x] = ok ? -rd : 0.0f;
+    }
+  };
+  // the score tile's staging role: as in attn_bwd_dkv_kernel
+  const long sc_tile_row = sc_pitch(d.Sk) * kTile;
+  const char* sptr = reinterpret_cast<const char*>(scores + (static_cast<long>(b) * d.H + head) * sc_rows(d.Sq) * sc_pitch(d.Sk) +
+                                                   static_cast<long>(4 * bc.blk) * kBlockFloats);      // + 16 * threadIdx.x
+  const unsigned sc_off = 16u * threadIdx.x;       // bytes
+  const int st_off = (threadIdx.x & 31) * kDsStride + 8 * (threadIdx.x >> 6) + 4 * ((threadIdx.x >> 5) & 1);
+  auto load_scores_next = [&]() {
+    DsRegs t;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      t.v[j] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(sptr + j * 4 * kBlockFloats + sc_off));
+    sptr += 4 * sc_tile_row;
+    return t;
+  };
+  auto store_scores = [&](const DsRegs& t) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(Sbuf + st_off + kTile * j) = t.v[j];
+  };
+  // Staging role of a thread, for Q and for dO alike: queries 2 qp, 2 qp + 1 with qp = tid / 16, dimensions 4 dq .. + 3
+  // with dq = tid % 16 -- one 16-byte load per query and operand, split once (split2 on the pair of queries), written
+  //   * to the transposed images (GTimg, QTimg) as the forward writes Vimg: one 32-bit pair per dimension and plane
+  //     (k-step qp / 8, lane half (qp / 2) % 2, elements j, j + 1 with j / 2 = 2 ((qp / 4) % 2) + qp % 2);
+  //   * for dO also to the row image Gimg: per query and plane the four dimensions as one 8-byte half (dq % 2) of the
+  //     16-byte slot of (k-step (dq / 2) % 4, lane half dq / 8, query).  Slot = 80 (3 s + plane) + 4 s + 33 h + query:
+  //     the rotation by 4 s + h (at most 13 slots, hence 80 per plane) spreads the 32 lanes of a write pass -- 2 queries
+  //     x 4 k-steps x 2 halves x 2 -- over all 64 banks, and a reading lane's slots stay 16 (lane + h) + an immediate,
+  //     consecutive over 16 lanes.
+  const int qp = threadIdx.x >> 4, dq = threadIdx.x & 15;
+  const int g_off = ((((dq >> 1) & 3) * 3) * 80 + 4 * ((dq >> 1) & 3) + 33 * (dq >> 3) + 2 * qp) * 16 + 8 * (dq & 1);
+  int t_off[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int slot = 32 * ((qp >> 1) & 1) + 4 * (dq & 7) + e;
+    t_off[e] = (((dq >> 3) * 2 + (qp >> 3)) * 3 * 64 + (slot ^ ((slot >> 3) & 3))) * 16 + 4 * (2 * ((qp >> 2) & 1) + (qp & 1));
+  }
+  // a thread's pieces of every tile: byte offsets from the tile's (uniform) base.  Only the sequence's last tile can
+  // have rows beyond Sq, which are clamped: its offsets are worked out when it comes, behind a uniform branch.
+  const int last_tile = (d.Sq - 1) / kTile;
+  const unsigned og = static_cast<unsigned>(2 * qp * go_ss + 4 * dq) * 4u, oq = static_cast<unsigned>(2 * qp * d.q_ss + 4 * dq) * 4u;
+  const unsigned go_row = static_cast<unsigned>(go_ss) * 4u, q_row = static_cast<unsigned>(d.q_ss) * 4u;
+  auto fetch = [&](int tile) {
+    X6BwdRegs t;
+    const char* gt = reinterpret_cast<const char*>(gb + static_cast<long>(tile) * kTile * go_ss);
+    const char* qt = reinterpret_cast<const char*>(qb + static_cast<long>(tile) * kTile * d.q_ss);
+    // (the empty asm statements keep the compiler from hoisting this arithmetic out of the loop into registers that
+    // live through it: one addition per operand and tile is cheaper than the four registers)
+    unsigned go_r = go_row, q_r = q_row;
+    asm volatile("" : "+s"(go_r), "+s"(q_r));
+    unsigned g0 = og, g1 = og + go_r, q0 = oq, q1 = oq + q_r;
+    if (tile == last_tile) {
+      int top = d.Sq - 1 - last_tile * kTile;                    // the last valid row of the tile
+      asm volatile("" : "+s"(top));
+      const unsigned r0 = 2 * qp < top ? 2 * qp : top, r1 = 2 * qp + 1 < top ? 2 * qp + 1 : top;
+      g0 = r0 * go_r + 16u * dq;
+      g1 = r1 * go_r + 16u * dq;
+      q0 = r0 * q_r + 16u * dq;
+      q1 = r1 * q_r + 16u * dq;
+    }
+    t.g[0] = *reinterpret_cast<const f32x4*>(gt + g0);
+    t.g[1] = *reinterpret_cast<const f32x4*>(gt + g1);
+    t.q[0] = *reinterpret_cast<const f32x4*>(qt + q0);
+    t.q[1] = *reinterpret_cast<const f32x4*>(qt + q1);
+    return t;
+  };
+  auto split = [&](const X6BwdRegs& t) {
+    X6BwdPlanes p;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      split2<false>(f32x2{t.g[0][e], t.g[1][e]}, p.g[e][0], p.g[e][1], p.g[e][2]);
+      split2<false>(f32x2{t.q[0][e], t.q[1][e]}, p.q[e][0], p.q[e][1], p.q[e][2]);
+      __builtin_amdgcn_sched_barrier(0);           // two splits' temporaries at a time, not eight (registers)
+    }
+    return p;
+  };
+  auto publish = [&](const X6BwdPlanes& p) {
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        *reinterpret_cast<bf16x2*>(GTimg + t_off[e] + pl * kX6Plane) = p.g[e][pl];
+        *reinterpret_cast<bf16x2*>(QTimg + t_off[e] + pl * kX6Plane) = p.q[e][pl];
+      }
+      // the row image: query 2 qp + t takes element t of every pair (v_perm_b32: bytes 1:0 or 3:2 of both sources)
+      unsigned w[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) w[e] = __builtin_bit_cast(unsigned, p.g[e][pl]);
+      typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+      *reinterpret_cast<u32x2*>(Gimg + g_off + pl * kX6RowPlane) =
+          u32x2{__builtin_amdgcn_perm(w[1], w[0], 0x05040100u), __builtin_amdgcn_perm(w[3], w[2], 0x05040100u)};
+      *reinterpret_cast<u32x2*>(Gimg + g_off + pl * kX6RowPlane + 16) =
+          u32x2{__builtin_amdgcn_perm(w[1], w[0], 0x07060302u), __builtin_amdgcn_perm(w[3], w[2], 0x07060302u)};
+    }
+  };
+  float rl = 0.0f, rd = 0.0f;                      // wave 0's prefetched row constants
+  {
+    const X6BwdRegs t = fetch(0);
+    if (rc_wave) row_consts(0, rl, rd);
+    store_scores(load_scores_next());
+    publish(split(t));
+    publish_consts(0, rl, rd);
+  }
+  __syncthreads();
+  const bf16x8* Gf = reinterpret_cast<const bf16x8*>(Gimg) + lane + h;
+  const int t_slot = lane ^ ((lane >> 3) & 3);
+  const bf16x8* GTf = reinterpret_cast<const bf16x8*>(GTimg) + t_slot;
+  const bf16x8* QTf = reinterpret_cast<const bf16x8*>(QTimg) + t_slot;
+  const float* Ls = LDbuf + 4 * h;
+  const float* Ds = LDbuf + kTile + 4 * h;
+  const float* Sc = Sbuf + 4 * h * kDsStride + wave * kTile + r;   // S[query acc_row(i, h)][this lane's key]
+  VQA_STAMP_DECL
+  VQA_STAMP_START();
+  // One tile.  The loop below runs it with `more` a constant: with the prefetches behind a run-time condition the
+  // compiler cannot tell that a tile's loads were waited for, and protects their registers with vmcnt waits that land
+  // behind the NEXT tile's score loads -- every tile would wait for HBM.
+  auto tile = [&](const int qt, const bool more) __attribute__((always_inline)) {
+    const int q0 = qt * kTile;
+    X6BwdRegs tn;
+    DsRegs ts;
+    if (more) {                                    // the score tile comes from HBM: in flight during the whole tile
+      ts = load_scores_next();
+      if (rc_wave) row_consts(q0 + kTile, rl, rd);
+    }
+    f32x16 dp, st;                                 // dP, then dS; P (live waves only)
+    if (active) {
+      __builtin_amdgcn_sched_barrier(0);
+      VQA_STAMP(0);                                // segment 0: the score prefetch's address work and issue
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {                // dP's chain starts from -delta of its query rows
+        const f32x4 nd = *reinterpret_cast<const f32x4*>(Ds + 8 * g);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) dp[4 * g + e] = nd[e];
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {                // dP = -delta + dO . V^T, small terms first per k-step
+        const bf16x8 g0 = Gf[(3 * s) * 80 + 4 * s], g1 = Gf[(3 * s + 1) * 80 + 4 * s], g2 = Gf[(3 * s + 2) * 80 + 4 * s];
+        dp = mfma_bf16(g2, vs[0][s], dp);
+        dp = mfma_bf16(g1, vs[1][s], dp);
+        dp = mfma_bf16(g0, vs[2][s], dp);
+        dp = mfma_bf16(g1, vs[0][s], dp);
+        dp = mfma_bf16(g0, vs[1][s], dp);
+        dp = mfma_bf16(g0, vs[0][s], dp);
+        if (s == 1) __builtin_amdgcn_sched_barrier(0);   // six fragments in flight, not twelve
+      }
+      VQA_STAMP(1);                                // segment 1: -delta and the dP chain's issue
+    }
+    // Q and dO, shared by the key blocks of the (batch, head), come from L2: fetched behind the dP chain, in flight
+    // during the other two products
+    if (more) tn = fetch(qt + 1);
+    if (active) {
+      __builtin_amdgcn_sched_barrier(0);
+      // P behind the chain, not ahead of it as in the fp32 kernel: its 16 registers are not live next to the chain's
+      // fragments and the V planes, and its LDS reads and exponentials run while the last MFMAs drain
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const f32x4 nl = *reinterpret_cast<const f32x4*>(Ls + 8 * g);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int i = 4 * g + e;
+          st[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(Sc[((i & 3) + 8 * (i >> 2)) * kDsStride], kLog2e, nl[e]));
+        }
+      }
+      VQA_STAMP(2);                                // segment 2: LDS reads of S, -LSE; 16 exponentials
+#pragma unroll
+      for (int i = 0; i < 16; ++i) dp[i] *= st[i];                                   // dS
+      VQA_STAMP(3);                                // segment 3: dS (waits for the chain's last MFMA)
+      // dV^T += dO^T . P: registers 8 s .. 8 s + 7 of P, split, are the B fragment of k-step s
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        bf16x8 p0, p1, p2;
+        split8<false>(f32x4{st[8 * s], st[8 * s + 1], st[8 * s + 2], st[8 * s + 3]},
+                      f32x4{st[8 * s + 4], st[8 * s + 5], st[8 * s + 6], st[8 * s + 7]}, p0, p1, p2);
+        const bf16x8 a0 = GTf[(3 * s) * 64], a1 = GTf[(3 * s + 1) * 64], a2 = GTf[(3 * s + 2) * 64];
+        const bf16x8 c0 = GTf[(3 * (2 + s)) * 64], c1 = GTf[(3 * (2 + s) + 1) * 64], c2 = GTf[(3 * (2 + s) + 2) * 64];
+        dv0 = mfma_bf16(a2, p0, dv0);
+        dv1 = mfma_bf16(c2, p0, dv1);
+        dv0 = mfma_bf16(a1, p1, dv0);
+        dv1 = mfma_bf16(c1, p1, dv1);
+        dv0 = mfma_bf16(a0, p2, dv0);
+        dv1 = mfma_bf16(c0, p2, dv1);
+        dv0 = mfma_bf16(a1, p0, dv0);
+        dv1 = mfma_bf16(c1, p0, dv1);
+        dv0 = mfma_bf16(a0, p1, dv0);
+        dv1 = mfma_bf16(c0, p1, dv1);
+        dv0 = mfma_bf16(a0, p0, dv0);
+        dv1 = mfma_bf16(c0, p0, dv1);
+        __builtin_amdgcn_sched_barrier(0);         // one k-step's six fragments in flight at a time
+      }
+      VQA_STAMP(4);                                // segment 4: the P split and the dV chains
+      // dK^T += Q^T . dS, likewise
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        bf16x8 s0, s1, s2;
+        split8<false>(f32x4{dp[8 * s], dp[8 * s + 1], dp[8 * s + 2], dp[8 * s + 3]},
+                      f32x4{dp[8 * s + 4], dp[8 * s + 5], dp[8 * s + 6], dp[8 * s + 7]}, s0, s1, s2);
+        const bf16x8 a0 = QTf[(3 * s) * 64], a1 = QTf[(3 * s + 1) * 64], a2 = QTf[(3 * s + 2) * 64];
+        const bf16x8 c0 = QTf[(3 * (2 + s)) * 64], c1 = QTf[(3 * (2 + s) + 1) * 64], c2 = QTf[(3 * (2 + s) + 2) * 64];
+        dk0 = mfma_bf16(a2, s0, dk0);
+        dk1 = mfma_bf16(c2, s0, dk1);
+        dk0 = mfma_bf16(a1, s1, dk0);
+        dk1 = mfma_bf16(c1, s1, dk1);
+        dk0 = mfma_bf16(a0, s2, dk0);
+        dk1 = mfma_bf16(c0, s2, dk1);
+        dk0 = mfma_bf16(a1, s0, dk0);
+        dk1 = mfma_bf16(c1, s0, dk1);
+        dk0 = mfma_bf16(a0, s1, dk0);
+        dk1 = mfma_bf16(c0, s1, dk1);
+        dk0 = mfma_bf16(a0, s0, dk0);
+        dk1 = mfma_bf16(c0, s0, dk1);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      VQA_STAMP(5);                                // segment 5: the dS split and the dK chains
+    }
+    // the next tile's planes, before the barrier: this wave's split runs while the others are still in their chains
+    X6BwdPlanes pn;
+    if (more) pn = split(tn);
+    __syncthreads();                               // every wave has read this tile's images, scores and constants
+    if (more) {
+      publish(pn);
+      store_scores(ts);
+      asm volatile("" : "+v"(rl), "+v"(rd));      // the raw values are first needed HERE (see attn_bwd_dkv_kernel)
+      publish_consts(q0 + kTile, rl, rd);
+    }
+    VQA_STAMP(6);                                  // segment 6: wait for the prefetched tile, split, barrier, publish
+    if (active && !VQA_ABLATE(1)) {                // dS^T, four consecutive queries per 16-byte store (as attn_bwd_dkv_kernel)
+      if (all_live) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(dsp + static_cast<long>(qt) * kBlockFloats + 256 * g) + (sc_off & 1023u)) =
+              f32x4{dp[4 * g], dp[4 * g + 1], dp[4 * g + 2], dp[4 * g + 3]};
+      } else {                                     // the wave that straddles Sk: zeros in the rows of keys beyond it
+        const bool live = ki < d.Sk;
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(dsp + static_cast<long>(qt) * kBlockFloats + 256 * g) + (sc_off & 1023u)) =
+              live ? f32x4{dp[4 * g], dp[4 * g + 1], dp[4 * g + 2], dp[4 * g + 3]} : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      }
+    }
+    __syncthreads();                               // the next tile is published
+    VQA_STAMP(7);                                  // segment 7: the dS^T stores' issue and the second barrier
+  };
+  for (int qt = 0; qt + 1 < n_tiles; ++qt) tile(qt, true);
+  tile(n_tiles - 1, false);
+  if (active) VQA_STAMP_FLUSH(1, n_tiles);
+  // the epilogue works its lane's key and dimensions out again from the thread id (the asm statement hides that they
+  // are the values above): nothing of the epilogue's then lives in a register through the loop
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  const int ke = bc.blk * 128 + (tid >> 6) * kTile + (tid & 31), he = (tid >> 5) & 1;
+  if (ke < d.Sk) {
+    float* pk = dk + b * dk_sb + head * dk_sh + static_cast<long>(ke) * dk_ss;
+    float* pv = dv + b * dv_sb + head * dv_sh + static_cast<long>(ke) * dv_ss;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int dim = 8 * g + 4 * he;
+      *reinterpret_cast<f32x4*>(pk + dim) =
+          f32x4{dk0[4 * g] * d.scale, dk0[4 * g + 1] * d.scale, dk0[4 * g + 2] * d.scale, dk0[4 * g + 3] * d.scale};
+      *reinterpret_cast<f32x4*>(pk + 32 + dim) =
+          f32x4{dk1[4 * g] * d.scale, dk1[4 * g + 1] * d.scale, dk1[4 * g + 2] * d.scale, dk1[4 * g + 3] * d.scale};
+      *reinterpret_cast<f32x4*>(pv + dim) = f32x4{dv0[4 * g], dv0[4 * g + 1], dv0[4 * g + 2], dv0[4 * g + 3]};
+      *reinterpret_cast<f32x4*>(pv + 32 + dim) = f32x4{dv1[4 * g], dv1[4 * g + 1], dv1[4 * g + 2], dv1[4 * g + 3]};
+    }
+  }
+}
+
 }  // namespace vqa
 
 using namespace vqa;
@@ -1373,16 +1728,15 @@ long vqa_attn_bwd_ws_floats(int B, int H, int Sq, int Sk) {
   return static_cast<long>(B) * H * ds_rows(Sk) * ds_pitch(Sq);
 }
 
-/* grad_strides: 12 longs = {go_sb, go_ss, go_sh, dq_sb, dq_ss, dq_sh, dk_sb, dk_ss, dk_sh, dv_sb, dv_ss, dv_sh} */
-int vqa_attn_bwd(const float* q, const float* k, const float* v, const float* bias, const float* o, const float* go,
-                 const float* lse, const float* scores, float* delta, float* dq, float* dk, float* dv, float* ds_ws, int B,
-                 int H, int Sq, int Sk, const long* strides, const long* bias_strides, const long* grad_strides,
-                 float scale, int nsplit, float* split_ws, vqa_stream_t stream) {
-  clear_stale_error();
+// The backward entries' arguments -> AttnDims, checked (everything but the loop split).
+static int bwd_dims(const float* q, const float* k, const float* v, const float* bias, const float* o, const float* go,
+                    const float* lse, const float* scores, const float* delta, const float* dq, const float* dk,
+                    const float* dv, const float* ds_ws, int B, int H, int Sq, int Sk, const long* strides,
+                    const long* bias_strides, const long* grad_strides, float scale, AttnDims& d) {
   if (!strides || !grad_strides || !o || !go || !lse || !delta || !dq || !dk || !dv || (bias && !bias_strides))
     return VQA_ERR_NULL;
-  AttnDims d{B, H, Sq, Sk, strides[0], strides[1], strides[2], strides[3], strides[4], strides[5], strides[6],
-             strides[7], strides[8], strides[9], strides[10], strides[11], 0, 0, 0, scale};
+  d = AttnDims{B, H, Sq, Sk, strides[0], strides[1], strides[2], strides[3], strides[4], strides[5], strides[6],
+               strides[7], strides[8], strides[9], strides[10], strides[11], 0, 0, 0, scale};
   if (bias) {
     d.bias_sb = bias_strides[0];
     d.bias_sh = bias_strides[1];
@@ -1402,6 +1756,19 @@ int vqa_attn_bwd(const float* q, const float* k, const float* v, const float* bi
   // the dS path addresses a (batch, head) slab of either workspace with 32-bit lane offsets
   if (ds_ws && (ds_rows(Sk) * ds_pitch(Sq) >= 2147483647L || sc_rows(Sq) * sc_pitch(Sk) >= 2147483647L))
     return VQA_ERR_SHAPE;
+  return VQA_OK;
+}
+
+/* grad_strides: 12 longs = {go_sb, go_ss, go_sh, dq_sb, dq_ss, dq_sh, dk_sb, dk_ss, dk_sh, dv_sb, dv_ss, dv_sh} */
+int vqa_attn_bwd(const float* q, const float* k, const float* v, const float* bias, const float* o, const float* go,
+                 const float* lse, const float* scores, float* delta, float* dq, float* dk, float* dv, float* ds_ws, int B,
+                 int H, int Sq, int Sk, const long* strides, const long* bias_strides, const long* grad_strides,
+                 float scale, int nsplit, float* split_ws, vqa_stream_t stream) {
+  clear_stale_error();
+  AttnDims d;
+  const int rc = bwd_dims(q, k, v, bias, o, go, lse, scores, delta, dq, dk, dv, ds_ws, B, H, Sq, Sk, strides, bias_strides,
+                          grad_strides, scale, d);
+  if (rc != VQA_OK) return rc;
   {
     const int tq = (Sq + kTile - 1) / kTile, tk = (Sk + kTile - 1) / kTile;
     const long big = (((Sq > Sk ? Sq : Sk) + 127L) / 128) * H * B;
@@ -1470,6 +1837,33 @@ int vqa_attn_bwd(const float* q, const float* k, const float* v, const float* bi
                                                                     g[8], g[9], g[10], g[11], g[0], g[1], g[2], nullptr,
                                                                     nullptr, sp);
   }
+  return launch_status();
+}
+
+int vqa_attn_bwd_x6(const float* q, const float* k, const float* v, const float* bias, const float* o, const float* go,
+                    const float* lse, const float* scores, float* delta, float* dq, float* dk, float* dv, float* ds_ws,
+                    int B, int H, int Sq, int Sk, const long* strides, const long* bias_strides, const long* grad_strides,
+                    float scale, int nsplit, float* split_ws, vqa_stream_t stream) {
+  clear_stale_error();
+  (void)split_ws;
+  if (!scores || !ds_ws || nsplit != 1) return VQA_ERR_SHAPE;      // every other form is fp32 only: vqa_attn_bwd
+  AttnDims d;
+  const int rc = bwd_dims(q, k, v, bias, o, go, lse, scores, delta, dq, dk, dv, ds_ws, B, H, Sq, Sk, strides, bias_strides,
+                          grad_strides, scale, d);
+  if (rc != VQA_OK) return rc;
+  // the dK / dV kernel addresses a tile of q and of go with 32-bit byte offsets from the tile's base
+  if (d.q_ss < 0 || d.q_ss >= (1L << 24) || grad_strides[1] < 0 || grad_strides[1] >= (1L << 24)) return VQA_ERR_SHAPE;
+  if (B == 0) return VQA_OK;
+  const long* g = grad_strides;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const long n_rows = static_cast<long>(B) * H * Sq;
+  const long blocks = (n_rows + kBlock / 16 - 1) / (kBlock / 16);
+  if (blocks > 2147483647L) return VQA_ERR_SHAPE;
+  const dim3 gq(static_cast<unsigned>(((Sq + 127) / 128) * H * B)), gk(static_cast<unsigned>(((Sk + 127) / 128) * H * B));
+  attn_delta_kernel<<<dim3(static_cast<unsigned>(blocks)), kBlock, 0, st>>>(o, go, delta, d, g[0], g[1], g[2]);
+  attn_bwd_dkv_x6_kernel<<<gk, kBlock, 0, st>>>(q, v, go, lse, delta, dk, dv, d, g[6], g[7], g[8], g[9], g[10], g[11], g[0],
+                                                g[1], g[2], ds_ws, scores);
+  attn_bwd_dq_staged_kernel<false><<<gq, kBlock, 0, st>>>(k, ds_ws, dq, d, g[3], g[4], g[5], SplitArgs{1, nullptr});
   return launch_status();
 }
 
