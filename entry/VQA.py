@@ -64,6 +64,12 @@ def parse(argv=None):
                     help="SI-FGSM number of scale copies 1, 1/2, ... of the image attack (Lin et al. 2020; 1..8); absent: off")
     ap.add_argument("--nesterov", action="store_true",
                     help="NI-FGSM: take gradients at the Nesterov look-ahead point (needs --decay_factor)")
+    ap.add_argument("--vt_neighbors", default=None, type=int,
+                    help="variance tuning (VMI / VNI-FGSM, Wang & He 2021): neighbours per gradient evaluation (1..64); "
+                         "absent: off")
+    ap.add_argument("--vt_beta", default=1.5, type=float,
+                    help="variance tuning: neighbours are drawn from U[-vt_beta * eps, vt_beta * eps)")
+    ap.add_argument("--vt_seed", default=None, type=int, help="variance tuning: seed of the device-side draws; absent: unseeded")
     ap.add_argument("--mlm_checkpoint", default="", help="BertForMaskedLM state dict -> candidate proposer (adv_attack.py:110)")
     ap.add_argument("--answer_list", default=None,
                     help="ALBEF answer_list json (configs: answer_list): the victim ranks it and acc_vqa compares answer "
@@ -138,7 +144,8 @@ def main():
                     config=AttackConfig(sim_threshold=args.sim_threshold, decay_factor=args.decay_factor,
                                         ti_kernel=args.ti_kernel, diversity_prob=args.diversity_prob,
                                         di_shrink=args.di_shrink, di_seed=args.di_seed, si_copies=args.si_copies,
-                                        nesterov=args.nesterov),
+                                        nesterov=args.nesterov, vt_neighbors=args.vt_neighbors, vt_beta=args.vt_beta,
+                                        vt_seed=args.vt_seed),
                     scoring=scoring)
     finish(rank, world, res, os.path.join(args.output_dir, "adv_txt.json") if args.output_dir else None,
            os.path.join(args.output_dir, "adv_txt_dict_albef.txt") if args.output_dir and scoring else None)

@@ -300,6 +300,62 @@ int vqa_linf_si_step(const float* x, const float* const* grads_host, const float
                      const float* x0, float* out, size_t n, float eps_iter, float eps, float cmin, float cmax,
                      unsigned mode, int* flag, vqa_stream_t stream);
 
+/* ---------------------------------------------------------------- variance tuning (VMI / VNI-FGSM, Wang & He 2021)
+ * The reference tree has it in no framework; this definition is the contract.  Let G(p) be the image gradient of one
+ * evaluation at p (after the SI combination and the DI adjoint, before TI smoothing).  Evaluation t at point p steps
+ * along  ghat = G(p) + v  and then sets  v <- w * (G(p + r_0) + G(p + r_1) + ... + G(p + r_{N-1})) - G(p),
+ * w = fp32(1) / fp32(N), the sum in ascending i starting from G(p + r_0) (not from +0), v = 0 before the first
+ * evaluation; r_i ~ U[-bound, bound) per element, bound = fp32(beta * eps), neighbours unclipped as in the authors'
+ * code.  All in fp32 with one rounding per operation (no contraction).
+ *
+ * The random numbers are Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85):
+ *   key     = (seed & 0xffffffff, seed >> 32)                of a 64-bit seed,
+ *   counter = (j & 0xffffffff, j >> 32, i, t),               j = block_offset + e / 4 for flat element index e,
+ *                                                            i the neighbour index, t the evaluation index,
+ * and output word e % 4 belongs to element e:
+ *   u = float(word >> 8) * 2^-24;  r = (u * 2 - 1) * bound  (only the last product rounds);  out = base + r.
+ * An element's value depends on (seed, t, i, e, block_offset) alone -- not on the vector or scalar path, the grid,
+ * the unroll or how the neighbours are grouped into launches.  Known answers (counter | key | output):
+ *   0 0 0 0 | 0 0 | 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *   ffffffff x 4 | ffffffff x 2 | 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *   243f6a88 85a308d3 13198a2e 03707344 | a4093822 299f31d0 | d16cfe09 94fdcceb 5001e420 24126ea1
+ *
+ * Capture-safe like the rest: no allocation, no copy, no sync; gradient pointer lists are HOST arrays that travel by
+ * value in the kernel arguments (as for SI); seed and t are read from DEVICE memory, so that a captured launch sees
+ * whatever the row holds at each replay.  16-byte accesses when n % 4 == 0 (and copy_stride % 4 == 0) and every pointer
+ * is 16-byte aligned.  Return codes, all before the first HIP call: a NULL required pointer, a NULL entry of
+ * grads_host, or VQA_CHECK_RANGE without flag, VQA_ERR_NULL; a count outside 1..VQA_VT_MAX_CHUNK, first < 0,
+ * copy_stride < n, or a forbidden overlap or alias, VQA_ERR_SHAPE; a pointer not 4-byte aligned VQA_ERR_ALIGN; n == 0
+ * VQA_OK, no launch.
+ */
+#define VQA_VT_MAX_CHUNK 8
+int vqa_vt_max_chunk(void);
+
+/* Neighbours first .. first + count - 1 of one evaluation: out[c * copy_stride + e] = base[e] + r_{first + c}[e], with
+ * base = x for m == NULL, else x + lookahead * m (multiply, add: the Nesterov point), and r as above.  key_dev: a DEVICE
+ * row of three uint32 (seed_lo, seed_hi, t).  One launch reads x (and m) once: 4 (+ 4) + 4 * count B/element.
+ * copy_stride >= n; out must not overlap x, m or the key row. */
+int vqa_vt_neighbors(const float* x, const float* m, float* out, size_t n, size_t copy_stride, int count, int first,
+                     unsigned long long block_offset, float bound, float lookahead, const unsigned* key_dev,
+                     vqa_stream_t stream);
+
+/* sum[e] = acc, acc = init ? g_0[e] : sum[e] + g_0[e], then acc = acc + g_i[e] for i = 1 .. count - 1 ascending:
+ * calling it with 8 pointers once or with 1 pointer eight times gives the same bits.  grads_host is a HOST array of
+ * `count` DEVICE pointers.  4 * count + 4 (+ 4) B/element.  sum may alias no gradient. */
+int vqa_vt_accumulate(const float* const* grads_host, int count, float* sum, size_t n, int init, vqa_stream_t stream);
+
+/* ghat[e] = g[e] + v[e];  v[e] = w * vsum[e] - g[e]  (multiply, subtract), the old v in the first, 20 B/element.
+ * ghat may be exactly g; v is updated in place; no other overlap among g, vsum, v, ghat. */
+int vqa_vt_tune(const float* g, const float* vsum, float* v, float* ghat, size_t n, float w, vqa_stream_t stream);
+
+/* The tune step above and the L-infinity update in ONE pass: out = vqa_linf_step(x, ghat, x0), or, for x0 == NULL,
+ * out = vqa_linf_fgm(x, ghat) -- bit for bit what vqa_vt_tune followed by that launch gives; ghat never goes to memory.
+ * 28 B/element (24 without x0) against 20 + 16 for the two launches.  `out` may be exactly `x` (in place) and must not
+ * otherwise overlap x, x0, g, vsum or v.  mode / flag as in vqa_linf_step. */
+int vqa_linf_vt_step(const float* x, const float* g, const float* vsum, float* v, const float* x0, float* out, size_t n,
+                     float w, float eps_iter, float eps, float cmin, float cmax, unsigned mode, int* flag,
+                     vqa_stream_t stream);
+
 /* ---------------------------------------------------------------- cross-modal loss reduction
  * Rows of D contiguous floats, addressed as row(o, i) = base + o*stride0 + i*stride1 (strides in ELEMENTS) for
  * o < rows0, i < rows1 -- this is how the reference's `out[k][:, :feat_len, :]` truncation views are consumed

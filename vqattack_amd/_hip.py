@@ -28,6 +28,7 @@ _f = ctypes.c_float
 _i = ctypes.c_int
 _u = ctypes.c_uint
 _l = ctypes.c_long
+_ull = ctypes.c_ulonglong
 _p = ctypes.c_void_p
 
 # name -> (restype, argtypes); must list every symbol of include/vqattack_hip.h (tests/test_abi.py checks it)
@@ -60,6 +61,11 @@ SIGNATURES = {
     "vqa_si_copies": (_i, [_p, _p, _p, _sz, _sz, _p, _i, _f, _p]),
     "vqa_si_combine": (_i, [_p, _p, _i, _p, _sz, _p]),
     "vqa_linf_si_step": (_i, [_p, _p, _p, _i, _p, _p, _sz, _f, _f, _f, _f, _u, _p, _p]),
+    "vqa_vt_max_chunk": (_i, []),
+    "vqa_vt_neighbors": (_i, [_p, _p, _p, _sz, _sz, _i, _i, _ull, _f, _f, _p, _p]),
+    "vqa_vt_accumulate": (_i, [_p, _i, _p, _sz, _i, _p]),
+    "vqa_vt_tune": (_i, [_p, _p, _p, _p, _sz, _f, _p]),
+    "vqa_linf_vt_step": (_i, [_p, _p, _p, _p, _p, _p, _sz, _f, _f, _f, _f, _f, _u, _p, _p]),
     "vqa_neg_cos_partials": (_i, []),
     "vqa_neg_cos_rows": (_i, [_p, _p, _p, _p, _p, _l, _l, _l, _i, _l, _l, _l, _l, _l, _l, _f, _f, _p, _i, _p]),
     "vqa_neg_cos_max_layers": (_i, []),

@@ -51,6 +51,9 @@ class AttackConfig:
     di_seed: Optional[int] = None          # DI: seed of the np.random.RandomState each attack call draws its rows from
     si_copies: object = None               # not None: SI-FGSM, every gradient is the weighted sum over scaled copies (1..8 or scales)
     nesterov: bool = False                 # NI-FGSM: gradients are taken at adv + eps_iter * decay_factor * momentum
+    vt_neighbors: Optional[int] = None     # not None: variance tuning (VMI / VNI-FGSM) with this many neighbours per evaluation (1..64)
+    vt_beta: float = 1.5                   # VT: neighbours are drawn from U[-vt_beta * eps, vt_beta * eps) (the paper's 1.5)
+    vt_seed: Optional[int] = None          # VT: 64-bit seed of the device-side draws (None: one seed from np.random per call)
 
     def __post_init__(self):
         attacks._validate_decay(self.decay_factor)
@@ -72,6 +75,9 @@ class AttackConfig:
         if self.si_copies is not None and self.patch_layout:
             # like the other three keys: the patch-major path is not exercised with any transfer method
             raise ValueError("si_copies and patch_layout=True cannot be combined")
+        attacks._validate_vt(self.vt_neighbors, self.vt_beta, self.vt_seed)
+        if self.vt_neighbors is not None and self.patch_layout:
+            raise ValueError("vt_neighbors and patch_layout=True cannot be combined")
 
 
 @dataclass
@@ -154,7 +160,8 @@ class BatchedVQAttack:
         common = dict(clip_min=c.clip_min, clip_max=c.clip_max, time=time, ori_x=clean,
                       sanity_checks=c.sanity_checks, init_eta=init_eta, decay_factor=c.decay_factor, momentum=momentum,
                       ti_kernel=c.ti_kernel, diversity_prob=c.diversity_prob, di_shrink=c.di_shrink,
-                      di_rng=self._di_draws, si_copies=c.si_copies, nesterov=c.nesterov)
+                      di_rng=self._di_draws, si_copies=c.si_copies, nesterov=c.nesterov, vt_neighbors=c.vt_neighbors,
+                      vt_beta=c.vt_beta, vt_seed=c.vt_seed)
         a = self.adapters
         if not dual:
             return self.pgd(a.pgd_attack, adv, c.eps, c.eps_iter, steps, c.norm, y=self._y_feature(targets), ls=1,
@@ -267,7 +274,8 @@ class BatchedVQAttack:
                                                  attack_mask=positions, sanity_checks=c.sanity_checks,
                                                  decay_factor=c.decay_factor, momentum=mom, ti_kernel=c.ti_kernel,
                                                  diversity_prob=c.diversity_prob, di_shrink=c.di_shrink,
-                                                 di_rng=self._di_draws, si_copies=c.si_copies, nesterov=c.nesterov)
+                                                 di_rng=self._di_draws, si_copies=c.si_copies, nesterov=c.nesterov,
+                                                 vt_neighbors=c.vt_neighbors, vt_beta=c.vt_beta, vt_seed=c.vt_seed)
                 res.gradient_steps += 1
                 if plan is not None:
                     scores = text_update.score_plan(self.tables, e_ori, text_grad, plan)
@@ -347,6 +355,9 @@ class BatchedVQAttack:
         c, a = self.cfg, self.adapters
         if c.norm != np.inf:
             raise ValueError("attack_mixed implements the L-inf attack")
+        if c.vt_neighbors is not None:
+            # the per-run updates of the mixed schedule carry no variance state: use attack_batch on schedule-pure buckets
+            raise ValueError("vt_neighbors is not supported by attack_mixed (the mixed-schedule driver)")
         dev, b, text_len = images.device, images.shape[0], text_ids.shape[1]
         images, init_eta, restore = self._enter_layout(images, init_eta)
         n_words = [int(w) for w in attackable.sum(dim=1).tolist()]

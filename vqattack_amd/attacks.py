@@ -158,6 +158,25 @@ def _validate_si(si_copies, nesterov=False, decay_factor=None):
     return scales, bool(nesterov)
 
 
+def _validate_vt(vt_neighbors, vt_beta=1.5, vt_seed=None):
+    """None (variance tuning off; the other two keys are then ignored) or ``(n, beta, seed)``: ``vt_neighbors`` an int N
+    in 1..64, ``vt_beta`` a finite number > 0 (the neighbourhood is ``U[-beta * eps, beta * eps)``), ``vt_seed`` None (one
+    seed is drawn from ``np.random`` when the state is built) or an int in ``[0, 2^64)``.  Raised before any tensor is
+    looked at, like the other arguments."""
+    if vt_neighbors is None:
+        return None
+    if isinstance(vt_neighbors, (bool, np.bool_)) or not isinstance(vt_neighbors, (int, np.integer)) or \
+            not 1 <= int(vt_neighbors) <= ops.VT_MAX_NEIGHBORS:
+        raise ValueError("vt_neighbors must be None or an int in 1..{}, got {!r}".format(ops.VT_MAX_NEIGHBORS, vt_neighbors))
+    if isinstance(vt_beta, (bool, np.bool_)) or not isinstance(vt_beta, (int, float, np.integer, np.floating)) or \
+            not 0.0 < float(vt_beta) < float("inf"):        # False for NaN too
+        raise ValueError("vt_beta must be a finite number greater than 0, got {!r}".format(vt_beta))
+    if vt_seed is not None and (isinstance(vt_seed, (bool, np.bool_)) or not isinstance(vt_seed, (int, np.integer))
+                                or not 0 <= int(vt_seed) < 1 << 64):
+        raise ValueError("vt_seed must be None or an int in [0, 2^64), got {!r}".format(vt_seed))
+    return int(vt_neighbors), float(vt_beta), (None if vt_seed is None else int(vt_seed))
+
+
 def _two_sided(clip_min, clip_max):
     if (clip_min is not None or clip_max is not None) and (clip_min is None or clip_max is None):
         raise ValueError("One of clip_min and clip_max is None but we don't currently support one-sided clipping")
@@ -464,14 +483,15 @@ class _Diversity:
         return ops.di_adjoint(gd, self.geom, out=self.grad)
 
 
-def _diversity(spec, like, n_evals, norm, decay, taps):
-    """None without DI; the adjoint scratch is needed by every update but the plain L-inf one."""
+def _diversity(spec, like, n_evals, norm, decay, taps, vt=False):
+    """None without DI; the adjoint scratch is needed by every update but the plain L-inf one (and by variance tuning,
+    whose state lives in x space)."""
     if spec is None:
         return None
     if like.dim() != 4:
         raise ValueError("diversity_prob needs a (B, C, H, W) image: the transform runs over its (H, W) planes, got shape "
                          "{}".format(tuple(like.shape)))
-    return _Diversity(spec, like, n_evals, scratch=decay is not None or taps is not None or norm != np.inf)
+    return _Diversity(spec, like, n_evals, scratch=decay is not None or taps is not None or norm != np.inf or vt)
 
 
 class _Scales:
@@ -491,33 +511,81 @@ class _Scales:
         self.ghat = torch.empty_like(like, memory_format=torch.contiguous_format) if scratch else None
         self.slot = _LossSlot(torch.zeros(1, dtype=torch.float32, device=like.device), 0)
 
-    def copies(self, adv):
-        return ops.si_copies(adv, self.scales, m=None if self.mom is None else self.mom.m, lookahead=self.lookahead,
-                             out=self.images)
+    def copies(self, adv, ahead=True):
+        """``ahead=False``: ``adv`` already is the point the copies are taken at (a variance-tuning neighbour)."""
+        if not ahead or self.mom is None:
+            return ops.si_copies(adv, self.scales, out=self.images)
+        return ops.si_copies(adv, self.scales, m=self.mom.m, lookahead=self.lookahead, out=self.images)
 
     def combine(self, grads):
         return ops.si_combine(grads, self.weights, out=self.ghat)
 
 
-def _scales(spec, like, eps_iter, norm, mom, ti, di):
-    """None without SI / NI; the combined-gradient scratch is needed by every update but the plain L-inf one."""
+def _scales(spec, like, eps_iter, norm, mom, ti, di, vt=False):
+    """None without SI / NI; the combined-gradient scratch is needed by every update but the plain L-inf one (and by
+    variance tuning)."""
     if spec is None:
         return None
     return _Scales(spec, like, eps_iter, mom, di,
-                   scratch=mom is not None or ti is not None or di is not None or norm != np.inf)
+                   scratch=mom is not None or ti is not None or di is not None or norm != np.inf or vt)
 
 
-def _evaluate(adv, si, di, call, advance=True):
+class _Variance:
+    """The variance-tuning (VMI / VNI-FGSM) state of one operator call, all of it allocated before the loop so that a
+    captured iteration finds it at static addresses: one variance tensor ``v`` per evaluation kind (the dual loop's
+    feature and MLM evaluations each tune their own), the running sum of the neighbours' gradients, the centre's
+    x-space gradient / the tuned gradient, a chunk of ``min(N, 8)`` neighbour images, the key table of all the call's
+    evaluations (row ``t`` = seed and ``t``, one upload), one static key row for a captured iteration and one word for
+    the neighbours' losses."""
+
+    def __init__(self, spec, like, eps, n_evals, kinds=1):
+        n, beta, seed = spec
+        if seed is None:
+            seed = (int(np.random.randint(0, 1 << 32)) << 32) | int(np.random.randint(0, 1 << 32))
+        self.n, self.seed = n, seed
+        self.w = float(np.float32(1.0) / np.float32(n))
+        self.bound = float(np.float32(beta * float(eps)))
+        self.v = [torch.zeros_like(like, memory_format=torch.contiguous_format) for _ in range(kinds)]
+        self.vsum = torch.empty_like(like, memory_format=torch.contiguous_format)
+        self.ghat = torch.empty_like(like, memory_format=torch.contiguous_format)
+        self.chunk = torch.empty((min(n, ops.VT_MAX_CHUNK),) + tuple(like.shape), dtype=torch.float32, device=like.device)
+        self.table = ops.vt_key_table(seed, n_evals, like.device)
+        self.row = torch.empty(3, dtype=torch.uint32, device=like.device)
+        self.slot = _LossSlot(torch.zeros(1, dtype=torch.float32, device=like.device), 0)
+        self.key, self.t, self.kind, self.plain = None, 0, 0, True
+
+    def use(self, t, static=False):
+        """Make evaluation ``t``'s key current: in place in the table, or (``static``) copied into the static row."""
+        if static:
+            self.row.copy_(self.table[t])
+        self.key = self.row if static else self.table[t]
+
+    def tune(self, grad):
+        return ops.vt_tune(grad, self.vsum, self.v[self.kind], self.w, out=self.ghat)
+
+
+def _variance(spec, like, eps, n_evals, kinds=1):
+    return None if spec is None else _Variance(spec, like, eps, n_evals, kinds)
+
+
+def _scratch_slot(si, vt):
+    """The word that takes the losses nobody reports: those of the scale copies after the first and of the neighbours."""
+    return si.slot if si is not None else (vt.slot if vt is not None else None)
+
+
+def _evaluate(adv, si, di, call, advance=True, ahead=True):
     """One gradient evaluation at ``adv``.  ``call(leaf, first)`` runs the white box and the loss on one leaf and leaves
     the gradient in ``leaf.grad``.  Without ``si``: one call on ``adv`` (or its DI transform).  With it: the copies in one
     launch, then one call per copy in ascending order, each on a leaf of its own; all copies of the evaluation share its
     DI rows, so the adjoint is linear over them and the combination may precede it.
+    ``ahead=False``: no Nesterov look-ahead in front of the copies (``adv`` is a variance-tuning neighbour, drawn around
+    the look-ahead point already).
     Returns ``(first leaf, gradient)``; with ``si`` the gradient is the list of the copies' gradients."""
     if si is None:
         leaf = adv.detach().requires_grad_(True) if di is None else di.leaf(adv, advance=advance)
         call(leaf, True)
         return leaf, _grad_of(leaf)
-    images = si.copies(adv)
+    images = si.copies(adv, ahead=ahead)
     first, grads = None, []
     for i in range(images.shape[0]):
         if di is None:
@@ -531,8 +599,52 @@ def _evaluate(adv, si, di, call, advance=True):
     return first, grads
 
 
+def _x_gradient(grad, si, di, out=None):
+    """``G`` of variance tuning: what ``_evaluate`` returned, taken to x space -- the SI combination, then the DI adjoint,
+    each into its own scratch (the last one into ``out`` when given); without either the leaf's gradient itself."""
+    if si is not None:
+        grad = ops.si_combine(grad, si.weights, out=si.ghat if (out is None or di is not None) else out)
+    if di is not None:
+        grad = ops.di_adjoint(grad, di.geom, out=di.grad if out is None else out)
+    return grad
+
+
+def _evaluate_vt(adv, si, di, vt, call, kind=0, advance=True):
+    """One variance-tuned gradient evaluation at ``adv``: the centre through ``_evaluate``, then the ``vt.n`` neighbours
+    ``p + r_i`` (``p`` the look-ahead point with Nesterov) in chunks of at most 8 images per launch through the same
+    ``_evaluate``, every one with the centre's DI rows and ``call(leaf, False)`` (their losses go to a scratch word).
+    Without SI / DI up to 8 leaf gradients are summed per launch; with either each neighbour's gradient is combined /
+    adjoint-ed into its scratch and summed one at a time -- the same bits.  Leaves ``sum_i G(p + r_i)`` in ``vt.vsum``
+    and returns ``(first leaf, G(p))``, ``G(p)`` in x space."""
+    if advance:
+        vt.use(vt.t)
+        vt.t += 1
+    vt.kind, vt.plain = kind, si is None and di is None
+    first, grad = _evaluate(adv, si, di, call, advance=advance)
+    g = _x_gradient(grad, si, di, out=vt.ghat)
+    m, lookahead = (si.mom.m, si.lookahead) if si is not None and si.mom is not None else (None, 0.0)
+
+    def other(leaf, _):
+        call(leaf, False)
+
+    for start in range(0, vt.n, ops.VT_MAX_CHUNK):
+        count = min(ops.VT_MAX_CHUNK, vt.n - start)
+        images = ops.vt_neighbors(adv, vt.key, count, vt.bound, first=start, m=m, lookahead=lookahead,
+                                  out=vt.chunk[:count])
+        grads = []
+        for c in range(count):
+            gn = _evaluate(images[c], si, di, other, advance=False, ahead=False)[1]
+            if vt.plain:
+                grads.append(gn)
+            else:
+                ops.vt_accumulate([_x_gradient(gn, si, di)], vt.vsum, init=start + c == 0)
+        if grads:
+            ops.vt_accumulate(grads, vt.vsum, init=start == 0)
+    return first, g
+
+
 def _fgm_update(x, grad, eps, norm, clip_min, clip_max, flag=None, out=None, check_range=True, mom=None, ti=None,
-                di=None, si=None):
+                di=None, si=None, vt=None):
     """``flag``: range violations of ``x`` (``check_range``) and, for the L2 / L1 updates, the degenerate-gradient bit
     that stands for the self-check asserts of the reference's ``optimize_linear`` (utils.py:101-104, :110-116).
     ``mom``: accumulate ``grad`` into the momentum first and step along the momentum instead.
@@ -541,7 +653,14 @@ def _fgm_update(x, grad, eps, norm, clip_min, clip_max, flag=None, out=None, che
     ``di``: ``grad`` is the gradient at the TRANSFORMED image (DI-FGSM): the transform's adjoint takes it back to ``x``
     first, in the same launch for the plain L-inf update, in front of smoothing / momentum / L2 otherwise.
     ``si``: ``grad`` is the LIST of the scale copies' gradients (SI-NI-FGSM): their weighted sum comes first of all, in
-    the same launch for the plain L-inf update, into a scratch in front of the rest of the chain otherwise."""
+    the same launch for the plain L-inf update, into a scratch in front of the rest of the chain otherwise.
+    ``vt``: ``grad`` is ``G(p)`` of ``_evaluate_vt``, in x space already (``si`` / ``di`` are done with): the tune step
+    comes first, in the same launch for the plain L-inf update, in front of smoothing / momentum / L2 otherwise."""
+    if vt is not None:
+        if vt.plain and ti is None and mom is None and norm == np.inf:
+            return ops.linf_vt_step(x, grad, vt.vsum, vt.v[vt.kind], None, vt.w, eps, 0.0, clip_min, clip_max,
+                                    flag=flag if check_range else None, out=out)
+        grad, si, di = vt.tune(grad), None, None
     if si is not None:
         if di is None and ti is None and mom is None and norm == np.inf:
             return ops.linf_si_step(x, grad, None, si.weights, eps, 0.0, clip_min, clip_max,
@@ -570,7 +689,11 @@ def _fgm_update(x, grad, eps, norm, clip_min, clip_max, flag=None, out=None, che
 
 
 def _fgm_then_project(x, grad, x0, eps_iter, eps, norm, clip_min, clip_max, out, flag=None, mom=None, ti=None,
-                      di=None, si=None):
+                      di=None, si=None, vt=None):
+    if vt is not None:
+        if vt.plain and ti is None and mom is None and norm == np.inf:
+            return ops.linf_vt_step(x, grad, vt.vsum, vt.v[vt.kind], x0, vt.w, eps_iter, eps, clip_min, clip_max, out=out)
+        grad, si, di = vt.tune(grad), None, None
     if si is not None:
         if di is None and ti is None and mom is None and norm == np.inf:
             return ops.linf_si_step(x, grad, x0, si.weights, eps_iter, eps, clip_min, clip_max, out=out)
@@ -729,7 +852,7 @@ def _finish(flag, eps, eps_iter, norm, clip_min, clip_max, sanity_checks):
 
 
 def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, clip_min, clip_max, nb_iter, loss_buf,
-                       mom=None, ti=None, di=None, si=None):
+                       mom=None, ti=None, di=None, si=None, vt=None):
     """``nb_iter`` feature-loss L-inf iterations with iterations 1.. replayed from ONE captured hipGraph.
 
     For the launch-bound regime (the reference's own batch 1: ~10^3 kernels of a few microseconds per iteration):
@@ -748,16 +871,23 @@ def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, cl
     ``si``: the copies launch, one model call per copy and the combining update are captured; the copies and the scratch
     were allocated before capture, and the gradients' addresses, which travel by value in the kernel arguments, are the
     graph's own and the same at every replay.
+    ``vt``: the neighbour launches, their model calls, the sums and the tuned update are captured against the static key
+    row; a device-to-device copy of the iteration's key (seed and ``t``) into it precedes each replay, like DI's rows, so
+    that every replay draws fresh numbers from the same captured launches.
     """
     word = torch.zeros(1, dtype=torch.float32, device=cur.device)
+    scratch = _scratch_slot(si, vt)
 
     def call(leaf, first):
-        _loss_and_grad(model_fn, [leaf], leaf, y, 1, flavor, targeted, _LossSlot(word, 0) if first else si.slot)
+        _loss_and_grad(model_fn, [leaf], leaf, y, 1, flavor, targeted, _LossSlot(word, 0) if first else scratch)
 
     def iteration():
-        _, grad = _evaluate(cur, si, di, call, advance=False)
+        if vt is None:
+            _, grad = _evaluate(cur, si, di, call, advance=False)
+        else:
+            _, grad = _evaluate_vt(cur, si, di, vt, call, advance=False)
         _fgm_then_project(cur, grad, x0, eps_iter, eps, np.inf, clip_min, clip_max, cur,   # in place: static address
-                          mom=mom, ti=ti, di=di, si=si)
+                          mom=mom, ti=ti, di=di, si=si, vt=vt)
 
     main = torch.cuda.current_stream(cur.device)
     side = torch.cuda.Stream(device=cur.device)
@@ -765,6 +895,8 @@ def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, cl
     with torch.cuda.stream(side):
         if di is not None:
             di.use(0, static=True)
+        if vt is not None:
+            vt.use(0, static=True)
         iteration()
         loss_buf[0:1].copy_(word)
     main.wait_stream(side)
@@ -775,6 +907,8 @@ def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, cl
         for i in range(1, nb_iter):
             if di is not None:
                 di.use(i, static=True)
+            if vt is not None:
+                vt.use(i, static=True)
             graph.replay()
             loss_buf[i:i + 1].copy_(word)
     return cur
@@ -784,7 +918,8 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
                                ori_x=None, time=None, targeted=False, rand_init=True, rand_minmax=None,
                                sanity_checks=True, ls=None, *, flavor=ALBEF, init_eta=None, graph=None,
                                per_sample=False, decay_factor=None, momentum=None, ti_kernel=None,
-                               diversity_prob=None, di_shrink=32, di_rng=None, si_copies=None, nesterov=False):
+                               diversity_prob=None, di_shrink=32, di_rng=None, si_copies=None, nesterov=False,
+                               vt_neighbors=None, vt_beta=1.5, vt_seed=None):
     """PGD over a frozen white box; returns ``(adv_x, loss_list)``, bare ``x`` when eps or eps_iter is 0.
 
     ``ls == 1``: feature loss, ``model_fn`` a callable.  Otherwise the dual-loss loop: ``model_fn = [feature_fn,
@@ -835,6 +970,20 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
     the call without ``si_copies``).  The reported loss is copy 0's; a closure that draws random numbers draws once per
     call.  The dual loop does all of this for both of its evaluations.  With ``si_copies=None, nesterov=False``
     (default) nothing changes.
+    ``vt_neighbors`` / ``vt_beta`` / ``vt_seed`` (extensions, keyword-only): variance tuning, VMI / VNI-FGSM (Wang & He
+    2021; the reference tree has it in no framework).  ``vt_neighbors`` an int N in 1..64: with ``G(p)`` the image
+    gradient of one evaluation at ``p`` (after the SI combination and the DI adjoint, before the smoothing), every
+    evaluation steps along ``G(p) + v`` and then sets ``v <- (1 / N) * sum_i G(p + r_i) - G(p)``, ``r_i ~ U[-vt_beta *
+    eps, vt_beta * eps)`` per element, ``v = 0`` at first; ``p`` is ``adv`` or, with ``nesterov``, the look-ahead point, and
+    the neighbours are not clipped, as in the authors' code.  That is N more model calls per evaluation (times the scale
+    copies), in ascending order after the centre's, all with the centre's DI rows.  The neighbours come from the device
+    (``ops.vt_neighbors``: Philox4x32-10 keyed by ``vt_seed`` -- None draws one seed from ``np.random`` -- the evaluation
+    index of the call and the neighbour index, at most 8 images per launch), their gradients are summed on the device
+    (``ops.vt_accumulate``) and the plain L-inf update tunes in the same launch (``ops.linf_vt_step``); every other path
+    tunes into a scratch (``ops.vt_tune``) in front of the smoothing, the momentum and the update, which run unchanged.
+    The reported loss is the centre's.  The dual loop keeps one ``v`` for its feature evaluations and one for its MLM
+    evaluations.  With ``vt_neighbors=None`` (default) nothing changes, ``vt_beta`` / ``vt_seed`` are ignored and no random
+    number is drawn.
     Reference: A projected_gradient_descent.py:10-199, V :10-196.
     """
     _check_flavor(flavor)
@@ -843,6 +992,7 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
     taps = _validate_ti(ti_kernel)
     spec = _validate_di(diversity_prob, di_shrink, di_rng)
     sspec = _validate_si(si_copies, nesterov, decay_factor)
+    vspec = _validate_vt(vt_neighbors, vt_beta, vt_seed)
     if unchanged:
         return x
     xin = _as_image(x)
@@ -861,8 +1011,9 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
     n_loss = 0
     mom = None if decay is None else _Momentum(decay, xin, momentum)
     ti = _smoother(taps, xin, norm, decay)
-    di = _diversity(spec, xin, nb_iter * (2 if dual else 1), norm, decay, taps)
-    si = _scales(sspec, xin, eps_iter, norm, mom, ti, di)
+    di = _diversity(spec, xin, nb_iter * (2 if dual else 1), norm, decay, taps, vt=vspec is not None)
+    si = _scales(sspec, xin, eps_iter, norm, mom, ti, di, vt=vspec is not None)
+    vt = _variance(vspec, xin, eps, nb_iter * (2 if dual else 1), kinds=2 if dual else 1)
     ws = ops.Workspace()       # loss-gradient / CE scratch buffers live for the whole call, not per iteration
     bad_flag = flag if flag is not None else (
         ops.new_flag(xin.device) if ((dual and sanity_checks) or norm != np.inf) else None)
@@ -873,17 +1024,20 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
             raise ValueError("graph=True supports the feature-loss (ls == 1) L-inf loop only")
         _two_sided(clip_min, clip_max)
         adv = _graphed_linf_loop(model_fn, adv, x0, y, flavor, targeted, eps_iter, eps, clip_min, clip_max, nb_iter,
-                                 loss_buf, mom=mom, ti=ti, di=di, si=si)
+                                 loss_buf, mom=mom, ti=ti, di=di, si=si, vt=vt)
         n_loss, nb_iter = nb_iter, 0
+    scratch = _scratch_slot(si, vt)
 
-    def evaluate(fn, at, y_, ls_, **extra):
+    def evaluate(fn, at, y_, ls_, kind=0, **extra):
         """One gradient evaluation at ``at`` with the loss of copy 0 in the next slot of the loss buffer."""
         slot = _LossSlot(loss_buf, n_loss)
 
         def call(leaf, first):
-            _loss_and_grad(fn, [leaf], leaf, y_, ls_, flavor, targeted, slot if first else si.slot, ws=ws,
+            _loss_and_grad(fn, [leaf], leaf, y_, ls_, flavor, targeted, slot if first else scratch, ws=ws,
                            flag=bad_flag, **extra)
 
+        if vt is not None:
+            return _evaluate_vt(at, si, di, vt, call, kind=kind)[1]
         return _evaluate(at, si, di, call)[1]
 
     for _ in range(nb_iter):
@@ -892,7 +1046,7 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
             n_loss += 1
             _two_sided(clip_min, clip_max)
             adv = _fgm_then_project(adv, grad, x0, eps_iter, eps, norm, clip_min, clip_max, buf[1 - cur],
-                                    flag=bad_flag, mom=mom, ti=ti, di=di, si=si)
+                                    flag=bad_flag, mom=mom, ti=ti, di=di, si=si, vt=vt)
         else:
             if flavor == ALBEF:      # A :163,177-181 slices y; V :162,175 passes it whole
                 y_feat, y_mlm, extra = [y[1], y[2]], [y[0]], dict(bkp=model_fn[0], bkp_y=[y[1], y[2]])
@@ -902,11 +1056,11 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
             n_loss += 1
             _two_sided(clip_min, clip_max)
             mid = _fgm_update(adv, grad, eps_iter, norm, clip_min, clip_max, out=buf[1 - cur], flag=bad_flag,
-                              check_range=False, mom=mom, ti=ti, di=di, si=si)
-            grad = evaluate(model_fn[1], mid, y_mlm, 0, per_sample=per_sample, **extra)
+                              check_range=False, mom=mom, ti=ti, di=di, si=si, vt=vt)
+            grad = evaluate(model_fn[1], mid, y_mlm, 0, kind=1, per_sample=per_sample, **extra)
             n_loss += 1
             adv = _fgm_then_project(mid, grad, x0, eps_iter, eps, norm, clip_min, clip_max, buf[cur],
-                                    flag=bad_flag, mom=mom, ti=ti, di=di, si=si)
+                                    flag=bad_flag, mom=mom, ti=ti, di=di, si=si, vt=vt)
             cur = 1 - cur            # result sits in buf[cur] again after the flip below
         cur = 1 - cur
         del grad
@@ -919,7 +1073,8 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
                                   ori_x=None, time=None, targeted=False, rand_init=True, rand_minmax=None,
                                   sanity_checks=True, ls=None, attack_mask=None, *, flavor=ALBEF, init_eta=None,
                                   decay_factor=None, momentum=None, ti_kernel=None, diversity_prob=None, di_shrink=32,
-                                  di_rng=None, si_copies=None, nesterov=False):
+                                  di_rng=None, si_copies=None, nesterov=False, vt_neighbors=None, vt_beta=1.5,
+                                  vt_seed=None):
     """PGD on ``x = [image, text_embeds]`` (only the image moves); returns ``(adv_image, text_embed_gradient)`` of
     the last iteration.  Only ``ls == 1`` is supported (``ValueError`` otherwise), as in the reference.
     ``decay_factor`` / ``momentum`` (extensions, keyword-only): MI-FGSM on the image, as in
@@ -927,6 +1082,8 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
     TI-FGSM smoothing of the image gradient, as there.  ``diversity_prob`` / ``di_shrink`` / ``di_rng`` (extensions,
     keyword-only): DI-FGSM, as there; only the image is transformed.  ``si_copies`` / ``nesterov`` (extensions,
     keyword-only): SI-NI-FGSM on the image, as there; the text gradient is copy 0's and the other copies see the text
+    embeddings detached.  ``vt_neighbors`` / ``vt_beta`` / ``vt_seed`` (extensions, keyword-only): variance tuning, as
+    there; only the image is perturbed, the text gradient is the centre evaluation's and the neighbours see the text
     embeddings detached.
     Reference: A projected_gradient_descent_vl.py:10-168, V :10-164."""
     _check_flavor(flavor)
@@ -935,6 +1092,7 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
     taps = _validate_ti(ti_kernel)
     spec = _validate_di(diversity_prob, di_shrink, di_rng)
     sspec = _validate_si(si_copies, nesterov, decay_factor)
+    vspec = _validate_vt(vt_neighbors, vt_beta, vt_seed)
     if unchanged:
         return x
     img = _as_image(x[0], "x[0]")
@@ -954,8 +1112,10 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
     ws = ops.Workspace()
     mom = None if decay is None else _Momentum(decay, img, momentum)
     ti = _smoother(taps, img, norm, decay)
-    di = _diversity(spec, img, nb_iter, norm, decay, taps)
-    si = _scales(sspec, img, eps_iter, norm, mom, ti, di)
+    di = _diversity(spec, img, nb_iter, norm, decay, taps, vt=vspec is not None)
+    si = _scales(sspec, img, eps_iter, norm, mom, ti, di, vt=vspec is not None)
+    vt = _variance(vspec, img, eps, nb_iter)
+    scratch = _scratch_slot(si, vt)
     if attack_mask is not None and not isinstance(attack_mask, ops.RowIndex):   # validated + uploaded once per call
         attack_mask = ops.RowIndex(attack_mask, emb.shape[1], emb.device)
     for it in range(nb_iter):
@@ -967,14 +1127,14 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
                 _loss_and_grad(model_fn, [leaf_img, leaf_txt], [leaf_img, leaf_txt], y, ls, flavor, targeted, slot,
                                vl=True, ws=ws, flag=flag)
             else:
-                _loss_and_grad(model_fn, [leaf_img], [leaf_img, emb.detach()], y, ls, flavor, targeted, si.slot, vl=True,
+                _loss_and_grad(model_fn, [leaf_img], [leaf_img, emb.detach()], y, ls, flavor, targeted, scratch, vl=True,
                                ws=ws, flag=flag)
 
-        grad = _evaluate(adv, si, di, call)[1]
+        grad = (_evaluate(adv, si, di, call) if vt is None else _evaluate_vt(adv, si, di, vt, call))[1]
         text_grad = ops.gather_rows(_grad_of(leaf_txt), attack_mask)
         _two_sided(clip_min, clip_max)
         adv = _fgm_then_project(adv, grad, x0, eps_iter, eps, norm, clip_min, clip_max, buf[1 - cur],
-                                flag=flag, mom=mom, ti=ti, di=di, si=si)
+                                flag=flag, mom=mom, ti=ti, di=di, si=si, vt=vt)
         cur = 1 - cur
         del grad, leaf_txt
     _finish(flag, eps, eps_iter, norm, clip_min, clip_max, sanity_checks)
@@ -985,7 +1145,8 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
 def momentum_iterative_method(model_fn, x, eps, eps_iter, nb_iter, norm, clip_min=None, clip_max=None, y=None,
                               ori_x=None, targeted=False, decay_factor=1.0, sanity_checks=True, ls=1, *, flavor=ALBEF,
                               graph=None, momentum=None, ti_kernel=None, diversity_prob=None, di_shrink=32,
-                              di_rng=None, si_copies=None, nesterov=False):
+                              di_rng=None, si_copies=None, nesterov=False, vt_neighbors=None, vt_beta=1.5,
+                              vt_seed=None):
     """The momentum iterative method (Dong et al. 2017) on this project's losses; returns ``(adv_x, loss_list)`` like
     ``projected_gradient_descent``, so a driver can swap one for the other.
 
@@ -996,7 +1157,8 @@ def momentum_iterative_method(model_fn, x, eps, eps_iter, nb_iter, norm, clip_mi
     (centre of the eps-ball) defaults to ``x``; ``ls``, ``flavor``, ``graph``, ``momentum`` and ``ti_kernel``
     (TI-MI-FGSM, the combination the TI paper recommends) as in ``projected_gradient_descent``, which runs the loop;
     ``diversity_prob`` / ``di_shrink`` / ``di_rng`` as there too (M-DI2-FGSM; with ``ti_kernel`` TI-DIM), and so are
-    ``si_copies`` / ``nesterov`` (SI-NI-FGSM; with the other keys SI-NI-TI-DIM)."""
+    ``si_copies`` / ``nesterov`` (SI-NI-FGSM; with the other keys SI-NI-TI-DIM) and ``vt_neighbors`` / ``vt_beta`` /
+    ``vt_seed`` (VMI-FGSM; with ``nesterov`` VNI-FGSM)."""
     if norm != 1 and decay_factor is None:
         raise ValueError("decay_factor must be a number (use projected_gradient_descent for the attack without momentum)")
     return projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_min=clip_min, clip_max=clip_max,
@@ -1004,4 +1166,5 @@ def momentum_iterative_method(model_fn, x, eps, eps_iter, nb_iter, norm, clip_mi
                                       sanity_checks=sanity_checks, ls=ls, flavor=flavor, graph=graph,
                                       decay_factor=decay_factor, momentum=momentum, ti_kernel=ti_kernel,
                                       diversity_prob=diversity_prob, di_shrink=di_shrink, di_rng=di_rng,
-                                      si_copies=si_copies, nesterov=nesterov)
+                                      si_copies=si_copies, nesterov=nesterov, vt_neighbors=vt_neighbors,
+                                      vt_beta=vt_beta, vt_seed=vt_seed)

@@ -639,8 +639,144 @@ def linf_si_step(x, grads, x0, weights, eps_iter, eps, clip_min, clip_max, flag=
     return out
 
 
+# ----------------------------------------------------------------------------------------- variance tuning (VMI / VNI-FGSM)
+VT_MAX_CHUNK = 8       # VQA_VT_MAX_CHUNK of include/vqattack_hip.h (vqa_vt_max_chunk())
+VT_MAX_NEIGHBORS = 64
+
+
+def vt_key_table(seed, n_evals, device):
+    """The ``(n_evals, 3)`` uint32 device table of ``vt_neighbors`` keys, row ``t`` = ``(seed & 0xffffffff, seed >> 32,
+    t)``, uploaded in one copy."""
+    seed, n_evals = int(seed), int(n_evals)
+    if seed < 0 or seed >= 1 << 64:
+        raise ValueError("seed must be in [0, 2^64), got {}".format(seed))
+    if n_evals < 0 or n_evals >= 1 << 32:
+        raise ValueError("n_evals must be in [0, 2^32), got {}".format(n_evals))
+    table = np.empty((n_evals, 3), dtype=np.uint32)
+    table[:, 0] = seed & 0xFFFFFFFF
+    table[:, 1] = seed >> 32
+    table[:, 2] = np.arange(n_evals, dtype=np.uint32)
+    return torch.from_numpy(table).to(device)
+
+
+def _vt_key(key):
+    if not isinstance(key, torch.Tensor):
+        raise TypeError("key must be a torch.Tensor, got {}".format(type(key)))
+    if not key.is_cuda:
+        raise _hip.HipExtensionError("key lives on '{}': there is no CPU fallback".format(key.device))
+    if key.dtype != torch.uint32 or tuple(key.shape) != (3,) or not key.is_contiguous():
+        raise ValueError("key must be a contiguous uint32 row (seed_lo, seed_hi, t), got {} {}".format(
+            key.dtype, tuple(key.shape)))
+    return key
+
+
+def vt_neighbors(x, key, count, bound, first=0, m=None, lookahead=0.0, block_offset=0, out=None):
+    """``out[c] = base + r_{first + c}``, ``c < count <= VT_MAX_CHUNK``: the neighbours ``first .. first + count - 1`` of
+    the evaluation whose ``(seed_lo, seed_hi, t)`` the device row ``key`` holds, in one launch, as a ``(count,) +
+    x.shape`` tensor.  ``base`` is ``x``, or ``x + lookahead * m`` with the momentum ``m``; ``r ~ U[-bound, bound)`` per
+    element from Philox4x32-10 (include/vqattack_hip.h states counter, key and the word-to-value chain).  No clamp.
+    ``out`` must not overlap ``x``, ``m`` or ``key``; each ``out[c]`` must be contiguous, and the neighbours may lie further
+    apart than ``x.numel()`` (the batch prefix of a larger buffer)."""
+    count, first, block_offset = int(count), int(first), int(block_offset)
+    if count < 1 or count > VT_MAX_CHUNK:
+        raise ValueError("count must be in 1..{}, got {}".format(VT_MAX_CHUNK, count))
+    if first < 0 or first + count > 1 << 31:
+        raise ValueError("first must be >= 0 and first + count <= 2^31, got {}".format(first))
+    if block_offset < 0 or block_offset >= 1 << 64:
+        raise ValueError("block_offset must be in [0, 2^64), got {}".format(block_offset))
+    dev_f32(x, "x")
+    _vt_key(key)
+    if m is not None:
+        dev_f32(m, "momentum")
+        if m.shape != x.shape:
+            raise ValueError("momentum shape {} != x shape {}".format(tuple(m.shape), tuple(x.shape)))
+    shape = (count,) + tuple(x.shape)
+    same_device(x, m, out, key)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        dev_f32(out, "out", contiguous=False)
+        if tuple(out.shape) != shape:
+            raise ValueError("out has shape {}, expected {}".format(tuple(out.shape), shape))
+        if not out[0].is_contiguous() or (count > 1 and out.stride(0) < x.numel()):
+            raise ValueError("every out[c] must be contiguous and the neighbours must not overlap")
+    if x.numel() == 0:
+        return out
+    stride = out.stride(0) if count > 1 else x.numel()
+    with _on(x):
+        check(lib().vqa_vt_neighbors(ptr(x), ptr(m), ptr(out), x.numel(), stride, count, first, block_offset,
+                                     float(bound), float(lookahead), ctypes.c_void_p(key.data_ptr()), stream_for(x)),
+              "vqa_vt_neighbors")
+    return out
+
+
+def vt_accumulate(grads, sum, init):
+    """``sum = (g_0 if init else sum + g_0) + g_1 + ...`` in place (ascending, one rounding per addition): 1..VT_MAX_CHUNK
+    gradients per launch; grouping them differently gives the same bits.  ``sum`` may alias no gradient."""
+    if isinstance(grads, torch.Tensor) or not isinstance(grads, (list, tuple)):
+        raise TypeError("grads must be a list or tuple of tensors, got {}".format(type(grads)))
+    if len(grads) < 1 or len(grads) > VT_MAX_CHUNK:
+        raise ValueError("grads must hold 1..{} tensors, got {}".format(VT_MAX_CHUNK, len(grads)))
+    dev_f32(sum, "sum")
+    for i, g in enumerate(grads):
+        dev_f32(g, "grads[{}]".format(i))
+        if g.shape != sum.shape:
+            raise ValueError("grads[{}] has shape {}, sum {}".format(i, tuple(g.shape), tuple(sum.shape)))
+    same_device(sum, *grads)
+    if sum.numel() == 0:
+        return sum
+    pbuf = (ctypes.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
+    with _on(sum):
+        check(lib().vqa_vt_accumulate(pbuf, len(grads), ptr(sum), sum.numel(), 1 if init else 0, stream_for(sum)),
+              "vqa_vt_accumulate")
+    return sum
+
+
+def _vt_state(g, vsum, v):
+    dev_f32(g, "grad"), dev_f32(vsum, "vsum"), dev_f32(v, "v")
+    if vsum.shape != g.shape or v.shape != g.shape:
+        raise ValueError("shape mismatch: grad {}, vsum {}, v {}".format(tuple(g.shape), tuple(vsum.shape),
+                                                                         tuple(v.shape)))
+
+
+def vt_tune(g, vsum, v, w, out=None):
+    """``out = g + v`` and then ``v = w * vsum - g`` in place, one pass, 20 B/element; returns ``out`` (the tuned gradient).
+    ``out`` may be ``g``; no other two of the four may overlap."""
+    _vt_state(g, vsum, v)
+    same_device(g, vsum, v, out)
+    out = _out_like(g, out)
+    if g.numel() == 0:
+        return out
+    with _on(g):
+        check(lib().vqa_vt_tune(ptr(g), ptr(vsum), ptr(v), ptr(out), g.numel(), float(w), stream_for(g)), "vqa_vt_tune")
+    return out
+
+
+def linf_vt_step(x, g, vsum, v, x0, w, eps_iter, eps, clip_min, clip_max, flag=None, out=None):
+    """``vt_tune`` and ``linf_step`` on its result in one pass, 28 B/element; ``x0=None``: and ``linf_fgm`` (no
+    projection).  The tuned gradient never reaches memory; ``v`` is updated in place; ``out`` may be ``x``."""
+    dev_f32(x, "x")
+    if x0 is not None:
+        dev_f32(x0, "ori_x")
+    _vt_state(g, vsum, v)
+    if g.shape != x.shape or (x0 is not None and x0.shape != x.shape):
+        raise ValueError("shape mismatch: x {}, grad {}, ori_x {}".format(
+            tuple(x.shape), tuple(g.shape), None if x0 is None else tuple(x0.shape)))
+    same_device(x, g, vsum, v, x0, out, flag)
+    out = _out_like(x, out)
+    mode, lo, hi = _clip_args(clip_min, clip_max)
+    if flag is not None and mode:
+        mode |= VQA_CHECK_RANGE
+    if x.numel() == 0:
+        return out
+    with _on(x):
+        check(lib().vqa_linf_vt_step(ptr(x), ptr(g), ptr(vsum), ptr(v), ptr(x0), ptr(out), x.numel(), float(w), eps_iter,
+                                     eps, lo, hi, mode, ptr(flag), stream_for(x)), "vqa_linf_vt_step")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- loss
-_COS_EPS = 1e-6  # nn.CosineSimilarity(eps=1e-6) in the reference
+_COS_EPS = 1e-6 # nn.CosineSimilarity(eps=1e-6) in the reference
 _partials = {}
 
 
