@@ -17,7 +17,6 @@ Attack hyper-parameters default to the reference's hard-coded literals (adv_atta
 L-inf, clip [-1, 1]).
 """
 from dataclasses import dataclass, field
-from types import SimpleNamespace
 from typing import Optional
 
 import numpy as np
@@ -55,29 +54,24 @@ class AttackConfig:
     vt_beta: float = 1.5                   # VT: neighbours are drawn from U[-vt_beta * eps, vt_beta * eps) (the paper's 1.5)
     vt_seed: Optional[int] = None          # VT: 64-bit seed of the device-side draws (None: one seed from np.random per call)
 
+    TRANSFER_KEYS = ("decay_factor", "ti_kernel", "diversity_prob", "di_shrink", "si_copies", "nesterov", "vt_neighbors",
+                     "vt_beta", "vt_seed")        # the fields the operators take under the same names
+
+    def transfer_kwargs(self):
+        """The transfer-method keywords of an operator call; the caller adds ``momentum`` and ``di_rng``."""
+        return {key: getattr(self, key) for key in self.TRANSFER_KEYS}
+
     def __post_init__(self):
-        attacks._validate_decay(self.decay_factor)
-        if self.decay_factor is not None and self.patch_layout:
-            # the per-sample sum of |grad| is folded in memory order: a patch-major image would round it differently
-            raise ValueError("decay_factor and patch_layout=True cannot be combined")
-        attacks._validate_ti(self.ti_kernel)
-        if self.ti_kernel is not None and self.patch_layout:
-            # the stencil runs over row-major (H, W) planes: a patch-major image has none
-            raise ValueError("ti_kernel and patch_layout=True cannot be combined")
-        attacks._validate_di(self.diversity_prob, self.di_shrink)
+        attacks._validate_stages(**self.transfer_kwargs())
         if self.di_seed is not None and (isinstance(self.di_seed, bool) or not isinstance(self.di_seed, (int, np.integer))
                                          or not 0 <= int(self.di_seed) < 2 ** 32):
             raise ValueError("di_seed must be None or an int in [0, 2^32), got {!r}".format(self.di_seed))
-        if self.diversity_prob is not None and self.patch_layout:
-            # the transform resamples row-major (H, W) planes: a patch-major image has none
-            raise ValueError("diversity_prob and patch_layout=True cannot be combined")
-        attacks._validate_si(self.si_copies, self.nesterov, self.decay_factor)
-        if self.si_copies is not None and self.patch_layout:
-            # like the other three keys: the patch-major path is not exercised with any transfer method
-            raise ValueError("si_copies and patch_layout=True cannot be combined")
-        attacks._validate_vt(self.vt_neighbors, self.vt_beta, self.vt_seed)
-        if self.vt_neighbors is not None and self.patch_layout:
-            raise ValueError("vt_neighbors and patch_layout=True cannot be combined")
+        # no transfer method runs on a patch-major image: the per-sample sum of |grad| is folded in memory order and would
+        # round differently, the TI stencil and the DI transform run over row-major (H, W) planes, and the patch-major path
+        # is not exercised with the other two
+        for key in ("decay_factor", "ti_kernel", "diversity_prob", "si_copies", "vt_neighbors"):
+            if getattr(self, key) is not None and self.patch_layout:
+                raise ValueError("{} and patch_layout=True cannot be combined".format(key))
 
 
 @dataclass
@@ -158,10 +152,8 @@ class BatchedVQAttack:
     def _pgd_block(self, adv, clean, targets, steps, time, dual, mlm_labels, init_eta=None, momentum=None):
         c = self.cfg
         common = dict(clip_min=c.clip_min, clip_max=c.clip_max, time=time, ori_x=clean,
-                      sanity_checks=c.sanity_checks, init_eta=init_eta, decay_factor=c.decay_factor, momentum=momentum,
-                      ti_kernel=c.ti_kernel, diversity_prob=c.diversity_prob, di_shrink=c.di_shrink,
-                      di_rng=self._di_draws, si_copies=c.si_copies, nesterov=c.nesterov, vt_neighbors=c.vt_neighbors,
-                      vt_beta=c.vt_beta, vt_seed=c.vt_seed)
+                      sanity_checks=c.sanity_checks, init_eta=init_eta, momentum=momentum, di_rng=self._di_draws,
+                      **c.transfer_kwargs())
         a = self.adapters
         if not dual:
             return self.pgd(a.pgd_attack, adv, c.eps, c.eps_iter, steps, c.norm, y=self._y_feature(targets), ls=1,
@@ -271,11 +263,8 @@ class BatchedVQAttack:
                     adv, text_grad = self.pgd_vl(a.pgd_attack_vl, [adv, adv_emb], c.eps, c.eps_iter,
                                                  1, c.norm, clip_min=c.clip_min, clip_max=c.clip_max,
                                                  y=self._y_feature(targets), time=1, ori_x=images, ls=1,
-                                                 attack_mask=positions, sanity_checks=c.sanity_checks,
-                                                 decay_factor=c.decay_factor, momentum=mom, ti_kernel=c.ti_kernel,
-                                                 diversity_prob=c.diversity_prob, di_shrink=c.di_shrink,
-                                                 di_rng=self._di_draws, si_copies=c.si_copies, nesterov=c.nesterov,
-                                                 vt_neighbors=c.vt_neighbors, vt_beta=c.vt_beta, vt_seed=c.vt_seed)
+                                                 attack_mask=positions, sanity_checks=c.sanity_checks, momentum=mom,
+                                                 di_rng=self._di_draws, **c.transfer_kwargs())
                 res.gradient_steps += 1
                 if plan is not None:
                     scores = text_update.score_plan(self.tables, e_ori, text_grad, plan)
@@ -414,14 +403,10 @@ class BatchedVQAttack:
             eta = torch.empty_like(images, memory_format=torch.contiguous_format).uniform_(-c.eps, c.eps)
         cur = ops.linf_init(images.contiguous(), eta, c.eps, c.clip_min, c.clip_max, flag=flag)
         mom = self._new_momentum(images)          # in the sorted order of `images`; only the active prefix is updated
-        # TI-FGSM: the taps and (with momentum) ONE smoothed-gradient scratch for the whole call
-        ti = attacks._smoother(attacks._validate_ti(c.ti_kernel), cur, np.inf, c.decay_factor)
-        # DI-FGSM: the rows of every global step for every sample, drawn and uploaded once; step t uses the active prefix
-        di = attacks._diversity(attacks._validate_di(c.diversity_prob, c.di_shrink, self._start_di()), cur, max(total),
-                                np.inf, c.decay_factor, ti)
-        # SI-NI-FGSM: the copies of every sample (step t fills the active prefix of each), the combined-gradient scratch
-        si = attacks._scales(attacks._validate_si(c.si_copies, c.nesterov, c.decay_factor), cur, c.eps_iter, np.inf,
-                             None if mom is None else SimpleNamespace(decay=float(c.decay_factor), m=mom), ti, di)
+        # the transfer stages of the whole call, sized for every sample: DI's rows of every global step are drawn and
+        # uploaded once, SI's copies and the scratches are filled for the active prefix (the update: for one run) of a step
+        chain = attacks._Chain(attacks._validate_stages(di_rng=self._start_di(), **c.transfer_kwargs()), cur, np.inf, c.eps,
+                               c.eps_iter, max(total), momentum=mom)
         losses = torch.zeros(max(total), dtype=torch.float32, device=dev)
         ws = ops.Workspace()
         res = BatchResult(adv_images=cur, adv_text_ids=adv_ids)
@@ -458,19 +443,8 @@ class BatchedVQAttack:
                 y = [v.rows(n_act) if isinstance(v, LayerFeatures) else (None if v is None else v[:n_act])
                      for v in self._y_feature(targets)]
                 text_key = key
-            if di is not None:
-                di.geom = di.table[t][:n_act]
-            if si is not None:
-                # one launch for every copy of the active prefix, looking ahead with the active prefix of the momentum
-                seen = ops.si_copies(cur[:n_act], si.scales, m=None if si.mom is None else mom[:n_act],
-                                     lookahead=si.lookahead, out=si.images[:, :n_act])
-                if di is not None:                   # all copies of a step share the step's rows
-                    seen = [ops.di_transform(seen[i], di.geom, out=si.transformed[i, :n_act]) for i in range(len(seen))]
-                leaves = [seen[i].detach().requires_grad_(True) for i in range(len(seen))]
-            elif di is None:
-                leaves = [cur[:n_act].detach().requires_grad_(True)]
-            else:
-                leaves = [ops.di_transform(cur[:n_act], di.geom, out=di.image[:n_act]).detach().requires_grad_(True)]
+            chain.use(t)                             # step t's DI rows; the leaves are made for the active prefix
+            leaves = list(chain.leaves(cur[:n_act], advance=False, n=n_act))
             probing = [s for s in range(n_act) if kinds[s][t][1]] if masker is not None else []
             emb_t = adv_emb[:n_act]
             if masker is None or probing:            # (a masked step without probing samples re-embeds every row below)
@@ -489,7 +463,7 @@ class BatchedVQAttack:
             for i, leaf_img in enumerate(leaves):
                 wrt = [leaf_img, leaf_txt] if i == 0 else [leaf_img]
                 seen_by_model = [leaf_img, leaf_txt if i == 0 else emb_t.detach()]
-                slot = attacks._LossSlot(losses, t) if i == 0 else si.slot
+                slot = attacks._LossSlot(losses, t) if i == 0 else chain.slot
                 if use_mixed_closure:
                     attacks._mixed_loss_and_grad(a.pgd_attack_mixed, wrt, seen_by_model, list(y), self.flavor, slot, ws=ws,
                                                  flag=flag, mlm_labels=labels_live[sel] if at_mlm else None)
@@ -497,7 +471,7 @@ class BatchedVQAttack:
                     attacks._loss_and_grad(a.pgd_attack_vl, wrt, seen_by_model, list(y), 1, self.flavor, False, slot,
                                            vl=True, ws=ws)
             grads = [attacks._grad_of(leaf) for leaf in leaves]
-            self._update_runs(cur, grads[0] if si is None else grads, images, now, mom, ti, di, si)
+            self._update_runs(cur, grads[0] if chain.si is None else grads, images, now, chain)
             firing = [s for s in range(n_act) if kinds[s][t][1]]
             if firing:
                 sub = plan.restricted_to(firing)
@@ -558,56 +532,21 @@ class BatchedVQAttack:
                 labels[s, j, :len(row)] = torch.tensor(row)
         return tasks, text_ids, text_masks, attackable, mlm_ids, mlm_mask, (labels[:, 0] if k == 1 else labels).to(dev)
 
-    def _update_runs(self, cur, grad, images, now, mom=None, ti=None, di=None, si=None):
-        """The fused image update of one global step, in place on the active prefix of ``cur``: one launch per run of
-        consecutive samples of one kind -- ``vqa_linf_fgm`` for ``N`` (first half of a dual iteration: no projection in
-        between, projected_gradient_descent.py:155-188), ``vqa_linf_step`` otherwise.  Finished samples stay untouched.
-        ``mom`` (MI-FGSM): ``vqa_linf_momentum_step`` instead, without ``x0`` for ``N`` runs; a run accumulates into its own
-        rows of the momentum, so a finished sample's momentum stays as it was.
-        ``ti`` (TI-FGSM): ``vqa_linf_ti_step`` instead of the two plain kernels; with momentum the run's gradient is smoothed
-        into its rows of the call's scratch first and the momentum step takes that.
-        ``di`` (DI-FGSM): ``grad`` is the gradient at the transformed images; ``vqa_linf_di_step`` applies the adjoint and
-        the update in one launch, with TI or momentum the run's adjoint goes into its rows of the call's scratch first.
-        ``si`` (SI-NI-FGSM): ``grad`` is the LIST of the copies' gradients, every one sliced per run; ``vqa_linf_si_step``
-        combines and updates in one launch, with DI, TI or momentum the run's combination goes into its rows of the call's
-        scratch first and the rest of the chain takes that."""
+    def _update_runs(self, cur, grad, images, now, chain=None):
+        """The fused image update of one global step, in place on the active prefix of ``cur``: one ``chain.update`` per
+        run of consecutive samples of one kind -- the FGM form (no ``x0``) for ``N`` (first half of a dual iteration: no
+        projection in between, projected_gradient_descent.py:155-188), the step form otherwise; without a chain that is
+        ``vqa_linf_fgm`` / ``vqa_linf_step``.  ``grad`` is what the chain's leaves gave for the active prefix (with SI the
+        LIST of the copies' gradients).  A run reads and writes its own rows of the chain's state only, so a finished
+        sample's image and momentum stay as they were."""
         c, lo, n_act = self.cfg, 0, len(now)
+        chain = attacks._Chain() if chain is None else chain
         while lo < n_act:
             hi = lo + 1
             while hi < n_act and (now[hi] == "N") == (now[lo] == "N"):
                 hi += 1
-            x0 = None if now[lo] == "N" else images[lo:hi]
-            if si is not None:
-                per_copy = [g[lo:hi] for g in grad]
-                if di is None and mom is None and ti is None:
-                    ops.linf_si_step(cur[lo:hi], per_copy, x0, si.weights, c.eps_iter, c.eps, c.clip_min, c.clip_max,
-                                     out=cur[lo:hi])
-                    lo = hi
-                    continue
-                grad_in = ops.si_combine(per_copy, si.weights, out=si.ghat[lo:hi])
-            else:
-                grad_in = grad[lo:hi]
-            if di is not None:
-                if mom is None and ti is None:
-                    ops.linf_di_step(cur[lo:hi], grad_in, x0, di.geom[lo:hi], c.eps_iter, c.eps, c.clip_min, c.clip_max,
-                                     out=cur[lo:hi])
-                    lo = hi
-                    continue
-                grad_run = ops.di_adjoint(grad_in, di.geom[lo:hi], out=di.grad[lo:hi])
-            else:
-                grad_run = grad_in
-            if mom is not None:
-                g = grad_run if ti is None else ops.ti_smooth(grad_run, ti.taps, out=ti.ghat[lo:hi])
-                ops.linf_momentum_step(cur[lo:hi], g, x0, mom[lo:hi], c.decay_factor, c.eps_iter, c.eps, c.clip_min,
-                                       c.clip_max, out=cur[lo:hi])
-            elif ti is not None:
-                ops.linf_ti_step(cur[lo:hi], grad_run, x0, ti.taps, c.eps_iter, c.eps, c.clip_min, c.clip_max,
-                                 out=cur[lo:hi])
-            elif now[lo] == "N":
-                ops.linf_fgm(cur[lo:hi], grad_run, c.eps_iter, c.clip_min, c.clip_max, out=cur[lo:hi])
-            else:
-                ops.linf_step(cur[lo:hi], grad_run, images[lo:hi], c.eps_iter, c.eps, c.clip_min, c.clip_max,
-                              out=cur[lo:hi])
+            chain.update(cur, grad, None if now[lo] == "N" else images, c.eps_iter, c.eps, c.clip_min, c.clip_max, out=cur,
+                         rows=(lo, hi))
             lo = hi
 
     def _follow_substitutions(self, tasks, samples, mlm_ids, mlm_mask, subs):

@@ -431,33 +431,20 @@ class _Momentum:
 
 class _Smoother:
     """The TI-FGSM state of one operator call: the taps and -- allocated once, so that a captured iteration finds it at a
-    static address -- one tensor for the smoothed gradient.  ``scratch=False``: the caller only runs the fused L-inf step
+    static address -- one tensor for the smoothed gradient.  ``scratch=False``: the update only runs the fused L-inf step
     (``ops.linf_ti_step``), which keeps the smoothed gradient in registers."""
 
-    def __init__(self, taps, like, scratch=True):
+    def __init__(self, taps, like, scratch):
         self.taps = taps
         self.ghat = torch.empty_like(like, memory_format=torch.contiguous_format) if scratch else None
-
-    def smooth(self, grad):
-        return ops.ti_smooth(grad, self.taps, out=self.ghat)
-
-
-def _smoother(taps, like, norm, decay):
-    """None without TI; the scratch is needed by every update but the plain L-inf one."""
-    if taps is None:
-        return None
-    if like.dim() != 4:
-        raise ValueError("ti_kernel needs a (B, C, H, W) image: the stencil runs over its (H, W) planes, got shape {}".format(
-            tuple(like.shape)))
-    return _Smoother(taps, like, scratch=decay is not None or norm != np.inf)
 
 
 class _Diversity:
     """The DI-FGSM state of one operator call: the geometry rows of ALL its gradient evaluations, drawn once on the host
     and uploaded in one copy (``(n_evals, B, 4)``), one static ``(B, 4)`` row for a captured iteration, the transformed
-    image and -- unless the caller only runs the fused L-inf step (``ops.linf_di_step``) -- the adjoint's result."""
+    image and -- unless the update only runs the fused L-inf step (``ops.linf_di_step``) -- the adjoint's result."""
 
-    def __init__(self, spec, like, n_evals, scratch=True):
+    def __init__(self, spec, like, n_evals, scratch):
         prob, shrink, rng = spec
         b, _, h, w = like.shape
         self.table = ops.di_geometry(ops.di_draw(rng, b, n_evals, h, w, shrink, prob), h, w, like.device)
@@ -472,35 +459,14 @@ class _Diversity:
             self.row.copy_(self.table[i])
         self.geom = self.row if static else self.table[i]
 
-    def leaf(self, adv, advance=True, out=None):
-        """The leaf the model sees: the transformed image (the next evaluation's rows unless ``advance=False``)."""
-        if advance:
-            self.use(self.n)
-            self.n += 1
-        return ops.di_transform(adv, self.geom, out=self.image if out is None else out).detach().requires_grad_(True)
-
-    def adjoint(self, gd):
-        return ops.di_adjoint(gd, self.geom, out=self.grad)
-
-
-def _diversity(spec, like, n_evals, norm, decay, taps, vt=False):
-    """None without DI; the adjoint scratch is needed by every update but the plain L-inf one (and by variance tuning,
-    whose state lives in x space)."""
-    if spec is None:
-        return None
-    if like.dim() != 4:
-        raise ValueError("diversity_prob needs a (B, C, H, W) image: the transform runs over its (H, W) planes, got shape "
-                         "{}".format(tuple(like.shape)))
-    return _Diversity(spec, like, n_evals, scratch=decay is not None or taps is not None or norm != np.inf or vt)
-
 
 class _Scales:
     """The SI-NI-FGSM state of one operator call: scales and weights on the host and -- allocated once, so that a
     captured iteration finds them at static addresses -- the scaled copies the model sees, their DI transforms when
-    there is input diversity, one word for the losses of the copies after the first and, unless the caller only runs the
+    there is input diversity, one word for the losses of the copies after the first and, unless the update only runs the
     fused L-inf step (``ops.linf_si_step``), the combined gradient.  ``mom``: look ahead along its momentum (Nesterov)."""
 
-    def __init__(self, spec, like, eps_iter, mom, di, scratch=True):
+    def __init__(self, spec, like, eps_iter, mom, di, scratch):
         scales, nesterov = spec
         self.scales, self.weights = scales, ops.si_weights(scales)
         self.mom = mom if nesterov else None
@@ -510,24 +476,6 @@ class _Scales:
         self.transformed = torch.empty(shape, dtype=torch.float32, device=like.device) if di is not None else None
         self.ghat = torch.empty_like(like, memory_format=torch.contiguous_format) if scratch else None
         self.slot = _LossSlot(torch.zeros(1, dtype=torch.float32, device=like.device), 0)
-
-    def copies(self, adv, ahead=True):
-        """``ahead=False``: ``adv`` already is the point the copies are taken at (a variance-tuning neighbour)."""
-        if not ahead or self.mom is None:
-            return ops.si_copies(adv, self.scales, out=self.images)
-        return ops.si_copies(adv, self.scales, m=self.mom.m, lookahead=self.lookahead, out=self.images)
-
-    def combine(self, grads):
-        return ops.si_combine(grads, self.weights, out=self.ghat)
-
-
-def _scales(spec, like, eps_iter, norm, mom, ti, di, vt=False):
-    """None without SI / NI; the combined-gradient scratch is needed by every update but the plain L-inf one (and by
-    variance tuning)."""
-    if spec is None:
-        return None
-    return _Scales(spec, like, eps_iter, mom, di,
-                   scratch=mom is not None or ti is not None or di is not None or norm != np.inf or vt)
 
 
 class _Variance:
@@ -552,7 +500,7 @@ class _Variance:
         self.table = ops.vt_key_table(seed, n_evals, like.device)
         self.row = torch.empty(3, dtype=torch.uint32, device=like.device)
         self.slot = _LossSlot(torch.zeros(1, dtype=torch.float32, device=like.device), 0)
-        self.key, self.t, self.kind, self.plain = None, 0, 0, True
+        self.key, self.t, self.kind = None, 0, 0
 
     def use(self, t, static=False):
         """Make evaluation ``t``'s key current: in place in the table, or (``static``) copied into the static row."""
@@ -560,161 +508,186 @@ class _Variance:
             self.row.copy_(self.table[t])
         self.key = self.row if static else self.table[t]
 
-    def tune(self, grad):
-        return ops.vt_tune(grad, self.vsum, self.v[self.kind], self.w, out=self.ghat)
+
+def _validate_stages(decay_factor=None, ti_kernel=None, diversity_prob=None, di_shrink=32, di_rng=None, si_copies=None,
+                     nesterov=False, vt_neighbors=None, vt_beta=1.5, vt_seed=None):
+    """The transfer keywords of an operator call as the specs ``_Chain`` takes (None: that stage is off), validated in
+    this order and before any tensor is looked at."""
+    return (_validate_decay(decay_factor), _validate_ti(ti_kernel), _validate_di(diversity_prob, di_shrink, di_rng),
+            _validate_si(si_copies, nesterov, decay_factor), _validate_vt(vt_neighbors, vt_beta, vt_seed))
 
 
-def _variance(spec, like, eps, n_evals, kinds=1):
-    return None if spec is None else _Variance(spec, like, eps, n_evals, kinds)
+class _Chain:
+    """The optional transfer stages of one operator call -- momentum, TI, DI, SI / NI, variance tuning, each None or its
+    state above -- and the ONE statement of how a gradient evaluation and an image update run through them.
 
+    The rule: the stages of an update run in the order SI combine, DI adjoint, VT tune, TI smooth, momentum.  With the
+    L-inf norm the last active one runs inside the update's own launch (``ops.linf_*_step``), variance tuning only on a
+    gradient that no SI / DI had to take to x space first; every other active stage writes into a scratch of its own,
+    allocated here, once, so that a captured iteration finds it at a static address.  ``fused`` names that last stage.
 
-def _scratch_slot(si, vt):
-    """The word that takes the losses nobody reports: those of the scale copies after the first and of the neighbours."""
-    return si.slot if si is not None else (vt.slot if vt is not None else None)
+    Built from ``_validate_stages``' specs in the order momentum, TI, DI, SI, VT: DI draws its rows and VT (without a seed)
+    its seed from ``np.random``, in that order.  ``like``: the image; ``n_evals``: gradient evaluations of the call;
+    ``kinds``: evaluation kinds that tune a variance of their own; ``momentum``: the caller's tensor or None (zeros).
+    Without specs it is the plain update and touches no tensor of its own.
 
+    The mixed-schedule driver runs one chain on row subsets of its state: ``leaves(.., n=)`` on the active batch prefix,
+    ``update(.., rows=(lo, hi))`` on one run of samples."""
 
-def _evaluate(adv, si, di, call, advance=True, ahead=True):
-    """One gradient evaluation at ``adv``.  ``call(leaf, first)`` runs the white box and the loss on one leaf and leaves
-    the gradient in ``leaf.grad``.  Without ``si``: one call on ``adv`` (or its DI transform).  With it: the copies in one
-    launch, then one call per copy in ascending order, each on a leaf of its own; all copies of the evaluation share its
-    DI rows, so the adjoint is linear over them and the combination may precede it.
-    ``ahead=False``: no Nesterov look-ahead in front of the copies (``adv`` is a variance-tuning neighbour, drawn around
-    the look-ahead point already).
-    Returns ``(first leaf, gradient)``; with ``si`` the gradient is the list of the copies' gradients."""
-    if si is None:
-        leaf = adv.detach().requires_grad_(True) if di is None else di.leaf(adv, advance=advance)
-        call(leaf, True)
-        return leaf, _grad_of(leaf)
-    images = si.copies(adv, ahead=ahead)
-    first, grads = None, []
-    for i in range(images.shape[0]):
-        if di is None:
-            leaf = images[i].detach().requires_grad_(True)
-        else:
-            leaf = di.leaf(images[i], advance=advance and i == 0, out=si.transformed[i])
-        call(leaf, i == 0)
-        grads.append(_grad_of(leaf))
-        if i == 0:
-            first = leaf
-    return first, grads
+    def __init__(self, specs=(None,) * 5, like=None, norm=np.inf, eps=0.0, eps_iter=0.0, n_evals=1, kinds=1,
+                 momentum=None):
+        decay, taps, dspec, sspec, vspec = specs
+        active = [name for name, spec in (("si", sspec), ("di", dspec), ("vt", vspec), ("ti", taps), ("mom", decay))
+                  if spec is not None]
+        self.norm = norm
+        self.fused = active[-1] if active and norm == np.inf else None
+        if self.fused == "vt" and len(active) > 1:
+            self.fused = None
+        self.plain = sspec is None and dspec is None           # a leaf's gradient is in x space as it is
+        self.mom = None if decay is None else _Momentum(decay, like, momentum)
+        for spec, key, what in ((taps, "ti_kernel", "stencil"), (dspec, "diversity_prob", "transform")):
+            if spec is not None and like.dim() != 4:
+                raise ValueError("{} needs a (B, C, H, W) image: the {} runs over its (H, W) planes, got shape {}".format(
+                    key, what, tuple(like.shape)))
+        self.ti = None if taps is None else _Smoother(taps, like, self.fused != "ti")
+        self.di = None if dspec is None else _Diversity(dspec, like, n_evals, self.fused != "di")
+        self.si = None if sspec is None else _Scales(sspec, like, eps_iter, self.mom, self.di, self.fused != "si")
+        self.vt = None if vspec is None else _Variance(vspec, like, eps, n_evals, kinds)
+        # the word that takes the losses nobody reports: those of the scale copies after the first and of the neighbours
+        self.slot = self.si.slot if self.si is not None else (self.vt.slot if self.vt is not None else None)
 
+    def use(self, i, static=False):
+        """Make DI's rows and VT's key of evaluation ``i`` current (``static``: copied to their static addresses)."""
+        if self.di is not None:
+            self.di.use(i, static)
+        if self.vt is not None:
+            self.vt.use(i, static)
 
-def _x_gradient(grad, si, di, out=None):
-    """``G`` of variance tuning: what ``_evaluate`` returned, taken to x space -- the SI combination, then the DI adjoint,
-    each into its own scratch (the last one into ``out`` when given); without either the leaf's gradient itself."""
-    if si is not None:
-        grad = ops.si_combine(grad, si.weights, out=si.ghat if (out is None or di is not None) else out)
-    if di is not None:
-        grad = ops.di_adjoint(grad, di.geom, out=di.grad if out is None else out)
-    return grad
+    def leaves(self, adv, advance=True, ahead=True, n=None):
+        """The leaves the model sees for one gradient evaluation at ``adv``, made one at a time: ``adv`` itself or its DI
+        transform (the next evaluation's rows unless ``advance=False``); with SI the scaled copies from one launch, in
+        ascending order -- all copies of an evaluation share its DI rows, so the adjoint is linear over them and the
+        combination may precede it.  ``ahead=False``: no Nesterov look-ahead in front of the copies (``adv`` is a
+        variance-tuning neighbour, drawn around the look-ahead point already).  ``n``: ``adv`` is the batch prefix
+        ``[:n]``; the state is sliced to match."""
+        si, di = self.si, self.di
+        head = (lambda t: t) if n is None else (lambda t: t[:n])
+        if di is not None and advance:
+            di.use(di.n)
+            di.n += 1
+        if si is None:
+            seen = adv if di is None else ops.di_transform(adv, head(di.geom), out=head(di.image))
+            yield seen.detach().requires_grad_(True)
+            return
+        m = head(si.mom.m) if ahead and si.mom is not None else None
+        images = ops.si_copies(adv, si.scales, m=m, lookahead=0.0 if m is None else si.lookahead,
+                               out=si.images if n is None else si.images[:, :n])
+        for i in range(images.shape[0]):
+            seen = images[i] if di is None else ops.di_transform(images[i], head(di.geom), out=head(si.transformed[i]))
+            yield seen.detach().requires_grad_(True)
 
-
-def _evaluate_vt(adv, si, di, vt, call, kind=0, advance=True):
-    """One variance-tuned gradient evaluation at ``adv``: the centre through ``_evaluate``, then the ``vt.n`` neighbours
-    ``p + r_i`` (``p`` the look-ahead point with Nesterov) in chunks of at most 8 images per launch through the same
-    ``_evaluate``, every one with the centre's DI rows and ``call(leaf, False)`` (their losses go to a scratch word).
-    Without SI / DI up to 8 leaf gradients are summed per launch; with either each neighbour's gradient is combined /
-    adjoint-ed into its scratch and summed one at a time -- the same bits.  Leaves ``sum_i G(p + r_i)`` in ``vt.vsum``
-    and returns ``(first leaf, G(p))``, ``G(p)`` in x space."""
-    if advance:
-        vt.use(vt.t)
-        vt.t += 1
-    vt.kind, vt.plain = kind, si is None and di is None
-    first, grad = _evaluate(adv, si, di, call, advance=advance)
-    g = _x_gradient(grad, si, di, out=vt.ghat)
-    m, lookahead = (si.mom.m, si.lookahead) if si is not None and si.mom is not None else (None, 0.0)
-
-    def other(leaf, _):
-        call(leaf, False)
-
-    for start in range(0, vt.n, ops.VT_MAX_CHUNK):
-        count = min(ops.VT_MAX_CHUNK, vt.n - start)
-        images = ops.vt_neighbors(adv, vt.key, count, vt.bound, first=start, m=m, lookahead=lookahead,
-                                  out=vt.chunk[:count])
+    def _gradient(self, adv, call, advance=True, ahead=True):
+        """``call(leaf, first)`` on every leaf in turn: it runs the white box and the loss and leaves the gradient in
+        ``leaf.grad``.  Returns the leaf's gradient, with SI the list of the copies' gradients."""
         grads = []
-        for c in range(count):
-            gn = _evaluate(images[c], si, di, other, advance=False, ahead=False)[1]
-            if vt.plain:
-                grads.append(gn)
-            else:
-                ops.vt_accumulate([_x_gradient(gn, si, di)], vt.vsum, init=start + c == 0)
-        if grads:
-            ops.vt_accumulate(grads, vt.vsum, init=start == 0)
-    return first, g
+        for i, leaf in enumerate(self.leaves(adv, advance, ahead)):
+            call(leaf, i == 0)
+            grads.append(_grad_of(leaf))
+        return grads if self.si is not None else grads[0]
 
+    def _x_gradient(self, grad, out=None):
+        """``G`` of variance tuning: what ``_gradient`` returned, taken to x space -- the SI combination, then the DI
+        adjoint, each into its own scratch (the last one into ``out`` when given); without either the leaf's gradient."""
+        si, di = self.si, self.di
+        if si is not None:
+            grad = ops.si_combine(grad, si.weights, out=si.ghat if (out is None or di is not None) else out)
+        if di is not None:
+            grad = ops.di_adjoint(grad, di.geom, out=di.grad if out is None else out)
+        return grad
 
-def _fgm_update(x, grad, eps, norm, clip_min, clip_max, flag=None, out=None, check_range=True, mom=None, ti=None,
-                di=None, si=None, vt=None):
-    """``flag``: range violations of ``x`` (``check_range``) and, for the L2 / L1 updates, the degenerate-gradient bit
-    that stands for the self-check asserts of the reference's ``optimize_linear`` (utils.py:101-104, :110-116).
-    ``mom``: accumulate ``grad`` into the momentum first and step along the momentum instead.
-    ``ti``: smooth ``grad`` first (TI-FGSM; with momentum the smoothed gradient is what gets normalised and accumulated,
-    TI-MI-FGSM); the plain L-inf update does both in one launch.
-    ``di``: ``grad`` is the gradient at the TRANSFORMED image (DI-FGSM): the transform's adjoint takes it back to ``x``
-    first, in the same launch for the plain L-inf update, in front of smoothing / momentum / L2 otherwise.
-    ``si``: ``grad`` is the LIST of the scale copies' gradients (SI-NI-FGSM): their weighted sum comes first of all, in
-    the same launch for the plain L-inf update, into a scratch in front of the rest of the chain otherwise.
-    ``vt``: ``grad`` is ``G(p)`` of ``_evaluate_vt``, in x space already (``si`` / ``di`` are done with): the tune step
-    comes first, in the same launch for the plain L-inf update, in front of smoothing / momentum / L2 otherwise."""
-    if vt is not None:
-        if vt.plain and ti is None and mom is None and norm == np.inf:
-            return ops.linf_vt_step(x, grad, vt.vsum, vt.v[vt.kind], None, vt.w, eps, 0.0, clip_min, clip_max,
-                                    flag=flag if check_range else None, out=out)
-        grad, si, di = vt.tune(grad), None, None
-    if si is not None:
-        if di is None and ti is None and mom is None and norm == np.inf:
-            return ops.linf_si_step(x, grad, None, si.weights, eps, 0.0, clip_min, clip_max,
-                                    flag=flag if check_range else None, out=out)
-        grad = si.combine(grad)
-    if di is not None:
-        if ti is None and mom is None and norm == np.inf:
-            return ops.linf_di_step(x, grad, None, di.geom, eps, 0.0, clip_min, clip_max,
-                                    flag=flag if check_range else None, out=out)
-        grad = di.adjoint(grad)
-    if ti is not None:
-        if mom is None and norm == np.inf:
-            return ops.linf_ti_step(x, grad, None, ti.taps, eps, 0.0, clip_min, clip_max,
-                                    flag=flag if check_range else None, out=out)
-        grad = ti.smooth(grad)
-    if mom is not None and norm == np.inf:
-        return ops.linf_momentum_step(x, grad, None, mom.m, mom.decay, eps, 0.0, clip_min, clip_max,
-                                      flag=flag if check_range else None, out=out, sumabs=mom.sums(grad))
-    if mom is not None:
-        grad = ops.momentum_accumulate(grad, mom.m, mom.decay, sumabs=mom.sums(grad))
-    if norm == np.inf:
-        return ops.linf_fgm(x, grad, eps, clip_min, clip_max, flag=flag if check_range else None, out=out)
-    if norm == 2:
-        return ops.l2_fgm(x, grad, eps, clip_min, clip_max, flag=flag, out=out, check_range=check_range)
-    return ops.l1_fgm(x, grad, eps, clip_min, clip_max, flag=flag, out=out, check_range=check_range)
+    def evaluate(self, adv, call, kind=0, advance=True):
+        """One gradient evaluation at ``adv`` in the form ``update`` expects.  Without variance tuning: ``_gradient``.
+        With it: the centre through ``_gradient``, then the ``vt.n`` neighbours ``p + r_i`` (``p`` the look-ahead point with
+        Nesterov) in chunks of at most 8 images per launch through the same ``_gradient``, every one with the centre's DI
+        rows and ``call(leaf, False)`` (their losses go to the scratch word).  Without SI / DI up to 8 leaf gradients are
+        summed per launch; with either each neighbour's gradient is combined / adjoint-ed into its scratch and summed one
+        at a time -- the same bits.  Leaves ``sum_i G(p + r_i)`` in ``vt.vsum`` and returns ``G(p)``, in x space; ``kind``
+        selects the variance the update tunes."""
+        si, vt = self.si, self.vt
+        if vt is None:
+            return self._gradient(adv, call, advance)
+        if advance:
+            vt.use(vt.t)
+            vt.t += 1
+        vt.kind = kind
+        g = self._x_gradient(self._gradient(adv, call, advance), out=vt.ghat)
+        m, lookahead = (si.mom.m, si.lookahead) if si is not None and si.mom is not None else (None, 0.0)
 
+        def other(leaf, _):
+            call(leaf, False)
 
-def _fgm_then_project(x, grad, x0, eps_iter, eps, norm, clip_min, clip_max, out, flag=None, mom=None, ti=None,
-                      di=None, si=None, vt=None):
-    if vt is not None:
-        if vt.plain and ti is None and mom is None and norm == np.inf:
-            return ops.linf_vt_step(x, grad, vt.vsum, vt.v[vt.kind], x0, vt.w, eps_iter, eps, clip_min, clip_max, out=out)
-        grad, si, di = vt.tune(grad), None, None
-    if si is not None:
-        if di is None and ti is None and mom is None and norm == np.inf:
-            return ops.linf_si_step(x, grad, x0, si.weights, eps_iter, eps, clip_min, clip_max, out=out)
-        grad = si.combine(grad)
-    if di is not None:
-        if ti is None and mom is None and norm == np.inf:
-            return ops.linf_di_step(x, grad, x0, di.geom, eps_iter, eps, clip_min, clip_max, out=out)
-        grad = di.adjoint(grad)
-    if ti is not None:
-        if mom is None and norm == np.inf:
-            return ops.linf_ti_step(x, grad, x0, ti.taps, eps_iter, eps, clip_min, clip_max, out=out)
-        grad = ti.smooth(grad)
-    if mom is not None and norm == np.inf:
-        return ops.linf_momentum_step(x, grad, x0, mom.m, mom.decay, eps_iter, eps, clip_min, clip_max, out=out,
-                                      sumabs=mom.sums(grad))
-    if mom is not None:
-        grad = ops.momentum_accumulate(grad, mom.m, mom.decay, sumabs=mom.sums(grad))
-    if norm == np.inf:
-        return ops.linf_step(x, grad, x0, eps_iter, eps, clip_min, clip_max, out=out)
-    mid = ops.l2_fgm(x, grad, eps_iter, clip_min, clip_max, flag=flag, check_range=False)
-    return ops.l2_project(mid, x0, eps, clip_min, clip_max, out=out)
+        for start in range(0, vt.n, ops.VT_MAX_CHUNK):
+            count = min(ops.VT_MAX_CHUNK, vt.n - start)
+            images = ops.vt_neighbors(adv, vt.key, count, vt.bound, first=start, m=m, lookahead=lookahead,
+                                      out=vt.chunk[:count])
+            grads = []
+            for c in range(count):
+                gn = self._gradient(images[c], other, advance=False, ahead=False)
+                if self.plain:
+                    grads.append(gn)
+                else:
+                    ops.vt_accumulate([self._x_gradient(gn)], vt.vsum, init=start + c == 0)
+            if grads:
+                ops.vt_accumulate(grads, vt.vsum, init=start == 0)
+        return g
+
+    def update(self, x, grad, x0, eps_iter, eps, clip_min, clip_max, out=None, flag=None, check_range=True, rows=None):
+        """One image update along ``grad`` (what ``evaluate`` returned).  ``x0=None`` is the FGM form, ``x + eps_iter *
+        direction`` clamped; otherwise the step form, projected onto the ``eps``-ball around ``x0`` as well.
+        ``flag``: the FGM form reports range violations of ``x`` there (``check_range``) and, for L2 / L1, the
+        degenerate-gradient bit that stands for the self-check asserts of the reference's ``optimize_linear``
+        (utils.py:101-104, :110-116); the step form's L2 update reports the degenerate bit only.
+        ``rows=(lo, hi)``: the update of that run of samples -- ``x``, ``grad``, ``x0``, ``out`` and the state are sliced."""
+        cut = (lambda t: t) if rows is None else (lambda t: t[rows[0]:rows[1]])
+        fgm = x0 is None
+        x, x0, out = cut(x), None if fgm else cut(x0), None if out is None else cut(out)
+        grad = [cut(g) for g in grad] if isinstance(grad, list) else cut(grad)
+        step = (eps_iter, 0.0 if fgm else eps, clip_min, clip_max)
+        tail = dict(flag=flag if fgm and check_range else None, out=out)     # what every L-inf kernel takes last
+        si, di, vt, ti, mom = self.si, self.di, self.vt, self.ti, self.mom
+        if vt is not None:            # ``grad`` is G(p), in x space already: SI and DI are done with
+            if self.fused == "vt":
+                return ops.linf_vt_step(x, grad, vt.vsum, vt.v[vt.kind], x0, vt.w, *step, **tail)
+            grad = ops.vt_tune(grad, vt.vsum, vt.v[vt.kind], vt.w, out=vt.ghat)
+        else:
+            if self.fused == "si":
+                return ops.linf_si_step(x, grad, x0, si.weights, *step, **tail)
+            if si is not None:
+                grad = ops.si_combine(grad, si.weights, out=cut(si.ghat))
+            if self.fused == "di":
+                return ops.linf_di_step(x, grad, x0, cut(di.geom), *step, **tail)
+            if di is not None:
+                grad = ops.di_adjoint(grad, cut(di.geom), out=cut(di.grad))
+        if self.fused == "ti":
+            return ops.linf_ti_step(x, grad, x0, ti.taps, *step, **tail)
+        if ti is not None:
+            grad = ops.ti_smooth(grad, ti.taps, out=cut(ti.ghat))
+        if mom is not None:
+            # a run of samples leaves the |grad| sums to the kernel's wrapper: the call's reduction workspace is sized for
+            # the whole batch, and a smaller batch may need a larger one (vqa_reduce_ws_bytes)
+            sums = mom.sums(grad) if rows is None else None
+            if self.fused == "mom":
+                return ops.linf_momentum_step(x, grad, x0, cut(mom.m), mom.decay, *step, sumabs=sums, **tail)
+            grad = ops.momentum_accumulate(grad, cut(mom.m), mom.decay, sumabs=sums)
+        if self.norm == np.inf:
+            if fgm:
+                return ops.linf_fgm(x, grad, eps_iter, clip_min, clip_max, **tail)
+            return ops.linf_step(x, grad, x0, *step, **tail)
+        if fgm:
+            l_fgm = ops.l2_fgm if self.norm == 2 else ops.l1_fgm
+            return l_fgm(x, grad, eps_iter, clip_min, clip_max, flag=flag, out=out, check_range=check_range)
+        mid = ops.l2_fgm(x, grad, eps_iter, clip_min, clip_max, flag=flag, check_range=False)
+        return ops.l2_project(mid, x0, eps, clip_min, clip_max, out=out)
 
 
 def _check_flag(flag, norm, sanity_checks):
@@ -756,26 +729,23 @@ def fast_gradient_method(model_fn, x, eps, norm, ori_x, clip_min=None, clip_max=
     Reference: A fast_gradient_method.py:30-165, V :36-152 (the VLMO copy has no ``bkp``/``bkp_y``)."""
     _check_flavor(flavor)
     _validate_fgm(norm, eps, clip_min, clip_max)
-    taps = _validate_ti(ti_kernel)
-    spec = _validate_di(diversity_prob, di_shrink, di_rng)
-    sspec = _validate_si(si_copies)
+    specs = _validate_stages(ti_kernel=ti_kernel, diversity_prob=diversity_prob, di_shrink=di_shrink, di_rng=di_rng,
+                             si_copies=si_copies)
     if eps == 0:
         return x
     xin = _as_image(x)
     check_range = sanity_checks and (clip_min is not None or clip_max is not None)
     flag = ops.new_flag(xin.device) if (check_range or norm != np.inf) else None
-    di = _diversity(spec, xin, 1, norm, None, taps)
-    ti = _smoother(taps, xin, norm, None)
-    si = _scales(sspec, xin, eps, norm, None, ti, di)
+    chain = _Chain(specs, xin, norm, eps, eps)
     loss_buf = torch.zeros(1, dtype=torch.float32, device=xin.device)
 
     def call(leaf, first):      # without DI / SI the leaf shares storage with x: nothing is written in place
-        _loss_and_grad(model_fn, [leaf], leaf, y, ls, flavor, targeted, _LossSlot(loss_buf, 0) if first else si.slot,
+        _loss_and_grad(model_fn, [leaf], leaf, y, ls, flavor, targeted, _LossSlot(loss_buf, 0) if first else chain.slot,
                        bkp=bkp, bkp_y=bkp_y, flag=flag, per_sample=per_sample)
 
-    _, grad = _evaluate(xin, si, di, call)
+    grad = chain.evaluate(xin, call)
     _two_sided(clip_min, clip_max)
-    adv = _fgm_update(xin, grad, eps, norm, clip_min, clip_max, flag=flag, check_range=check_range, ti=ti, di=di, si=si)
+    adv = chain.update(xin, grad, None, eps, eps, clip_min, clip_max, flag=flag, check_range=check_range)
     assert _check_flag(flag, norm, sanity_checks), "input x is outside [clip_min, clip_max]"
     return adv, loss_buf[0]
 
@@ -793,18 +763,15 @@ def fast_gradient_method_vl(model_fn, x, eps, norm, ori_x, clip_min=None, clip_m
     Reference: A fast_gradient_method_vl.py:30-130, V :34-141."""
     _check_flavor(flavor)
     _validate_fgm(norm, eps, clip_min, clip_max)
-    taps = _validate_ti(ti_kernel)
-    spec = _validate_di(diversity_prob, di_shrink, di_rng)
-    sspec = _validate_si(si_copies)
+    specs = _validate_stages(ti_kernel=ti_kernel, diversity_prob=diversity_prob, di_shrink=di_shrink, di_rng=di_rng,
+                             si_copies=si_copies)
     if eps == 0:
         return x
     img = _as_image(x[0], "x[0]")
     emb = _as_image(x[1], "x[1]")
     check_range = sanity_checks and (clip_min is not None or clip_max is not None)
     flag = ops.new_flag(img.device) if (check_range or norm != np.inf) else None
-    di = _diversity(spec, img, 1, norm, None, taps)
-    ti = _smoother(taps, img, norm, None)
-    si = _scales(sspec, img, eps, norm, None, ti, di)
+    chain = _Chain(specs, img, norm, eps, eps)
     x[1] = emb.detach().requires_grad_(True)
     loss_buf = torch.zeros(1, dtype=torch.float32, device=img.device)
 
@@ -813,12 +780,12 @@ def fast_gradient_method_vl(model_fn, x, eps, norm, ori_x, clip_min=None, clip_m
             x[0] = leaf
             _loss_and_grad(model_fn, [leaf, x[1]], [leaf, x[1]], y, ls, flavor, targeted, _LossSlot(loss_buf, 0), vl=True)
         else:
-            _loss_and_grad(model_fn, [leaf], [leaf, emb.detach()], y, ls, flavor, targeted, si.slot, vl=True)
+            _loss_and_grad(model_fn, [leaf], [leaf, emb.detach()], y, ls, flavor, targeted, chain.slot, vl=True)
 
-    _, grad = _evaluate(img, si, di, call)
+    grad = chain.evaluate(img, call)
     text_grad = ops.gather_rows(_grad_of(x[1]), text_emb_pick)
     _two_sided(clip_min, clip_max)
-    adv = _fgm_update(img, grad, eps, norm, clip_min, clip_max, flag=flag, check_range=check_range, ti=ti, di=di, si=si)
+    adv = chain.update(img, grad, None, eps, eps, clip_min, clip_max, flag=flag, check_range=check_range)
     assert _check_flag(flag, norm, sanity_checks), "input x is outside [clip_min, clip_max]"
     return adv, text_grad
 
@@ -852,7 +819,7 @@ def _finish(flag, eps, eps_iter, norm, clip_min, clip_max, sanity_checks):
 
 
 def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, clip_min, clip_max, nb_iter, loss_buf,
-                       mom=None, ti=None, di=None, si=None, vt=None):
+                       chain):
     """``nb_iter`` feature-loss L-inf iterations with iterations 1.. replayed from ONE captured hipGraph.
 
     For the launch-bound regime (the reference's own batch 1: ~10^3 kernels of a few microseconds per iteration):
@@ -862,41 +829,28 @@ def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, cl
     iteration is the 4-byte copy of the loss word into its slot of the loss buffer.
     ``model_fn`` must be capturable: no host<->device copies or host RNG inside (ALBEF's per-forward token masking
     is not; use ``mlm_probability=0`` or eager mode there).
-    ``mom``: the |grad| reduction and the fused momentum step take the place of the step inside the captured iteration;
-    the momentum, the per-sample sums and the reduction's workspace were allocated before capture.
-    ``ti``: the fused TI step (or smoothing + reduction + momentum step) is what the iteration captures; the taps travel in
-    the kernel arguments and the smoothed-gradient scratch was allocated before capture.
-    ``di``: the transform and the fused DI step (or the adjoint in front of the rest) are captured against the static
+    ``chain`` (``_Chain``, L-inf): whatever its stages launch is captured with the iteration, and all of their state was
+    allocated before capture.  Momentum: the |grad| reduction and the fused momentum step take the place of the step.
+    TI: the taps travel in the kernel arguments.  DI: the transform and the adjoint are captured against the static
     geometry row; a device-to-device copy of the iteration's rows into it precedes each replay (eager, like the loss word).
-    ``si``: the copies launch, one model call per copy and the combining update are captured; the copies and the scratch
-    were allocated before capture, and the gradients' addresses, which travel by value in the kernel arguments, are the
-    graph's own and the same at every replay.
-    ``vt``: the neighbour launches, their model calls, the sums and the tuned update are captured against the static key
-    row; a device-to-device copy of the iteration's key (seed and ``t``) into it precedes each replay, like DI's rows, so
-    that every replay draws fresh numbers from the same captured launches.
+    SI: the gradients' addresses, which travel by value in the kernel arguments, are the graph's own and the same at every
+    replay.  VT: the neighbour launches are captured against the static key row; a copy of the iteration's key (seed and
+    ``t``) into it precedes each replay, like DI's rows, so that every replay draws fresh numbers from the same launches.
     """
     word = torch.zeros(1, dtype=torch.float32, device=cur.device)
-    scratch = _scratch_slot(si, vt)
 
     def call(leaf, first):
-        _loss_and_grad(model_fn, [leaf], leaf, y, 1, flavor, targeted, _LossSlot(word, 0) if first else scratch)
+        _loss_and_grad(model_fn, [leaf], leaf, y, 1, flavor, targeted, _LossSlot(word, 0) if first else chain.slot)
 
     def iteration():
-        if vt is None:
-            _, grad = _evaluate(cur, si, di, call, advance=False)
-        else:
-            _, grad = _evaluate_vt(cur, si, di, vt, call, advance=False)
-        _fgm_then_project(cur, grad, x0, eps_iter, eps, np.inf, clip_min, clip_max, cur,   # in place: static address
-                          mom=mom, ti=ti, di=di, si=si, vt=vt)
+        grad = chain.evaluate(cur, call, advance=False)
+        chain.update(cur, grad, x0, eps_iter, eps, clip_min, clip_max, out=cur)       # in place: static address
 
     main = torch.cuda.current_stream(cur.device)
     side = torch.cuda.Stream(device=cur.device)
     side.wait_stream(main)
     with torch.cuda.stream(side):
-        if di is not None:
-            di.use(0, static=True)
-        if vt is not None:
-            vt.use(0, static=True)
+        chain.use(0, static=True)
         iteration()
         loss_buf[0:1].copy_(word)
     main.wait_stream(side)
@@ -905,10 +859,7 @@ def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, cl
         with torch.cuda.graph(graph):
             iteration()
         for i in range(1, nb_iter):
-            if di is not None:
-                di.use(i, static=True)
-            if vt is not None:
-                vt.use(i, static=True)
+            chain.use(i, static=True)
             graph.replay()
             loss_buf[i:i + 1].copy_(word)
     return cur
@@ -988,11 +939,8 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
     """
     _check_flavor(flavor)
     unchanged = _validate_pgd(norm, eps, eps_iter, clip_min, clip_max)
-    decay = _validate_decay(decay_factor)
-    taps = _validate_ti(ti_kernel)
-    spec = _validate_di(diversity_prob, di_shrink, di_rng)
-    sspec = _validate_si(si_copies, nesterov, decay_factor)
-    vspec = _validate_vt(vt_neighbors, vt_beta, vt_seed)
+    specs = _validate_stages(decay_factor, ti_kernel, diversity_prob, di_shrink, di_rng, si_copies, nesterov,
+                             vt_neighbors, vt_beta, vt_seed)
     if unchanged:
         return x
     xin = _as_image(x)
@@ -1009,11 +957,8 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
     dual = ls != 1
     loss_buf = torch.zeros(max(nb_iter, 1) * (2 if dual else 1), dtype=torch.float32, device=xin.device)
     n_loss = 0
-    mom = None if decay is None else _Momentum(decay, xin, momentum)
-    ti = _smoother(taps, xin, norm, decay)
-    di = _diversity(spec, xin, nb_iter * (2 if dual else 1), norm, decay, taps, vt=vspec is not None)
-    si = _scales(sspec, xin, eps_iter, norm, mom, ti, di, vt=vspec is not None)
-    vt = _variance(vspec, xin, eps, nb_iter * (2 if dual else 1), kinds=2 if dual else 1)
+    chain = _Chain(specs, xin, norm, eps, eps_iter, nb_iter * (2 if dual else 1), kinds=2 if dual else 1,
+                   momentum=momentum)
     ws = ops.Workspace()       # loss-gradient / CE scratch buffers live for the whole call, not per iteration
     bad_flag = flag if flag is not None else (
         ops.new_flag(xin.device) if ((dual and sanity_checks) or norm != np.inf) else None)
@@ -1024,29 +969,25 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
             raise ValueError("graph=True supports the feature-loss (ls == 1) L-inf loop only")
         _two_sided(clip_min, clip_max)
         adv = _graphed_linf_loop(model_fn, adv, x0, y, flavor, targeted, eps_iter, eps, clip_min, clip_max, nb_iter,
-                                 loss_buf, mom=mom, ti=ti, di=di, si=si, vt=vt)
+                                 loss_buf, chain)
         n_loss, nb_iter = nb_iter, 0
-    scratch = _scratch_slot(si, vt)
 
     def evaluate(fn, at, y_, ls_, kind=0, **extra):
         """One gradient evaluation at ``at`` with the loss of copy 0 in the next slot of the loss buffer."""
         slot = _LossSlot(loss_buf, n_loss)
 
         def call(leaf, first):
-            _loss_and_grad(fn, [leaf], leaf, y_, ls_, flavor, targeted, slot if first else scratch, ws=ws,
+            _loss_and_grad(fn, [leaf], leaf, y_, ls_, flavor, targeted, slot if first else chain.slot, ws=ws,
                            flag=bad_flag, **extra)
 
-        if vt is not None:
-            return _evaluate_vt(at, si, di, vt, call, kind=kind)[1]
-        return _evaluate(at, si, di, call)[1]
+        return chain.evaluate(at, call, kind=kind)
 
     for _ in range(nb_iter):
         if not dual:
             grad = evaluate(model_fn, adv, y, ls)
             n_loss += 1
             _two_sided(clip_min, clip_max)
-            adv = _fgm_then_project(adv, grad, x0, eps_iter, eps, norm, clip_min, clip_max, buf[1 - cur],
-                                    flag=bad_flag, mom=mom, ti=ti, di=di, si=si, vt=vt)
+            adv = chain.update(adv, grad, x0, eps_iter, eps, clip_min, clip_max, out=buf[1 - cur], flag=bad_flag)
         else:
             if flavor == ALBEF:      # A :163,177-181 slices y; V :162,175 passes it whole
                 y_feat, y_mlm, extra = [y[1], y[2]], [y[0]], dict(bkp=model_fn[0], bkp_y=[y[1], y[2]])
@@ -1055,12 +996,11 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
             grad = evaluate(model_fn[0], adv, y_feat, 1)
             n_loss += 1
             _two_sided(clip_min, clip_max)
-            mid = _fgm_update(adv, grad, eps_iter, norm, clip_min, clip_max, out=buf[1 - cur], flag=bad_flag,
-                              check_range=False, mom=mom, ti=ti, di=di, si=si, vt=vt)
+            mid = chain.update(adv, grad, None, eps_iter, eps, clip_min, clip_max, out=buf[1 - cur], flag=bad_flag,
+                               check_range=False)
             grad = evaluate(model_fn[1], mid, y_mlm, 0, kind=1, per_sample=per_sample, **extra)
             n_loss += 1
-            adv = _fgm_then_project(mid, grad, x0, eps_iter, eps, norm, clip_min, clip_max, buf[cur],
-                                    flag=bad_flag, mom=mom, ti=ti, di=di, si=si, vt=vt)
+            adv = chain.update(mid, grad, x0, eps_iter, eps, clip_min, clip_max, out=buf[cur], flag=bad_flag)
             cur = 1 - cur            # result sits in buf[cur] again after the flip below
         cur = 1 - cur
         del grad
@@ -1088,11 +1028,8 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
     Reference: A projected_gradient_descent_vl.py:10-168, V :10-164."""
     _check_flavor(flavor)
     unchanged = _validate_pgd(norm, eps, eps_iter, clip_min, clip_max)
-    decay = _validate_decay(decay_factor)
-    taps = _validate_ti(ti_kernel)
-    spec = _validate_di(diversity_prob, di_shrink, di_rng)
-    sspec = _validate_si(si_copies, nesterov, decay_factor)
-    vspec = _validate_vt(vt_neighbors, vt_beta, vt_seed)
+    specs = _validate_stages(decay_factor, ti_kernel, diversity_prob, di_shrink, di_rng, si_copies, nesterov,
+                             vt_neighbors, vt_beta, vt_seed)
     if unchanged:
         return x
     img = _as_image(x[0], "x[0]")
@@ -1110,12 +1047,7 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
     text_grad = None
     loss_buf = torch.zeros(max(nb_iter, 1), dtype=torch.float32, device=img.device)
     ws = ops.Workspace()
-    mom = None if decay is None else _Momentum(decay, img, momentum)
-    ti = _smoother(taps, img, norm, decay)
-    di = _diversity(spec, img, nb_iter, norm, decay, taps, vt=vspec is not None)
-    si = _scales(sspec, img, eps_iter, norm, mom, ti, di, vt=vspec is not None)
-    vt = _variance(vspec, img, eps, nb_iter)
-    scratch = _scratch_slot(si, vt)
+    chain = _Chain(specs, img, norm, eps, eps_iter, nb_iter, momentum=momentum)
     if attack_mask is not None and not isinstance(attack_mask, ops.RowIndex):   # validated + uploaded once per call
         attack_mask = ops.RowIndex(attack_mask, emb.shape[1], emb.device)
     for it in range(nb_iter):
@@ -1127,14 +1059,13 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
                 _loss_and_grad(model_fn, [leaf_img, leaf_txt], [leaf_img, leaf_txt], y, ls, flavor, targeted, slot,
                                vl=True, ws=ws, flag=flag)
             else:
-                _loss_and_grad(model_fn, [leaf_img], [leaf_img, emb.detach()], y, ls, flavor, targeted, scratch, vl=True,
-                               ws=ws, flag=flag)
+                _loss_and_grad(model_fn, [leaf_img], [leaf_img, emb.detach()], y, ls, flavor, targeted, chain.slot,
+                               vl=True, ws=ws, flag=flag)
 
-        grad = (_evaluate(adv, si, di, call) if vt is None else _evaluate_vt(adv, si, di, vt, call))[1]
+        grad = chain.evaluate(adv, call)
         text_grad = ops.gather_rows(_grad_of(leaf_txt), attack_mask)
         _two_sided(clip_min, clip_max)
-        adv = _fgm_then_project(adv, grad, x0, eps_iter, eps, norm, clip_min, clip_max, buf[1 - cur],
-                                flag=flag, mom=mom, ti=ti, di=di, si=si, vt=vt)
+        adv = chain.update(adv, grad, x0, eps_iter, eps, clip_min, clip_max, out=buf[1 - cur], flag=flag)
         cur = 1 - cur
         del grad, leaf_txt
     _finish(flag, eps, eps_iter, norm, clip_min, clip_max, sanity_checks)

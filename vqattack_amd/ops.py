@@ -40,6 +40,24 @@ def _out_like(x, out):
     return out
 
 
+def _fused_step_args(x, g, x0, clip_min, clip_max, flag, out, also=(), what="grad"):
+    """What the fused L-inf steps (``linf_*_step``) share in front of their launch: ``x`` and ``x0`` (None: the FGM form)
+    checked, ``g`` -- checked by its own stage -- against their shape, every tensor (``also``: the stage's own) on one
+    device.  Returns ``(out, mode bits, cmin, cmax)``; with a ``flag`` and a clip range the mode asks for the range check."""
+    dev_f32(x, "x")
+    if x0 is not None:
+        dev_f32(x0, "ori_x")
+    if g.shape != x.shape or (x0 is not None and x0.shape != x.shape):
+        raise ValueError("shape mismatch: x {}, {} {}, ori_x {}".format(
+            tuple(x.shape), what, tuple(g.shape), None if x0 is None else tuple(x0.shape)))
+    same_device(x, g, x0, out, flag, *also)
+    out = _out_like(x, out)
+    mode, lo, hi = _clip_args(clip_min, clip_max)
+    if flag is not None and mode:
+        mode |= VQA_CHECK_RANGE
+    return out, mode, lo, hi
+
+
 def new_flag(device):
     """int32[1] device word the kernels OR range violations into (read once at the end of an attack)."""
     return torch.zeros(1, dtype=torch.int32, device=device)
@@ -327,18 +345,8 @@ def momentum_accumulate(g, m, decay, sumabs=None):
 def linf_momentum_step(x, g, x0, m, decay, eps_iter, eps, clip_min, clip_max, flag=None, out=None, sumabs=None):
     """``momentum_accumulate`` and ``linf_step`` on the new momentum in one pass, 24 B/element; ``x0=None``: and
     ``linf_fgm`` (no projection), 20 B/element.  ``m`` is updated in place; ``out`` may be ``x``."""
-    dev_f32(x, "x")
-    if x0 is not None:
-        dev_f32(x0, "ori_x")
-    if g.shape != x.shape or (x0 is not None and x0.shape != x.shape):
-        raise ValueError("shape mismatch: x {}, grad {}, ori_x {}".format(
-            tuple(x.shape), tuple(g.shape), None if x0 is None else tuple(x0.shape)))
-    same_device(x, g, x0, out, flag)
+    out, mode, lo, hi = _fused_step_args(x, g, x0, clip_min, clip_max, flag, out)
     sumabs = _momentum_args(g, m, sumabs)
-    out = _out_like(x, out)
-    mode, lo, hi = _clip_args(clip_min, clip_max)
-    if flag is not None and mode:
-        mode |= VQA_CHECK_RANGE
     if x.numel() == 0:
         return out
     batch, n_per = _per_sample(x)
@@ -398,19 +406,9 @@ def ti_smooth(g, taps, out=None):
 def linf_ti_step(x, g, x0, taps, eps_iter, eps, clip_min, clip_max, flag=None, out=None):
     """``ti_smooth`` and ``linf_step`` on the smoothed gradient in one pass, 16 B/element; ``x0=None``: and ``linf_fgm``
     (no projection), 12 B/element.  The smoothed gradient never reaches memory; ``out`` may be ``x``."""
-    dev_f32(x, "x")
-    if x0 is not None:
-        dev_f32(x0, "ori_x")
     planes, h, w = _ti_planes(g)
-    if g.shape != x.shape or (x0 is not None and x0.shape != x.shape):
-        raise ValueError("shape mismatch: x {}, grad {}, ori_x {}".format(
-            tuple(x.shape), tuple(g.shape), None if x0 is None else tuple(x0.shape)))
-    same_device(x, g, x0, out, flag)
     buf, k = _ti_taps(taps)
-    out = _out_like(x, out)
-    mode, lo, hi = _clip_args(clip_min, clip_max)
-    if flag is not None and mode:
-        mode |= VQA_CHECK_RANGE
+    out, mode, lo, hi = _fused_step_args(x, g, x0, clip_min, clip_max, flag, out)
     if x.numel() == 0:
         return out
     with _on(x):
@@ -509,18 +507,8 @@ def di_adjoint(gd, geom, out=None):
 def linf_di_step(x, gd, x0, geom, eps_iter, eps, clip_min, clip_max, flag=None, out=None):
     """``di_adjoint`` and ``linf_step`` on its result in one pass, at most 16 B/element; ``x0=None``: and ``linf_fgm`` (no
     projection).  The image gradient never reaches memory; ``out`` may be ``x``."""
-    dev_f32(x, "x")
-    if x0 is not None:
-        dev_f32(x0, "ori_x")
     b, c, h, w = _di_args(gd, geom, "grad")
-    if gd.shape != x.shape or (x0 is not None and x0.shape != x.shape):
-        raise ValueError("shape mismatch: x {}, grad {}, ori_x {}".format(
-            tuple(x.shape), tuple(gd.shape), None if x0 is None else tuple(x0.shape)))
-    same_device(x, gd, x0, geom, out, flag)
-    out = _out_like(x, out)
-    mode, lo, hi = _clip_args(clip_min, clip_max)
-    if flag is not None and mode:
-        mode |= VQA_CHECK_RANGE
+    out, mode, lo, hi = _fused_step_args(x, gd, x0, clip_min, clip_max, flag, out, also=(geom,))
     if x.numel() == 0:
         return out
     with _on(x):
@@ -619,18 +607,8 @@ def si_combine(grads, weights, out=None):
 def linf_si_step(x, grads, x0, weights, eps_iter, eps, clip_min, clip_max, flag=None, out=None):
     """``si_combine`` and ``linf_step`` on its result in one pass, 4 * copies + 12 B/element; ``x0=None``: and
     ``linf_fgm`` (no projection).  The combined gradient never reaches memory; ``out`` may be ``x``."""
-    dev_f32(x, "x")
-    if x0 is not None:
-        dev_f32(x0, "ori_x")
     pbuf, wbuf, copies = _si_grads(grads, weights)
-    if grads[0].shape != x.shape or (x0 is not None and x0.shape != x.shape):
-        raise ValueError("shape mismatch: x {}, grads {}, ori_x {}".format(
-            tuple(x.shape), tuple(grads[0].shape), None if x0 is None else tuple(x0.shape)))
-    same_device(x, grads[0], x0, out, flag)
-    out = _out_like(x, out)
-    mode, lo, hi = _clip_args(clip_min, clip_max)
-    if flag is not None and mode:
-        mode |= VQA_CHECK_RANGE
+    out, mode, lo, hi = _fused_step_args(x, grads[0], x0, clip_min, clip_max, flag, out, what="grads")
     if x.numel() == 0:
         return out
     with _on(x):
@@ -755,18 +733,8 @@ def vt_tune(g, vsum, v, w, out=None):
 def linf_vt_step(x, g, vsum, v, x0, w, eps_iter, eps, clip_min, clip_max, flag=None, out=None):
     """``vt_tune`` and ``linf_step`` on its result in one pass, 28 B/element; ``x0=None``: and ``linf_fgm`` (no
     projection).  The tuned gradient never reaches memory; ``v`` is updated in place; ``out`` may be ``x``."""
-    dev_f32(x, "x")
-    if x0 is not None:
-        dev_f32(x0, "ori_x")
     _vt_state(g, vsum, v)
-    if g.shape != x.shape or (x0 is not None and x0.shape != x.shape):
-        raise ValueError("shape mismatch: x {}, grad {}, ori_x {}".format(
-            tuple(x.shape), tuple(g.shape), None if x0 is None else tuple(x0.shape)))
-    same_device(x, g, vsum, v, x0, out, flag)
-    out = _out_like(x, out)
-    mode, lo, hi = _clip_args(clip_min, clip_max)
-    if flag is not None and mode:
-        mode |= VQA_CHECK_RANGE
+    out, mode, lo, hi = _fused_step_args(x, g, x0, clip_min, clip_max, flag, out, also=(vsum, v))
     if x.numel() == 0:
         return out
     with _on(x):
