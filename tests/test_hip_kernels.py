@@ -45,7 +45,8 @@ def _same_bits(a, b):
     return np.array_equal(a, b)
 
 
-SHAPES = [(4, 3, 384, 384), (2, 3, 32, 32), (1, 3, 5, 7), (3, 1, 1, 1), (1, 1, 1, 2)]
+# (11276,): 2819 16-byte pieces = 2048 + 512 + 256 + 3, a partial tile of 3 whole slots and 3 lanes at 4 slots per tile
+SHAPES = [(4, 3, 384, 384), (2, 3, 32, 32), (1, 3, 5, 7), (11276,), (3, 1, 1, 1), (1, 1, 1, 2)]
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=[str(s) for s in SHAPES])
@@ -93,7 +94,7 @@ def test_linf_unaligned_views_take_scalar_path():
     assert _same_bits(out, want)
 
 
-@pytest.mark.parametrize("shape", SHAPES[:3], ids=[str(s) for s in SHAPES[:3]])
+@pytest.mark.parametrize("shape", SHAPES[:4], ids=[str(s) for s in SHAPES[:4]])
 def test_linf_fgm_init_project_bitexact(shape):
     ops = _ops()
     x0 = _rand(shape, 10)

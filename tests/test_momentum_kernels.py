@@ -21,7 +21,9 @@ DEV = "cuda:0"
 NORM_RTOL = 2e-6          # the project's bar on per-sample norms vs fp64; the two-stage fp32 sum emulated on the CPU for
 #                           1..108 chunks is off by at most 3.1e-7 at 3 * 384 * 384 normal draws (about 6x room)
 SMALL = ["3x3x5x7", "2x3x64x64", "2x4100", "offset"]
-_SHAPES = {"3x3x5x7": (3, 3, 5, 7), "2x3x64x64": (2, 3, 64, 64), "2x4100": (2, 4100), "offset": (2, 4100)}
+PARTIAL = SMALL + ["2x11276"]          # 2819 16-byte pieces per row: a partial tile with whole slots and 3 lanes
+_SHAPES = {"3x3x5x7": (3, 3, 5, 7), "2x3x64x64": (2, 3, 64, 64), "2x4100": (2, 4100), "offset": (2, 4100),
+           "2x11276": (2, 11276)}
 _cache = {}
 
 
@@ -107,7 +109,7 @@ def _chain(g, m, sumabs, decay):
 
 
 @pytest.mark.parametrize("decay", [1.0, 0.9, 0.0])
-@pytest.mark.parametrize("name", SMALL)
+@pytest.mark.parametrize("name", PARTIAL)
 def test_accumulate_equals_the_numpy_fp32_chain_bitwise(name, decay):
     from vqattack_amd import ops
     host, dev = _data(name)
@@ -145,7 +147,7 @@ def _two_launches(ops, t, m, decay, sums, with_x0, clip, out=None, flag=None):
 @pytest.mark.parametrize("in_place", [False, True])
 @pytest.mark.parametrize("clip", [True, False])
 @pytest.mark.parametrize("with_x0", [True, False])
-@pytest.mark.parametrize("name", SMALL)
+@pytest.mark.parametrize("name", PARTIAL)
 def test_fused_step_equals_accumulate_then_linf_kernel_bitwise(name, with_x0, clip, in_place):
     from vqattack_amd import ops
     host, dev = _data(name)

@@ -23,10 +23,11 @@ F = np.float32
 EPS_ITER, EPS, LO, HI = 0.01, 0.05, -1.0, 1.0
 LOOKAHEAD = 0.009
 SMALL = ["3x3x5x7", "2x3x64x64", "2x4100", "offset", "one_off"]
+PARTIAL = SMALL + ["2x11276"]          # 2819 16-byte pieces per row: a partial tile with whole slots and 3 lanes
 COPIES = [1, 2, 5, 8]
 FLAT = 256 * 12 * 2048 + 5 * 2048 + 1036          # > grid x the larger tile (2 x 256 pieces of 4 floats), partial tile
 _SHAPES = {"3x3x5x7": (3, 3, 5, 7), "2x3x64x64": (2, 3, 64, 64), "2x4100": (2, 4100), "offset": (2, 4100),
-           "one_off": (2, 4100), "flat": (FLAT,)}
+           "one_off": (2, 4100), "flat": (FLAT,), "2x11276": (2, 11276)}
 _cache = {}
 
 
@@ -161,7 +162,7 @@ def test_copies_into_the_prefix_of_a_larger_buffer():
 
 # ------------------------------------------------------------------------------------------------ combine
 @pytest.mark.parametrize("copies", COPIES)
-@pytest.mark.parametrize("name", SMALL)
+@pytest.mark.parametrize("name", PARTIAL)
 def test_combine_equals_the_numpy_fp32_chain_bitwise_and_stays_inside_the_fp64_bound(name, copies):
     """Against float64: the fp32 chain makes one rounding per product and one per add, `copies` products and
     `copies - 1` adds; every intermediate is at most S = sum_i |w_i * g_i| (1 + O(2^-24)) in magnitude, so each rounding
@@ -206,7 +207,7 @@ def test_one_copy_of_weight_one_is_the_identity(name):
 @pytest.mark.parametrize("in_place", [False, True])
 @pytest.mark.parametrize("with_x0", [True, False])
 @pytest.mark.parametrize("copies", COPIES)
-@pytest.mark.parametrize("name", SMALL)
+@pytest.mark.parametrize("name", PARTIAL)
 def test_fused_step_equals_the_numpy_chain_and_the_two_launches_bitwise(name, copies, with_x0, in_place):
     from vqattack_amd import ops
     host, dev = _data(name)

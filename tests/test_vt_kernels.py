@@ -29,10 +29,11 @@ LOOKAHEAD = 0.009
 BOUND = float(F(1.5 * EPS))
 SEED = 0x9E3779B97F4A7C15
 SMALL = ["3x3x5x7", "2x3x64x64", "2x4100", "offset", "one_off"]
+PARTIAL = SMALL + ["2x11276"]          # 2819 16-byte pieces per row: a partial tile with whole slots and 3 lanes
 COUNTS = [1, 3, 8]
 FLAT = 256 * 12 * 2048 + 5 * 2048 + 1036          # > grid x the larger tile (2 x 256 pieces of 4 floats), partial tile
 _SHAPES = {"3x3x5x7": (3, 3, 5, 7), "2x3x64x64": (2, 3, 64, 64), "2x4100": (2, 4100), "offset": (2, 4100),
-           "one_off": (2, 4100), "flat": (FLAT,)}
+           "one_off": (2, 4100), "flat": (FLAT,), "2x11276": (2, 11276)}
 _cache = {}
 M0, M1, W0, W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 MASK = np.uint64(0xFFFFFFFF)
@@ -233,7 +234,7 @@ def test_neighbors_into_the_prefix_of_a_larger_buffer():
 # ------------------------------------------------------------------------------------------------ accumulate
 @pytest.mark.parametrize("init", [True, False])
 @pytest.mark.parametrize("count", COUNTS)
-@pytest.mark.parametrize("name", SMALL)
+@pytest.mark.parametrize("name", PARTIAL)
 def test_accumulate_equals_the_numpy_chain_bitwise_however_grouped(name, count, init):
     from vqattack_amd import ops
     host, dev = _data(name)
@@ -286,7 +287,7 @@ def test_tune_equals_the_numpy_chain_bitwise_and_the_variance_stays_inside_the_f
 
 @pytest.mark.parametrize("in_place", [False, True])
 @pytest.mark.parametrize("with_x0", [True, False])
-@pytest.mark.parametrize("name", SMALL)
+@pytest.mark.parametrize("name", PARTIAL)
 def test_fused_step_equals_the_numpy_chain_and_the_two_launches_bitwise(name, with_x0, in_place):
     from vqattack_amd import ops
     host, dev = _data(name)

@@ -30,7 +30,7 @@ KERNEL_SOURCES = (("stream4_kernel", "linf.hip"), ("neg_cos_rows", "loss.hip"), 
 
 
 def kernel_source_digest(kernel_name):
-    """sha256 over the source file a kernel is compiled from + the shared headers (``common.hpp``, ``gelu.hpp``) + the
+    """sha256 over the source file a kernel is compiled from + the shared headers (``common.hpp``, ``gelu.hpp``, ``stream.hpp``) + the
     C-ABI header + the compiler flags: changes whenever that kernel's code object can have changed.  None for a kernel
     this table does not know."""
     import hashlib
@@ -39,7 +39,7 @@ def kernel_source_digest(kernel_name):
         return None
     h = hashlib.sha256(" ".join(FLAGS).encode())
     for path in (os.path.join(SRC_DIR, src), os.path.join(SRC_DIR, "common.hpp"), os.path.join(SRC_DIR, "gelu.hpp"),
-                 os.path.join(HERE, "..", "include", "vqattack_hip.h")):
+                 os.path.join(SRC_DIR, "stream.hpp"), os.path.join(HERE, "..", "include", "vqattack_hip.h")):
         with open(path, "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()

@@ -1,28 +1,18 @@
 // L-infinity image-update kernels of the PGD loop (gfx950 / MI355X).
 //
-// All kernels here are pure HBM streams (arithmetic intensity < 0.5 flop/B): one 16-byte load per lane per
-// stream, U tiles in flight per wave before the first use, 256-thread workgroups, a grid capped at
-// 8 workgroups per CU that grid-strides over block-contiguous tiles.  No LDS, no MFMA: there is no reuse to
-// stage and no contraction.  The arithmetic is the reference's op chain in its exact fp32 order (see
-// include/vqattack_hip.h), compiled with -ffp-contract=off, so results are bit-identical to eager PyTorch.
-#include "common.hpp"
+// All kernels here are pure HBM streams on the tile loop of stream.hpp.  The arithmetic is the reference's op chain in its
+// exact fp32 order (see include/vqattack_hip.h), compiled with -ffp-contract=off, so results are bit-identical to eager
+// PyTorch.
+#include "stream.hpp"
 
 namespace vqa {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // ---- launch shape (VQA_KNOB: compile-time constants in the shipped library, see common.hpp)
-// option 0: workgroups per CU in the grid.  The step kernel keeps 6 workgroups resident per CU (76 registers: all 12
-// loads of a tile in flight): 12 = two whole rounds.  profiles/r06/step/step_ab.jsonl (tools/step_ab.py, alternating):
-// batch 64 warm / after a cache flush 68.8 / 83.8 us at 12, 68.9 / 85.4 at 8 (previous build 69.6 / 87.0); batch 256
-// 315.7 / 320.5 at 12, 318.4 / 321.7 at 8 (previous build 316.4 / 320.5) -- the memory system's ceiling either way.
-VQA_KNOB g_opt_blocks_per_cu = 12;
+VQA_KNOB g_opt_blocks_per_cu = kStreamBlocksPerCu;   // option 0: workgroups per CU in the grid (stream.hpp)
 // option 1: bit0 = nt loads of the second stream (the gradient: read exactly once), bit1 = nt stores of the result,
 // bit2 = nt loads of the first and third stream (x, x0), bit3 = nt stores only when the result is larger than the
-// 256 MB Infinity Cache (a smaller result is re-read from the cache by the white box's next forward; a larger one
-// cannot stay resident anyway and the plain-store allocation only costs bandwidth: tools/stream_probe, +10 % at 1.8 GB)
+// Infinity Cache (kInfinityCacheBytes, stream.hpp)
 VQA_KNOB g_opt_nontemporal = 1 | 4 | 8;
-constexpr size_t kNtStoreBytes = 256ull << 20;
 VQA_KNOB g_opt_unroll = 4;          // option 2: 16-byte tiles in flight per lane and stream (2, 4 or 8)
 VQA_KNOB g_opt_chunked = 0;         // option 3: 0 = grid-stride tiles, 1 = one contiguous chunk per workgroup
 
@@ -76,6 +66,29 @@ struct SignScaleOp {
 // ---- 16-byte streaming kernel -----------------------------------------------------------------
 // NT bit0: the second stream (the gradient, read exactly once) is loaded non-temporally;
 // NT bit1: the result is stored non-temporally; NT bit2: the first and third stream are loaded non-temporally.
+template <class Op, int NT>
+struct Stream4Tile {
+  const f32x4* s0;
+  const f32x4* s1;
+  const f32x4* s2;
+  f32x4* out;
+  StepParams p;
+  struct Slot {
+    f32x4 v0, v1 = {}, v2 = {};
+  };
+  __device__ __forceinline__ void load(Slot& s, size_t i) const {
+    s.v0 = ld4<4, NT>(s0 + i);
+    if (Op::kIn > 1) s.v1 = ld4<1, NT>(s1 + i);
+    if (Op::kIn > 2) s.v2 = ld4<4, NT>(s2 + i);
+  }
+  __device__ __forceinline__ void compute(Slot& s, bool& bad) const {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s.v0[k] = Op::apply(p, s.v0[k], s.v1[k], s.v2[k], bad);
+  }
+  static constexpr int kOutputs = 1;
+  __device__ __forceinline__ void store(const Slot& s, size_t i, int) const { st4<2, NT>(out + i, s.v0); }
+};
+
 template <class Op, int U, int NT>
 __global__ __launch_bounds__(kBlock) void stream4_kernel(const f32x4* s0,  // may alias out (in-place update)
                                                          const f32x4* __restrict__ s1,
@@ -88,65 +101,7 @@ __global__ __launch_bounds__(kBlock) void stream4_kernel(const f32x4* s0,  // ma
   const size_t first = chunk ? static_cast<size_t>(blockIdx.x) * chunk : static_cast<size_t>(blockIdx.x) * tile;
   size_t last = chunk ? first + chunk : n4;
   if (last > n4) last = n4;
-  bool bad = false;
-  // Whole tiles first, in a loop of their own WITHOUT a branch around any load or store: the compiler counts a wave's
-  // outstanding loads and stores in one counter and, behind a per-lane `i < last` guard, no longer knows how many are
-  // younger than the one it needs -- the guarded form of this loop waited for the first of three loads before issuing
-  // the fourth, and for every store to be acknowledged before computing the next 16 bytes (tools/isa_loop_mix.py --src
-  // linf.hip --waits).  Here a tile's 3 U loads are issued back to back, consumed in order with exact waits, and its U
-  // stores leave together.  Only the last tile of the buffer can be partial; it takes the guarded form below.
-  size_t base = first;
-  for (; base + tile <= last; base += stride) {
-    f32x4 v0[U], v1[U], v2[U], r[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const size_t i = base + static_cast<size_t>(u) * kBlock + threadIdx.x;
-      v0[u] = (NT & 4) ? __builtin_nontemporal_load(&s0[i]) : s0[i];
-      if (Op::kIn > 1) v1[u] = (NT & 1) ? __builtin_nontemporal_load(&s1[i]) : s1[i];
-      if (Op::kIn > 2) v2[u] = (NT & 4) ? __builtin_nontemporal_load(&s2[i]) : s2[i];
-    }
-    __builtin_amdgcn_sched_barrier(0);    // every load of the tile is in flight before the first one is waited for
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        r[u][k] = Op::apply(p, v0[u][k], Op::kIn > 1 ? v1[u][k] : 0.0f, Op::kIn > 2 ? v2[u][k] : 0.0f, bad);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const size_t i = base + static_cast<size_t>(u) * kBlock + threadIdx.x;
-      if (NT & 2)
-        __builtin_nontemporal_store(r[u], &out[i]);
-      else
-        out[i] = r[u];
-    }
-  }
-  if (base < last) {                      // the partial tile
-    f32x4 v0[U], v1[U], v2[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const size_t i = base + static_cast<size_t>(u) * kBlock + threadIdx.x;
-      if (i < last) {
-        v0[u] = (NT & 4) ? __builtin_nontemporal_load(&s0[i]) : s0[i];
-        if (Op::kIn > 1) v1[u] = (NT & 1) ? __builtin_nontemporal_load(&s1[i]) : s1[i];
-        if (Op::kIn > 2) v2[u] = (NT & 4) ? __builtin_nontemporal_load(&s2[i]) : s2[i];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const size_t i = base + static_cast<size_t>(u) * kBlock + threadIdx.x;
-      if (i < last) {
-        f32x4 r;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          r[k] = Op::apply(p, v0[u][k], Op::kIn > 1 ? v1[u][k] : 0.0f, Op::kIn > 2 ? v2[u][k] : 0.0f, bad);
-        if (NT & 2)
-          __builtin_nontemporal_store(r, &out[i]);
-        else
-          out[i] = r;
-      }
-    }
-  }
+  const bool bad = stream_tiles<U>(Stream4Tile<Op, NT>{s0, s1, s2, out, p}, first, last, stride);
   if ((p.mode & VQA_CHECK_RANGE) && bad) atomicOr(flag, 1);
 }
 
@@ -199,7 +154,7 @@ static int launch_stream(const float* s0, const float* s1, const float* s2, floa
   if (vec && n >= 4) {
     const size_t n4 = n / 4;
     const int unroll = TUNABLE ? g_opt_unroll : 4;
-    const int grid = blocks_for(n4, kBlock * unroll, cu_count() * g_opt_blocks_per_cu);
+    const int grid = stream_grid(n4, unroll, 1, g_opt_blocks_per_cu);
     size_t chunk = 0;
     if (g_opt_chunked) {   // equal contiguous chunks, rounded up to whole tiles
       const size_t tile = static_cast<size_t>(kBlock) * unroll;
@@ -210,7 +165,7 @@ static int launch_stream(const float* s0, const float* s1, const float* s2, floa
     auto a2 = reinterpret_cast<const f32x4*>(s2);
     auto o = reinterpret_cast<f32x4*>(out);
     int nt = g_opt_nontemporal & 7;
-    if ((g_opt_nontemporal & 8) && n * sizeof(float) > kNtStoreBytes) nt |= 2;
+    if ((g_opt_nontemporal & 8) && n * sizeof(float) > kInfinityCacheBytes) nt |= 2;
     nt &= NTMASK;
     if (s0 == out) nt &= ~4;        // in-place update: the first stream is about to be rewritten, keep it plain
 #ifdef VQA_TUNING

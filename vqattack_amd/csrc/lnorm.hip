@@ -7,11 +7,9 @@
 // The update kernels re-read the gradient; at the path's sizes (<= 453 MB per tensor) that second read is mostly
 // served by the 256 MiB Infinity Cache when the batch is small and by HBM otherwise (algorithmic bytes are
 // counted as HBM bytes either way).
-#include "common.hpp"
+#include "stream.hpp"
 
 namespace vqa {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kRedU = 4;                 // 16-byte loads in flight per lane
 constexpr int kMaxChunks = 512;          // partials per sample (stage 2 folds them with one workgroup)
@@ -347,8 +345,6 @@ __global__ __launch_bounds__(kBlock) void sumabs_stage1(const float* __restrict_
   if (threadIdx.x == 0) ws[static_cast<size_t>(blockIdx.y) * chunks + blockIdx.x] = r;
 }
 
-enum MomentumForm { kMomAccumulate, kMomFgm, kMomStep };   // m only | + FgmOp (no projection) | + StepOp
-
 // 16-byte tiles in flight per lane and stream of the momentum kernels, chosen by register count (tools/isa_loop_mix.py
 // --src lnorm.hip --waits).  The step form holds FOUR input streams: with 4 tiles it takes 120 registers (4 waves per
 // SIMD; the form without x0 131: 3 waves) and the compiler starts storing before the last loads are back; with 2 tiles
@@ -364,107 +360,57 @@ __device__ __forceinline__ float momentum_den(const float* __restrict__ sumabs, 
   return fmaxf(1e-12f, sumabs[blockIdx.y] / static_cast<float>(n_per));    // workgroup-uniform: grid.y is the sample
 }
 
-// One element: the momentum update (fp32 mul, IEEE div, add -- no contraction) ...
-__device__ __forceinline__ float momentum_update(float decay, float den, float m, float g) {
+// One element (or 16-byte piece): the momentum update (fp32 mul, IEEE div, add -- no contraction); the image update of
+// stream.hpp follows on the new m.
+template <class T>
+__device__ __forceinline__ T momentum_update(float decay, float den, const T& m, const T& g) {
   return decay * m + g / den;
 }
-// ... and the image update on the new m.
-template <int FORM>
-__device__ __forceinline__ float momentum_image(const StepParams& p, float x, float m, float x0, bool& bad) {
-  if (FORM == kMomStep) return StepOp::apply(p, x, m, x0, bad);
-  if (FORM == kMomFgm) return FgmOp::apply(p, x, m, 0.0f, bad);
-  return 0.0f;
-}
 
-// grid = (tiles dealt round-robin, batch): den is uniform per workgroup and no 16-byte piece straddles two samples.
-// The loop has the form linf.hip's stream4_kernel argues for: whole tiles without a branch around any load or store,
-// all loads of a tile issued before the first use, its stores leaving together; the sample's one partial tile apart.
+// grid = (tiles dealt round-robin, batch): den is uniform per workgroup and no 16-byte piece straddles two samples; the
+// tile's pointers start at the sample.  FORM: kNoImage updates m only.
 // g and x0 are read exactly once (non-temporal); NT bit1: non-temporal stores of `out`, NT bit2: non-temporal loads of
 // x (never for an in-place update), NT bit3: non-temporal loads and stores of m (g_opt_momentum_nt_m, above).
+template <int FORM, int NT>
+struct MomentumTile {
+  const f32x4* x;
+  const f32x4* g;
+  const f32x4* x0;
+  f32x4* m;
+  f32x4* out;
+  size_t off;      // the sample's first piece
+  float decay, den;
+  StepParams p;
+  struct Slot {
+    f32x4 x = {}, g, x0 = {}, m;
+  };
+  __device__ __forceinline__ void load(Slot& s, size_t i) const {
+    if (FORM != kNoImage) s.x = ld4<4, NT>(x + off + i);
+    s.g = ld4_once(g + off + i);
+    if (FORM == kStep) s.x0 = ld4_once(x0 + off + i);
+    s.m = ld4<8, NT>(m + off + i);
+  }
+  __device__ __forceinline__ void compute(Slot& s, bool& bad) const {
+    s.m = momentum_update(decay, den, s.m, s.g);
+    if (FORM != kNoImage) s.x = image<FORM>(p, s.x, s.m, s.x0, bad);
+  }
+  static constexpr int kOutputs = FORM != kNoImage ? 2 : 1;
+  __device__ __forceinline__ void store(const Slot& s, size_t i, int o) const {
+    if (o == kOutputs - 1) st4<8, NT>(m + off + i, s.m);
+    else st4<2, NT>(out + off + i, s.x);
+  }
+};
+
 template <int FORM, int U, int NT>
 __global__ __launch_bounds__(kBlock) void momentum_vec_kernel(const f32x4* x,   // may alias out
                                                               const f32x4* __restrict__ g,
                                                               const f32x4* __restrict__ x0, f32x4* m, f32x4* out,
                                                               const float* __restrict__ sumabs, size_t n_per,
                                                               float decay, StepParams p, int* __restrict__ flag) {
-  constexpr bool kImage = FORM != kMomAccumulate;
   const size_t n4 = n_per / 4;
-  const size_t off = static_cast<size_t>(blockIdx.y) * n4;
-  const float den = momentum_den(sumabs, n_per);
-  const size_t tile = static_cast<size_t>(kBlock) * U;
-  const size_t stride = static_cast<size_t>(gridDim.x) * tile;
-  bool bad = false;
-  size_t base = static_cast<size_t>(blockIdx.x) * tile;
-  for (; base + tile <= n4; base += stride) {
-    f32x4 vx[U], vg[U], v0[U], vm[U], r[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const size_t i = off + base + static_cast<size_t>(u) * kBlock + threadIdx.x;
-      if (kImage) vx[u] = (NT & 4) ? __builtin_nontemporal_load(&x[i]) : x[i];
-      vg[u] = __builtin_nontemporal_load(&g[i]);
-      if (FORM == kMomStep) v0[u] = __builtin_nontemporal_load(&x0[i]);
-      vm[u] = (NT & 8) ? __builtin_nontemporal_load(&m[i]) : m[i];
-    }
-    __builtin_amdgcn_sched_barrier(0);    // every load of the tile is in flight before the first one is waited for
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        vm[u][k] = momentum_update(decay, den, vm[u][k], vg[u][k]);
-        r[u][k] = momentum_image<FORM>(p, kImage ? vx[u][k] : 0.0f, vm[u][k], FORM == kMomStep ? v0[u][k] : 0.0f, bad);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const size_t i = off + base + static_cast<size_t>(u) * kBlock + threadIdx.x;
-      if (kImage) {
-        if (NT & 2)
-          __builtin_nontemporal_store(r[u], &out[i]);
-        else
-          out[i] = r[u];
-      }
-      if (NT & 8)
-        __builtin_nontemporal_store(vm[u], &m[i]);
-      else
-        m[i] = vm[u];
-    }
-  }
-  if (base < n4) {                        // the sample's partial tile
-    f32x4 vx[U], vg[U], v0[U], vm[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const size_t j = base + static_cast<size_t>(u) * kBlock + threadIdx.x;
-      if (j < n4) {
-        if (kImage) vx[u] = (NT & 4) ? __builtin_nontemporal_load(&x[off + j]) : x[off + j];
-        vg[u] = __builtin_nontemporal_load(&g[off + j]);
-        if (FORM == kMomStep) v0[u] = __builtin_nontemporal_load(&x0[off + j]);
-        vm[u] = (NT & 8) ? __builtin_nontemporal_load(&m[off + j]) : m[off + j];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const size_t j = base + static_cast<size_t>(u) * kBlock + threadIdx.x;
-      if (j < n4) {
-        f32x4 r;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          vm[u][k] = momentum_update(decay, den, vm[u][k], vg[u][k]);
-          r[k] = momentum_image<FORM>(p, kImage ? vx[u][k] : 0.0f, vm[u][k], FORM == kMomStep ? v0[u][k] : 0.0f, bad);
-        }
-        if (kImage) {
-          if (NT & 2)
-            __builtin_nontemporal_store(r, &out[off + j]);
-          else
-            out[off + j] = r;
-        }
-        if (NT & 8)
-          __builtin_nontemporal_store(vm[u], &m[off + j]);
-        else
-          m[off + j] = vm[u];
-      }
-    }
-  }
-  if (kImage && (p.mode & VQA_CHECK_RANGE) && bad) atomicOr(flag, VQA_FLAG_RANGE);
+  const MomentumTile<FORM, NT> t{x, g, x0, m, out, static_cast<size_t>(blockIdx.y) * n4, decay, momentum_den(sumabs, n_per), p};
+  const bool bad = stream_tiles<U>(t, n4);
+  if (FORM != kNoImage && (p.mode & VQA_CHECK_RANGE) && bad) atomicOr(flag, VQA_FLAG_RANGE);
 }
 
 // scalar path: n_per % 4 != 0 (sample boundaries fall inside 16-byte groups) or a pointer that is not 16-byte aligned
@@ -473,15 +419,14 @@ __global__ __launch_bounds__(kBlock) void momentum_scalar_kernel(const float* x,
                                                                  const float* __restrict__ x0, float* m, float* out,
                                                                  const float* __restrict__ sumabs, size_t n_per,
                                                                  float decay, StepParams p, int* __restrict__ flag) {
-  constexpr bool kImage = FORM != kMomAccumulate;
+  constexpr bool kImage = FORM != kNoImage;
   const size_t off = static_cast<size_t>(blockIdx.y) * n_per;
   const float den = momentum_den(sumabs, n_per);
   bool bad = false;
   for (size_t i = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x; i < n_per;
        i += static_cast<size_t>(gridDim.x) * kBlock) {
     const float mi = momentum_update(decay, den, m[off + i], g[off + i]);
-    const float r = momentum_image<FORM>(p, kImage ? x[off + i] : 0.0f, mi, FORM == kMomStep ? x0[off + i] : 0.0f, bad);
-    if (kImage) out[off + i] = r;
+    if (kImage) out[off + i] = image<FORM>(p, x[off + i], mi, FORM == kStep ? x0[off + i] : 0.0f, bad);
     m[off + i] = mi;
   }
   if (kImage && (p.mode & VQA_CHECK_RANGE) && bad) atomicOr(flag, VQA_FLAG_RANGE);
@@ -498,7 +443,7 @@ static void launch_momentum_vec(int nt, dim3 grid, hipStream_t st, const float* 
   auto o4 = reinterpret_cast<f32x4*>(out);
   // shipped hint sets: {0, 4} up to the Infinity Cache's size, {10, 14} above it (bit2 dropped for an in-place update);
   // the accumulate form has no image streams: {0, 8}
-  switch (FORM == kMomAccumulate ? (nt & 8) : (nt & 14)) {
+  switch (FORM == kNoImage ? (nt & 8) : (nt & 14)) {
 #ifdef VQA_TUNING
     case 2: momentum_vec_kernel<FORM, U, 2><<<grid, kBlock, 0, st>>>(x4, g4, z4, m4, o4, sumabs, n_per, decay, p, flag); break;
     case 6: momentum_vec_kernel<FORM, U, 6><<<grid, kBlock, 0, st>>>(x4, g4, z4, m4, o4, sumabs, n_per, decay, p, flag); break;
@@ -514,25 +459,22 @@ static void launch_momentum_vec(int nt, dim3 grid, hipStream_t st, const float* 
 template <int FORM>
 static int launch_momentum(const float* x, const float* g, const float* x0, float* m, float* out, const float* sumabs,
                            int batch, size_t n_per, float decay, const StepParams& p, int* flag, vqa_stream_t stream) {
-  constexpr bool kImage = FORM != kMomAccumulate;
-  if (!g || !sumabs || !m || (kImage && (!x || !out)) || (FORM == kMomStep && !x0)) return VQA_ERR_NULL;
+  constexpr bool kImage = FORM != kNoImage;
+  if (!g || !sumabs || !m || (kImage && (!x || !out)) || (FORM == kStep && !x0)) return VQA_ERR_NULL;
   if (kImage && (p.mode & VQA_CHECK_RANGE) && !flag) return VQA_ERR_NULL;
   if (batch < 0 || batch > 65535) return VQA_ERR_SHAPE;
   if (!aligned4(g) || !aligned4(m) || !aligned4(sumabs) || (kImage && (!aligned4(x) || !aligned4(out))) ||
-      (FORM == kMomStep && !aligned4(x0)))
+      (FORM == kStep && !aligned4(x0)))
     return VQA_ERR_ALIGN;
   if (batch == 0 || n_per == 0) return VQA_OK;
   const bool vec = (n_per % 4 == 0) && aligned16(g) && aligned16(m) && (!kImage || (aligned16(x) && aligned16(out))) &&
-                   (FORM != kMomStep || aligned16(x0));
+                   (FORM != kStep || aligned16(x0));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int unroll = g_opt_momentum_unroll;
-  // as many workgroups as linf.hip's grid (12 per CU: two whole rounds of its 6 resident ones), dealt over the samples
-  int cap = cu_count() * 12 / batch;
-  if (cap < 1) cap = 1;
   if (vec) {
-    dim3 grid(blocks_for(n_per / 4, kBlock * unroll, cap), batch);
+    dim3 grid(stream_grid(n_per / 4, unroll, batch), batch);    // linf.hip's grid, dealt over the samples
     int nt = 4;                                                              // x is read once ...
-    if (static_cast<size_t>(batch) * n_per * sizeof(float) > (256ull << 20))            // linf.hip's Infinity-Cache rule
+    if (static_cast<size_t>(batch) * n_per * sizeof(float) > kInfinityCacheBytes)
       nt |= g_opt_momentum_nt_m ? 2 | 8 : 2;
     if (x == out) nt &= ~4;                                                  // ... unless it is about to be rewritten
 #ifdef VQA_TUNING
@@ -541,7 +483,7 @@ static int launch_momentum(const float* x, const float* g, const float* x0, floa
 #endif
     launch_momentum_vec<FORM, 2>(nt, grid, st, x, g, x0, m, out, sumabs, n_per, decay, p, flag);
   } else {
-    dim3 grid(blocks_for(n_per, kBlock, cap), batch);
+    dim3 grid(stream_grid(n_per, 1, batch), batch);
     momentum_scalar_kernel<FORM><<<grid, kBlock, 0, st>>>(x, g, x0, m, out, sumabs, n_per, decay, p, flag);
   }
   return launch_status();
@@ -583,7 +525,7 @@ int vqa_momentum_accumulate(const float* g, const float* sumabs, float* m, int b
                             vqa_stream_t stream) {
   clear_stale_error();
   StepParams p{0.0f, 0.0f, 0.0f, 0.0f, 0u};
-  return launch_momentum<kMomAccumulate>(nullptr, g, nullptr, m, nullptr, sumabs, batch, n_per_sample, decay, p, nullptr,
+  return launch_momentum<kNoImage>(nullptr, g, nullptr, m, nullptr, sumabs, batch, n_per_sample, decay, p, nullptr,
                                          stream);
 }
 
@@ -592,8 +534,8 @@ int vqa_linf_momentum_step(const float* x, const float* g, const float* sumabs, 
                            float cmax, unsigned mode, int* flag, vqa_stream_t stream) {
   clear_stale_error();
   StepParams p{eps_iter, eps, cmin, cmax, mode};
-  if (x0) return launch_momentum<kMomStep>(x, g, x0, m, out, sumabs, batch, n_per_sample, decay, p, flag, stream);
-  return launch_momentum<kMomFgm>(x, g, nullptr, m, out, sumabs, batch, n_per_sample, decay, p, flag, stream);
+  if (x0) return launch_momentum<kStep>(x, g, x0, m, out, sumabs, batch, n_per_sample, decay, p, flag, stream);
+  return launch_momentum<kFgm>(x, g, nullptr, m, out, sumabs, batch, n_per_sample, decay, p, flag, stream);
 }
 
 size_t vqa_reduce_ws_bytes(int batch, size_t n_per_sample) {
