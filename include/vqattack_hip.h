@@ -113,6 +113,12 @@ int vqa_zero_out_clipped_grads(const float* grad, const float* x, float* out, si
 /* ---------------------------------------------------------------- per-sample reductions (L2 / L1 norms)
  * Deterministic two-stage reductions: stage 1 writes per-block partials into `ws`, stage 2 combines them in a
  * fixed order, so results are bitwise reproducible run to run.  `ws` must hold vqa_reduce_ws_bytes() bytes.
+ * Return codes of the reductions and of the L2 / L1 updates below, checked in this order: a required pointer NULL (`sub`,
+ * `stat2` of kinds 0 / 1 and a `flag` without VQA_CHECK_RANGE are optional) VQA_ERR_NULL; batch outside 0..65535, or a
+ * kind outside 0..2, VQA_ERR_SHAPE; any pointer -- statistics, workspace and flag included -- not 4-byte aligned
+ * VQA_ERR_ALIGN; batch == 0 or n_per_sample == 0 VQA_OK, no launch.  A refused call writes nothing.  16-byte accesses
+ * are used where n_per_sample % 4 == 0 and every element stream is 16-byte aligned, 4-byte accesses otherwise.
+ * max(1e-12, s) and min(1, f) below are torch.max / torch.min: a NaN sum of squares stays NaN and makes its whole sample NaN.
  */
 size_t vqa_reduce_ws_bytes(int batch, size_t n_per_sample);
 

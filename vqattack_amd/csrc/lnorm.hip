@@ -209,15 +209,23 @@ struct NormParams {
 
 enum Kind { kL2Fgm, kL2Project, kL1Fgm, kClipEtaL2, kOptLinL2, kOptLinL1 };
 
+// sqrt(max(1e-12, st)) and min(1, eps / length) as the reference forms them (A-ch/utils.py:33-37, :106-107): torch.max and
+// torch.min PROPAGATE a NaN (a NaN sum of squares makes the whole sample NaN), fmaxf / fminf drop it.
+__device__ __forceinline__ float l2_length(float st) { return sqrtf((st != st) ? st : fmaxf(1e-12f, st)); }
+__device__ __forceinline__ float l2_factor(float eps, float st) {
+  const float q = eps / l2_length(st);
+  return (q != q) ? q : fminf(1.0f, q);
+}
+
 // s0/s1: the two element streams (x,g | adv,x0 | t,-); st/st2: per-sample statistics.
 template <int KIND>
 __device__ __forceinline__ float norm_apply(const NormParams& p, float a, float b, float st, float st2, bool& bad) {
   if (KIND == kL2Fgm) {
     if (p.mode & VQA_CHECK_RANGE) bad |= out_of_range(a, p.cmin, p.cmax);
-    float v = a + p.eps * (b / sqrtf(fmaxf(1e-12f, st)));
+    float v = a + p.eps * (b / l2_length(st));
     return (p.mode & VQA_CLIP) ? clamp_torch(v, p.cmin, p.cmax) : v;
   } else if (KIND == kL2Project) {
-    float factor = fminf(1.0f, p.eps / sqrtf(fmaxf(1e-12f, st)));
+    float factor = l2_factor(p.eps, st);
     float v = b + (a - b) * factor;
     return (p.mode & VQA_CLIP) ? clamp_torch(v, p.cmin, p.cmax) : v;
   } else if (KIND == kL1Fgm) {
@@ -226,9 +234,9 @@ __device__ __forceinline__ float norm_apply(const NormParams& p, float a, float 
     float v = a + p.eps * (sign_torch(b) * hit / st2);
     return (p.mode & VQA_CLIP) ? clamp_torch(v, p.cmin, p.cmax) : v;
   } else if (KIND == kClipEtaL2) {
-    return a * fminf(1.0f, p.eps / sqrtf(fmaxf(1e-12f, st)));
+    return a * l2_factor(p.eps, st);
   } else if (KIND == kOptLinL2) {
-    return p.eps * (a / sqrtf(fmaxf(1e-12f, st)));
+    return p.eps * (a / l2_length(st));
   } else {
     float hit = (fabsf(a) == st) ? 1.0f : 0.0f;
     return p.eps * (sign_torch(a) * hit / st2);
@@ -295,7 +303,9 @@ static int launch_per_sample(const float* s0, const float* s1, const float* stat
   if ((KIND == kL1Fgm || KIND == kOptLinL1) && !stat2) return VQA_ERR_NULL;
   if ((p.mode & VQA_CHECK_RANGE) && !flag) return VQA_ERR_NULL;
   if (batch < 0 || batch > 65535) return VQA_ERR_SHAPE;
-  if (!aligned4(s0) || !aligned4(out) || (s1 && !aligned4(s1))) return VQA_ERR_ALIGN;
+  if (!aligned4(s0) || !aligned4(out) || (s1 && !aligned4(s1)) || !aligned4(stat) || (stat2 && !aligned4(stat2)) ||
+      (flag && !aligned4(flag)))
+    return VQA_ERR_ALIGN;
   if (batch == 0 || n_per == 0) return VQA_OK;
   const bool vec = (n_per % 4 == 0) && aligned16(s0) && aligned16(out) && (!TWO || aligned16(s1));
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -508,8 +518,8 @@ int vqa_sumabs_per_sample(const float* g, float* out, int batch, size_t n_per_sa
   clear_stale_error();
   if (!g || !out || !ws) return VQA_ERR_NULL;
   if (batch < 0 || batch > 65535) return VQA_ERR_SHAPE;
-  if (!aligned4(g)) return VQA_ERR_ALIGN;
-  if (batch == 0) return VQA_OK;
+  if (!aligned4(g) || !aligned4(out) || !aligned4(ws)) return VQA_ERR_ALIGN;
+  if (batch == 0 || n_per_sample == 0) return VQA_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int chunks = chunks_for(batch, n_per_sample);
   dim3 grid(chunks, batch);
@@ -548,8 +558,8 @@ int vqa_sumsq_per_sample(const float* t, const float* sub, float* out, int batch
   clear_stale_error();
   if (!t || !out || !ws) return VQA_ERR_NULL;
   if (batch < 0 || batch > 65535) return VQA_ERR_SHAPE;
-  if (!aligned4(t) || (sub && !aligned4(sub))) return VQA_ERR_ALIGN;
-  if (batch == 0) return VQA_OK;
+  if (!aligned4(t) || (sub && !aligned4(sub)) || !aligned4(out) || !aligned4(ws)) return VQA_ERR_ALIGN;
+  if (batch == 0 || n_per_sample == 0) return VQA_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int chunks = chunks_for(batch, n_per_sample);
   const bool vec = (n_per_sample % 4 == 0) && aligned16(t) && (!sub || aligned16(sub));
@@ -567,8 +577,8 @@ int vqa_absmax_ties_per_sample(const float* g, float* amax, float* ties, int bat
   clear_stale_error();
   if (!g || !amax || !ties || !ws) return VQA_ERR_NULL;
   if (batch < 0 || batch > 65535) return VQA_ERR_SHAPE;
-  if (!aligned4(g)) return VQA_ERR_ALIGN;
-  if (batch == 0) return VQA_OK;
+  if (!aligned4(g) || !aligned4(amax) || !aligned4(ties) || !aligned4(ws)) return VQA_ERR_ALIGN;
+  if (batch == 0 || n_per_sample == 0) return VQA_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int chunks = chunks_for(batch, n_per_sample);
   dim3 grid(chunks, batch);
