@@ -70,6 +70,11 @@ def parse(argv=None):
     ap.add_argument("--vt_beta", default=1.5, type=float,
                     help="variance tuning: neighbours are drawn from U[-vt_beta * eps, vt_beta * eps)")
     ap.add_argument("--vt_seed", default=None, type=int, help="variance tuning: seed of the device-side draws; absent: unseeded")
+    ap.add_argument("--admix_images", default=None, type=int,
+                    help="Admix (Wang et al. 2021): mixed groups x + admix_eta * x' of the scale copies per gradient "
+                         "evaluation, x' another sample of the batch (1..8); absent: off")
+    ap.add_argument("--admix_eta", default=0.2, type=float, help="Admix: the share of the partner image")
+    ap.add_argument("--admix_seed", default=None, type=int, help="Admix: seed of the partner draws; absent: unseeded")
     ap.add_argument("--mlm_checkpoint", default="", help="BertForMaskedLM state dict -> candidate proposer (adv_attack.py:110)")
     ap.add_argument("--answer_list", default=None,
                     help="ALBEF answer_list json (configs: answer_list): the victim ranks it and acc_vqa compares answer "
@@ -145,7 +150,8 @@ def main():
                                         ti_kernel=args.ti_kernel, diversity_prob=args.diversity_prob,
                                         di_shrink=args.di_shrink, di_seed=args.di_seed, si_copies=args.si_copies,
                                         nesterov=args.nesterov, vt_neighbors=args.vt_neighbors, vt_beta=args.vt_beta,
-                                        vt_seed=args.vt_seed),
+                                        vt_seed=args.vt_seed, admix_images=args.admix_images,
+                                        admix_eta=args.admix_eta, admix_seed=args.admix_seed),
                     scoring=scoring)
     finish(rank, world, res, os.path.join(args.output_dir, "adv_txt.json") if args.output_dir else None,
            os.path.join(args.output_dir, "adv_txt_dict_albef.txt") if args.output_dir and scoring else None)

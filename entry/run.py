@@ -38,13 +38,16 @@ DEFAULTS = dict(arch="vlmo_base", image_size=384, max_text_len=40, per_gpu_batch
                 n_samples=128, image_only=False, attack_dir="", dual_every=0, mixed=False, questions="", image_root="",
                 vocab_file="", tables_dir="", pretrain_path="", load_path="", mlm_checkpoint="", sim_threshold=0.95,
                 id2answer="", decay_factor=None, ti_kernel=None, diversity_prob=None, di_shrink=32,
-                di_seed=None, si_copies=None, nesterov=False, vt_neighbors=None, vt_beta=1.5, vt_seed=None)
+                di_seed=None, si_copies=None, nesterov=False, vt_neighbors=None, vt_beta=1.5, vt_seed=None,
+                admix_images=None, admix_eta=0.2, admix_seed=None)
 # absent = off (None): MI-FGSM momentum of the image attack; DI-FGSM probability of the random shrink-and-pad transform
 OPTIONAL_FLOATS = ("decay_factor", "diversity_prob")
 # absent = off (None): TI-FGSM Gaussian kernel length (odd, 1..31); seed of the DI draws (None: unseeded); number of
 # SI-FGSM scale copies (1..8).  nesterov=true (NI-FGSM look-ahead) needs decay_factor.  vt_neighbors= (1..64) turns on
-# variance tuning (VMI / VNI-FGSM) with neighbours from U[-vt_beta * eps, vt_beta * eps); vt_seed= (None: unseeded)
-OPTIONAL_INTS = ("ti_kernel", "di_seed", "si_copies", "vt_neighbors", "vt_seed")
+# variance tuning (VMI / VNI-FGSM) with neighbours from U[-vt_beta * eps, vt_beta * eps); vt_seed= (None: unseeded).
+# admix_images= (1..8) turns on Admix: that many mixed groups x + admix_eta * x' of the scale copies per gradient, x'
+# another sample of the batch; admix_seed= seeds the partner draws (None: unseeded)
+OPTIONAL_INTS = ("ti_kernel", "di_seed", "si_copies", "vt_neighbors", "vt_seed", "admix_images", "admix_seed")
 
 
 def parse(argv):
@@ -120,7 +123,9 @@ def main():
                                         decay_factor=cfg["decay_factor"], ti_kernel=cfg["ti_kernel"],
                                         diversity_prob=cfg["diversity_prob"], di_shrink=cfg["di_shrink"],
                                         di_seed=cfg["di_seed"], si_copies=cfg["si_copies"], nesterov=cfg["nesterov"],
-                                        vt_neighbors=cfg["vt_neighbors"], vt_beta=cfg["vt_beta"], vt_seed=cfg["vt_seed"]),
+                                        vt_neighbors=cfg["vt_neighbors"], vt_beta=cfg["vt_beta"], vt_seed=cfg["vt_seed"],
+                                        admix_images=cfg["admix_images"], admix_eta=cfg["admix_eta"],
+                                        admix_seed=cfg["admix_seed"]),
                     scoring=scoring)
     # adversarial images <qid>.pt and the adversarial-text json go to attack_dir (vlmo_module.py:166-167,2059-2062,2095-2097)
     finish(rank, world, res, os.path.join(cfg["attack_dir"], "adv_txt.json") if cfg["attack_dir"] else None,

@@ -306,6 +306,49 @@ int vqa_linf_si_step(const float* x, const float* const* grads_host, const float
                      const float* x0, float* out, size_t n, float eps_iter, float eps, float cmin, float cmax,
                      unsigned mode, int* flag, vqa_stream_t stream);
 
+/* ---------------------------------------------------------------- mixed-image copies (Admix, Wang et al. 2021)
+ * The reference tree has it in no framework; this definition is the contract.  Per gradient evaluation the model sees
+ * m2 GROUPS of `copies` scaled images; group j mixes every sample b with another sample partner_j[b] of the batch:
+ *   v = (x[b] [+ lookahead * m[b]]) + eta * x[partner_j[b]],   leaf_{j,i}[b] = s_i * v
+ * (the paper: eta = 0.2, s_i = 2^-i, 5 copies, 3 groups; the partner is read from x itself, without the look-ahead; no
+ * clamp and no projection), and the image gradient is the running sum over the groups in ascending j, copies ascending,
+ *   gsum = sum_j sum_i w_i * g_{j,i},   w_i = s_i / (copies * m2),
+ * group 0 through vqa_si_combine (the sum starts from its first product, not from +0), every later group continuing it
+ * through the entry points below -- all in fp32 with one rounding per operation (no contraction).  At most
+ * VQA_SI_MAX_COPIES copies per group and launch.  Scales, weights and the list of gradient pointers are HOST arrays that
+ * travel by value in the kernel arguments, as for SI (capture-safe: no allocation, no copy, no sync); the partner row is
+ * read from DEVICE memory, so that a captured launch sees whatever the row holds at each replay.  16-byte accesses are
+ * used when per % 4 == 0 and copy_stride % 4 == 0 (the copies), n % 4 == 0 (the sums), and every pointer, each gradient
+ * included, is 16-byte aligned.  Return codes, all before the first HIP call: a NULL required pointer, a NULL entry of
+ * grads_host, or VQA_CHECK_RANGE without flag, VQA_ERR_NULL; copies outside 1..VQA_SI_MAX_COPIES, batch outside
+ * 0..65535, copy_stride < batch * per, or a forbidden overlap or alias, VQA_ERR_SHAPE; a pointer not 4-byte aligned
+ * VQA_ERR_ALIGN; no element VQA_OK, no launch.
+ */
+
+/* The `copies` scaled copies of ONE group: out[i * copy_stride + b * per + e] = s_i * v with v as above (multiply, add
+ * for the look-ahead; multiply for eta * partner; add; multiply), i < copies, b < batch, e < per.  partner: a DEVICE row
+ * of `batch` int32; an entry outside [0, batch) never addresses memory, it stands for b itself.  One launch reads x
+ * twice (as itself and as a partner; the second read comes from the Infinity Cache) and m once and writes every copy:
+ * 4 (+ 4) + 4 + 4 * copies B/element.  copy_stride >= batch * per; out must not overlap x, m or the partner row. */
+int vqa_admix_copies(const float* x, const float* m, const int* partner, float* out, int batch, size_t per,
+                     size_t copy_stride, const float* scales_host, int copies, float eta, float lookahead,
+                     vqa_stream_t stream);
+
+/* acc[e] = a, a = acc[e], then a = a + w_i * g_i[e] for i = 0 .. copies - 1 ascending, exactly in place: vqa_si_combine
+ * on group 0 followed by this on the groups 1 .. m2 - 1 is the sum above.  grads_host is a HOST array of `copies` DEVICE
+ * pointers.  4 * copies + 8 B/element.  acc may alias no gradient. */
+int vqa_admix_accumulate(float* acc, const float* const* grads_host, const float* weights_host, int copies, size_t n,
+                         vqa_stream_t stream);
+
+/* The same sum and the L-infinity update in ONE pass: out = vqa_linf_step(x, a, x0), or, for x0 == NULL,
+ * out = vqa_linf_fgm(x, a) -- bit for bit what vqa_admix_accumulate followed by that launch gives; neither the sum nor
+ * acc is written.  4 * copies + 16 B/element (12 without x0) against (4 * copies + 8) + 16 for the two launches.  `out`
+ * may be exactly `x` (in place) and must not otherwise overlap x, x0, acc or a gradient.  mode / flag as in
+ * vqa_linf_step. */
+int vqa_linf_admix_step(const float* x, const float* acc, const float* const* grads_host, const float* weights_host,
+                        int copies, const float* x0, float* out, size_t n, float eps_iter, float eps, float cmin,
+                        float cmax, unsigned mode, int* flag, vqa_stream_t stream);
+
 /* ---------------------------------------------------------------- variance tuning (VMI / VNI-FGSM, Wang & He 2021)
  * The reference tree has it in no framework; this definition is the contract.  Let G(p) be the image gradient of one
  * evaluation at p (after the SI combination and the DI adjoint, before TI smoothing).  Evaluation t at point p steps

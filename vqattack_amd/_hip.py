@@ -61,6 +61,9 @@ SIGNATURES = {
     "vqa_si_copies": (_i, [_p, _p, _p, _sz, _sz, _p, _i, _f, _p]),
     "vqa_si_combine": (_i, [_p, _p, _i, _p, _sz, _p]),
     "vqa_linf_si_step": (_i, [_p, _p, _p, _i, _p, _p, _sz, _f, _f, _f, _f, _u, _p, _p]),
+    "vqa_admix_copies": (_i, [_p, _p, _p, _p, _i, _sz, _sz, _p, _i, _f, _f, _p]),
+    "vqa_admix_accumulate": (_i, [_p, _p, _p, _i, _sz, _p]),
+    "vqa_linf_admix_step": (_i, [_p, _p, _p, _p, _i, _p, _p, _sz, _f, _f, _f, _f, _u, _p, _p]),
     "vqa_vt_max_chunk": (_i, []),
     "vqa_vt_neighbors": (_i, [_p, _p, _p, _sz, _sz, _i, _i, _ull, _f, _f, _p, _p]),
     "vqa_vt_accumulate": (_i, [_p, _i, _p, _sz, _i, _p]),

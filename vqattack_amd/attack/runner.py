@@ -53,23 +53,37 @@ class AttackConfig:
     vt_neighbors: Optional[int] = None     # not None: variance tuning (VMI / VNI-FGSM) with this many neighbours per evaluation (1..64)
     vt_beta: float = 1.5                   # VT: neighbours are drawn from U[-vt_beta * eps, vt_beta * eps) (the paper's 1.5)
     vt_seed: Optional[int] = None          # VT: 64-bit seed of the device-side draws (None: one seed from np.random per call)
+    admix_images: Optional[int] = None     # not None: Admix, every gradient is taken over this many mixed groups of the scale copies (1..8)
+    admix_eta: float = 0.2                 # Admix: the share of the partner image (the paper's 0.2)
+    admix_seed: Optional[int] = None       # Admix: seed of the np.random.RandomState each attack call draws its partners from
 
-    TRANSFER_KEYS = ("decay_factor", "ti_kernel", "diversity_prob", "di_shrink", "si_copies", "nesterov", "vt_neighbors",
-                     "vt_beta", "vt_seed")        # the fields the operators take under the same names
+    STAGE_KEYS = ("decay_factor", "ti_kernel", "diversity_prob", "di_shrink", "si_copies", "nesterov", "vt_neighbors",
+                  "vt_beta", "vt_seed")           # what attacks._validate_stages takes
+    ADMIX_KEYS = ("admix_images", "admix_eta")    # what attacks._validate_admix takes
+    TRANSFER_KEYS = STAGE_KEYS + ADMIX_KEYS       # the fields the operators take under the same names
 
     def transfer_kwargs(self):
-        """The transfer-method keywords of an operator call; the caller adds ``momentum`` and ``di_rng``."""
+        """The transfer-method keywords of an operator call; the caller adds ``momentum``, ``di_rng`` and ``admix_rng``."""
         return {key: getattr(self, key) for key in self.TRANSFER_KEYS}
 
+    def stage_kwargs(self):
+        """The keywords of ``attacks._validate_stages``."""
+        return {key: getattr(self, key) for key in self.STAGE_KEYS}
+
     def __post_init__(self):
-        attacks._validate_stages(**self.transfer_kwargs())
+        attacks._validate_stages(**self.stage_kwargs())
+        attacks._validate_admix(self.admix_images, self.admix_eta)
+        if self.admix_seed is not None and (isinstance(self.admix_seed, bool)
+                                            or not isinstance(self.admix_seed, (int, np.integer))
+                                            or not 0 <= int(self.admix_seed) < 2 ** 32):
+            raise ValueError("admix_seed must be None or an int in [0, 2^32), got {!r}".format(self.admix_seed))
         if self.di_seed is not None and (isinstance(self.di_seed, bool) or not isinstance(self.di_seed, (int, np.integer))
                                          or not 0 <= int(self.di_seed) < 2 ** 32):
             raise ValueError("di_seed must be None or an int in [0, 2^32), got {!r}".format(self.di_seed))
         # no transfer method runs on a patch-major image: the per-sample sum of |grad| is folded in memory order and would
         # round differently, the TI stencil and the DI transform run over row-major (H, W) planes, and the patch-major path
-        # is not exercised with the other two
-        for key in ("decay_factor", "ti_kernel", "diversity_prob", "si_copies", "vt_neighbors"):
+        # is not exercised with the others
+        for key in ("decay_factor", "ti_kernel", "diversity_prob", "si_copies", "vt_neighbors", "admix_images"):
             if getattr(self, key) is not None and self.patch_layout:
                 raise ValueError("{} and patch_layout=True cannot be combined".format(key))
 
@@ -121,6 +135,8 @@ class BatchedVQAttack:
         self.pgd_vl = ns.projected_gradient_descent_vl.projected_gradient_descent
         self.di_rng = None        # DI: set to anything with .uniform to draw from it instead of RandomState(cfg.di_seed)
         self._di_draws = None     # the generator of the attack call that is running
+        self.admix_rng = None     # Admix: the same for its partner draws (RandomState(cfg.admix_seed))
+        self._admix_draws = None
 
     def _start_di(self):
         """DI-FGSM: one generator per attack_batch / attack_mixed call; every operator call inside draws its rows from
@@ -130,6 +146,10 @@ class BatchedVQAttack:
             self._di_draws = None
         else:
             self._di_draws = self.di_rng if self.di_rng is not None else np.random.RandomState(c.di_seed)
+        if c.admix_images is None:
+            self._admix_draws = None
+        else:   # Admix: likewise, one draw per sample, mixed group and gradient evaluation (ops.admix_draw)
+            self._admix_draws = self.admix_rng if self.admix_rng is not None else np.random.RandomState(c.admix_seed)
         return self._di_draws
 
     # the y lists the reference passes (adv_attack.py:609,637; vlmo_module.py:1948,1975)
@@ -153,7 +173,7 @@ class BatchedVQAttack:
         c = self.cfg
         common = dict(clip_min=c.clip_min, clip_max=c.clip_max, time=time, ori_x=clean,
                       sanity_checks=c.sanity_checks, init_eta=init_eta, momentum=momentum, di_rng=self._di_draws,
-                      **c.transfer_kwargs())
+                      admix_rng=self._admix_draws, **c.transfer_kwargs())
         a = self.adapters
         if not dual:
             return self.pgd(a.pgd_attack, adv, c.eps, c.eps_iter, steps, c.norm, y=self._y_feature(targets), ls=1,
@@ -264,7 +284,8 @@ class BatchedVQAttack:
                                                  1, c.norm, clip_min=c.clip_min, clip_max=c.clip_max,
                                                  y=self._y_feature(targets), time=1, ori_x=images, ls=1,
                                                  attack_mask=positions, sanity_checks=c.sanity_checks, momentum=mom,
-                                                 di_rng=self._di_draws, **c.transfer_kwargs())
+                                                 di_rng=self._di_draws, admix_rng=self._admix_draws,
+                                                 **c.transfer_kwargs())
                 res.gradient_steps += 1
                 if plan is not None:
                     scores = text_update.score_plan(self.tables, e_ori, text_grad, plan)
@@ -347,6 +368,10 @@ class BatchedVQAttack:
         if c.vt_neighbors is not None:
             # the per-run updates of the mixed schedule carry no variance state: use attack_batch on schedule-pure buckets
             raise ValueError("vt_neighbors is not supported by attack_mixed (the mixed-schedule driver)")
+        if c.admix_images is not None:
+            # the per-run updates of the mixed schedule materialise all leaves at once and update runs of samples; Admix
+            # folds group by group into one running sum for the whole batch: use attack_batch on schedule-pure buckets
+            raise ValueError("admix_images is not supported by attack_mixed (the mixed-schedule driver)")
         dev, b, text_len = images.device, images.shape[0], text_ids.shape[1]
         images, init_eta, restore = self._enter_layout(images, init_eta)
         n_words = [int(w) for w in attackable.sum(dim=1).tolist()]
@@ -405,7 +430,7 @@ class BatchedVQAttack:
         mom = self._new_momentum(images)          # in the sorted order of `images`; only the active prefix is updated
         # the transfer stages of the whole call, sized for every sample: DI's rows of every global step are drawn and
         # uploaded once, SI's copies and the scratches are filled for the active prefix (the update: for one run) of a step
-        chain = attacks._Chain(attacks._validate_stages(di_rng=self._start_di(), **c.transfer_kwargs()), cur, np.inf, c.eps,
+        chain = attacks._Chain(attacks._validate_stages(di_rng=self._start_di(), **c.stage_kwargs()), cur, np.inf, c.eps,
                                c.eps_iter, max(total), momentum=mom)
         losses = torch.zeros(max(total), dtype=torch.float32, device=dev)
         ws = ops.Workspace()

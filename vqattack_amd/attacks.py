@@ -177,6 +177,33 @@ def _validate_vt(vt_neighbors, vt_beta=1.5, vt_seed=None):
     return int(vt_neighbors), float(vt_beta), (None if vt_seed is None else int(vt_seed))
 
 
+def _validate_admix(admix_images, admix_eta=0.2, admix_rng=None):
+    """None (no mixing; the other two keys are then ignored) or ``(images, eta, rng)``: ``admix_images`` an int m2 in
+    1..8, ``admix_eta`` a finite number >= 0 (the partner's share), ``admix_rng`` None (``np.random``) or anything with a
+    callable ``.uniform``, as ``di_rng``.  Raised before any tensor is looked at, like the other arguments."""
+    if admix_images is None:
+        return None
+    if isinstance(admix_images, (bool, np.bool_)) or not isinstance(admix_images, (int, np.integer)) or \
+            not 1 <= int(admix_images) <= ops.ADMIX_MAX_IMAGES:
+        raise ValueError("admix_images must be None or an int in 1..{}, got {!r}".format(ops.ADMIX_MAX_IMAGES, admix_images))
+    if isinstance(admix_eta, (bool, np.bool_)) or not isinstance(admix_eta, (int, float, np.integer, np.floating)) or \
+            not 0.0 <= float(admix_eta) < float("inf"):        # False for NaN too
+        raise ValueError("admix_eta must be a finite number greater than or equal to 0, got {!r}".format(admix_eta))
+    if admix_rng is not None and not callable(getattr(admix_rng, "uniform", None)):
+        raise ValueError("admix_rng must be None or have a .uniform method (np.random, a RandomState, a Generator), "
+                         "got {!r}".format(admix_rng))
+    return int(admix_images), float(admix_eta), (np.random if admix_rng is None else admix_rng)
+
+
+def _admix_batch(aspec, x):
+    """Admix mixes every sample with ANOTHER sample of the batch: a batch of one is refused before any launch."""
+    if aspec is not None:
+        shape = getattr(x, "shape", None)
+        if shape is None or len(shape) < 1 or shape[0] < 2:
+            raise ValueError("admix_images needs a batch of at least 2 samples (every sample is mixed with another one "
+                             "of the batch), got shape {}".format(None if shape is None else tuple(shape)))
+
+
 def _two_sided(clip_min, clip_max):
     if (clip_min is not None or clip_max is not None) and (clip_min is None or clip_max is None):
         raise ValueError("One of clip_min and clip_max is None but we don't currently support one-sided clipping")
@@ -509,6 +536,27 @@ class _Variance:
         self.key = self.row if static else self.table[t]
 
 
+class _Admix:
+    """The Admix state of one operator call: the partner table of ALL its gradient evaluations, drawn once on the host and
+    uploaded in one copy (``(n_evals, m2, B)``), one static ``(m2, B)`` row for a captured iteration, the current rows
+    and -- with more than one mixed group -- the running sum ``gsum`` of the groups' weighted gradients.  ``acc``: where
+    the evaluation under way keeps that sum (``gsum``, or the tensor its caller named)."""
+
+    def __init__(self, spec, like, n_evals):
+        self.images, self.eta, rng = spec
+        b = like.shape[0]
+        self.table = ops.admix_partners(ops.admix_draw(rng, b, n_evals, self.images), b, like.device)
+        self.row = torch.empty((self.images, b), dtype=torch.int32, device=like.device)
+        self.gsum = torch.empty_like(like, memory_format=torch.contiguous_format) if self.images > 1 else None
+        self.rows, self.acc, self.n = None, self.gsum, 0
+
+    def use(self, i, static=False):
+        """Make evaluation ``i``'s rows current: in place in the table, or (``static``) copied into the static row."""
+        if static:
+            self.row.copy_(self.table[i])
+        self.rows = self.row if static else self.table[i]
+
+
 def _validate_stages(decay_factor=None, ti_kernel=None, diversity_prob=None, di_shrink=32, di_rng=None, si_copies=None,
                      nesterov=False, vt_neighbors=None, vt_beta=1.5, vt_seed=None):
     """The transfer keywords of an operator call as the specs ``_Chain`` takes (None: that stage is off), validated in
@@ -531,12 +579,30 @@ class _Chain:
     ``kinds``: evaluation kinds that tune a variance of their own; ``momentum``: the caller's tensor or None (zeros).
     Without specs it is the plain update and touches no tensor of its own.
 
+    ``admix`` (``_validate_admix``'s spec, None: off): Admix runs in SI's place in the order above.  Every evaluation sees
+    m2 mixed groups of the m1 scale copies (without ``si_copies``: one copy at scale 1), in ascending group order, each
+    group's copies from one launch (``ops.admix_copies``) into SI's image buffer; the weights are ``s_i / (m1 * m2)``.
+    The groups 0 .. m2-2 are folded into the running sum as soon as their m1 model calls have returned --
+    ``ops.si_combine`` for group 0, ``ops.admix_accumulate`` behind it -- so at most m1 images and m1 gradients are live;
+    the last group's gradients are handed on with the sum, and the update folds them in its own launch
+    (``ops.linf_admix_step``) where SI / Admix is the last active stage under L-inf, else through
+    ``ops.admix_accumulate`` in front of the DI adjoint, VT, TI, momentum and the L2 update.  With m2 = 1 there is no
+    running sum and every launch behind the model is SI's.  All copies and all VT neighbours of an evaluation share its
+    partner rows (a neighbour tensor is mixed with its own samples) and its DI rows; the partner table is drawn after
+    DI's rows and VT's seed.  ``call(leaf, first)`` gets ``first=True`` for the first copy of the first group only: the
+    reported loss is that mixed copy's.  The leaves of all groups share SI's image buffer, so a leaf is valid until the
+    next group's copies are written.
+
     The mixed-schedule driver runs one chain on row subsets of its state: ``leaves(.., n=)`` on the active batch prefix,
     ``update(.., rows=(lo, hi))`` on one run of samples."""
 
     def __init__(self, specs=(None,) * 5, like=None, norm=np.inf, eps=0.0, eps_iter=0.0, n_evals=1, kinds=1,
-                 momentum=None):
+                 momentum=None, admix=None):
         decay, taps, dspec, sspec, vspec = specs
+        if admix is not None:
+            _admix_batch(admix, like)
+            if sspec is None:
+                sspec = (ops.si_scales(1), False)              # one copy at scale 1 per mixed image
         active = [name for name, spec in (("si", sspec), ("di", dspec), ("vt", vspec), ("ti", taps), ("mom", decay))
                   if spec is not None]
         self.norm = norm
@@ -551,17 +617,25 @@ class _Chain:
                     key, what, tuple(like.shape)))
         self.ti = None if taps is None else _Smoother(taps, like, self.fused != "ti")
         self.di = None if dspec is None else _Diversity(dspec, like, n_evals, self.fused != "di")
-        self.si = None if sspec is None else _Scales(sspec, like, eps_iter, self.mom, self.di, self.fused != "si")
+        multi = admix is not None and admix[0] > 1             # a running sum takes the place of SI's scratch
+        self.si = None if sspec is None else _Scales(sspec, like, eps_iter, self.mom, self.di,
+                                                     self.fused != "si" and not multi)
         self.vt = None if vspec is None else _Variance(vspec, like, eps, n_evals, kinds)
+        self.ax = None if admix is None else _Admix(admix, like, n_evals)
+        if self.ax is not None:
+            self.si.weights = ops.admix_weights(self.si.scales, self.ax.images)
         # the word that takes the losses nobody reports: those of the scale copies after the first and of the neighbours
         self.slot = self.si.slot if self.si is not None else (self.vt.slot if self.vt is not None else None)
 
     def use(self, i, static=False):
-        """Make DI's rows and VT's key of evaluation ``i`` current (``static``: copied to their static addresses)."""
+        """Make DI's rows, VT's key and Admix's partner rows of evaluation ``i`` current (``static``: copied to their
+        static addresses)."""
         if self.di is not None:
             self.di.use(i, static)
         if self.vt is not None:
             self.vt.use(i, static)
+        if self.ax is not None:
+            self.ax.use(i, static)
 
     def leaves(self, adv, advance=True, ahead=True, n=None):
         """The leaves the model sees for one gradient evaluation at ``adv``, made one at a time: ``adv`` itself or its DI
@@ -569,8 +643,9 @@ class _Chain:
         ascending order -- all copies of an evaluation share its DI rows, so the adjoint is linear over them and the
         combination may precede it.  ``ahead=False``: no Nesterov look-ahead in front of the copies (``adv`` is a
         variance-tuning neighbour, drawn around the look-ahead point already).  ``n``: ``adv`` is the batch prefix
-        ``[:n]``; the state is sliced to match."""
-        si, di = self.si, self.di
+        ``[:n]``; the state is sliced to match.  With Admix the copies of one mixed group after the other, each group
+        from one launch into the same buffer (no batch prefix: the partners are samples of the whole batch)."""
+        si, di, ax = self.si, self.di, self.ax
         head = (lambda t: t) if n is None else (lambda t: t[:n])
         if di is not None and advance:
             di.use(di.n)
@@ -580,26 +655,51 @@ class _Chain:
             yield seen.detach().requires_grad_(True)
             return
         m = head(si.mom.m) if ahead and si.mom is not None else None
-        images = ops.si_copies(adv, si.scales, m=m, lookahead=0.0 if m is None else si.lookahead,
-                               out=si.images if n is None else si.images[:, :n])
-        for i in range(images.shape[0]):
-            seen = images[i] if di is None else ops.di_transform(images[i], head(di.geom), out=head(si.transformed[i]))
-            yield seen.detach().requires_grad_(True)
+        if ax is not None:
+            if n is not None:
+                raise ValueError("Admix mixes samples of the whole batch: no batch prefix")
+            if advance:
+                ax.use(ax.n)
+                ax.n += 1
+        for j in range(1 if ax is None else ax.images):
+            if ax is None:
+                images = ops.si_copies(adv, si.scales, m=m, lookahead=0.0 if m is None else si.lookahead,
+                                       out=si.images if n is None else si.images[:, :n])
+            else:
+                images = ops.admix_copies(adv, ax.rows[j], si.scales, ax.eta, m=m,
+                                          lookahead=0.0 if m is None else si.lookahead, out=si.images)
+            for i in range(images.shape[0]):
+                seen = images[i] if di is None else ops.di_transform(images[i], head(di.geom), out=head(si.transformed[i]))
+                yield seen.detach().requires_grad_(True)
 
-    def _gradient(self, adv, call, advance=True, ahead=True):
+    def _gradient(self, adv, call, advance=True, ahead=True, acc=None):
         """``call(leaf, first)`` on every leaf in turn: it runs the white box and the loss and leaves the gradient in
-        ``leaf.grad``.  Returns the leaf's gradient, with SI the list of the copies' gradients."""
-        grads = []
+        ``leaf.grad``.  Returns the leaf's gradient, with SI the list of the copies' gradients; with Admix the list of the
+        LAST group's, the groups before it folded into the running sum (``acc``, None: the state's ``gsum``) one by one."""
+        ax, grads = self.ax, []
+        multi = ax is not None and ax.images > 1
+        if multi:
+            ax.acc = ax.gsum if acc is None else acc
+            m1, last = len(self.si.scales), len(self.si.scales) * ax.images - 1
         for i, leaf in enumerate(self.leaves(adv, advance, ahead)):
             call(leaf, i == 0)
             grads.append(_grad_of(leaf))
+            if multi and len(grads) == m1 and i < last:
+                if i < m1:
+                    ops.si_combine(grads, self.si.weights, out=ax.acc)
+                else:
+                    ops.admix_accumulate(grads, self.si.weights, ax.acc)
+                grads = []
         return grads if self.si is not None else grads[0]
 
     def _x_gradient(self, grad, out=None):
         """``G`` of variance tuning: what ``_gradient`` returned, taken to x space -- the SI combination, then the DI
         adjoint, each into its own scratch (the last one into ``out`` when given); without either the leaf's gradient."""
-        si, di = self.si, self.di
-        if si is not None:
+        si, di, ax = self.si, self.di, self.ax
+        if ax is not None and ax.images > 1:   # in place in the running sum, which is ``out`` where nothing follows
+            ops.admix_accumulate(grad, si.weights, ax.acc)
+            grad = ax.acc
+        elif si is not None:
             grad = ops.si_combine(grad, si.weights, out=si.ghat if (out is None or di is not None) else out)
         if di is not None:
             grad = ops.di_adjoint(grad, di.geom, out=di.grad if out is None else out)
@@ -613,14 +713,16 @@ class _Chain:
         summed per launch; with either each neighbour's gradient is combined / adjoint-ed into its scratch and summed one
         at a time -- the same bits.  Leaves ``sum_i G(p + r_i)`` in ``vt.vsum`` and returns ``G(p)``, in x space; ``kind``
         selects the variance the update tunes."""
-        si, vt = self.si, self.vt
+        si, vt, ax = self.si, self.vt, self.ax
         if vt is None:
             return self._gradient(adv, call, advance)
         if advance:
             vt.use(vt.t)
             vt.t += 1
         vt.kind = kind
-        g = self._x_gradient(self._gradient(adv, call, advance), out=vt.ghat)
+        # the centre's running sum must outlive the neighbours': it is kept where G(p) ends up unless DI's adjoint follows
+        acc = vt.ghat if ax is not None and ax.images > 1 and self.di is None else None
+        g = self._x_gradient(self._gradient(adv, call, advance, acc=acc), out=vt.ghat)
         m, lookahead = (si.mom.m, si.lookahead) if si is not None and si.mom is not None else (None, 0.0)
 
         def other(leaf, _):
@@ -655,14 +757,22 @@ class _Chain:
         step = (eps_iter, 0.0 if fgm else eps, clip_min, clip_max)
         tail = dict(flag=flag if fgm and check_range else None, out=out)     # what every L-inf kernel takes last
         si, di, vt, ti, mom = self.si, self.di, self.vt, self.ti, self.mom
+        multi = self.ax is not None and self.ax.images > 1
+        if multi and rows is not None:
+            raise ValueError("Admix keeps one running sum for the whole batch: no update of a run of samples")
         if vt is not None:            # ``grad`` is G(p), in x space already: SI and DI are done with
             if self.fused == "vt":
                 return ops.linf_vt_step(x, grad, vt.vsum, vt.v[vt.kind], x0, vt.w, *step, **tail)
             grad = ops.vt_tune(grad, vt.vsum, vt.v[vt.kind], vt.w, out=vt.ghat)
         else:
+            if self.fused == "si" and multi:
+                return ops.linf_admix_step(x, self.ax.acc, grad, x0, si.weights, *step, **tail)
             if self.fused == "si":
                 return ops.linf_si_step(x, grad, x0, si.weights, *step, **tail)
-            if si is not None:
+            if multi:
+                ops.admix_accumulate(grad, si.weights, self.ax.acc)
+                grad = self.ax.acc
+            elif si is not None:
                 grad = ops.si_combine(grad, si.weights, out=cut(si.ghat))
             if self.fused == "di":
                 return ops.linf_di_step(x, grad, x0, cut(di.geom), *step, **tail)
@@ -721,22 +831,27 @@ def _grad_of(leaf):
 # ----------------------------------------------------------------------------------------- FGM
 def fast_gradient_method(model_fn, x, eps, norm, ori_x, clip_min=None, clip_max=None, y=None, targeted=False,
                          sanity_checks=False, ls=None, bkp=None, bkp_y=None, *, flavor=ALBEF, per_sample=False,
-                         ti_kernel=None, diversity_prob=None, di_shrink=32, di_rng=None, si_copies=None):
+                         ti_kernel=None, diversity_prob=None, di_shrink=32, di_rng=None, si_copies=None,
+                         admix_images=None, admix_eta=0.2, admix_rng=None):
     """One FGM step; returns ``(adv_x, loss)`` (``loss`` is a 0-d device tensor), bare ``x`` when ``eps == 0``.
     ``ti_kernel`` (extension, keyword-only): TI-FGSM smoothing of the gradient, as in ``projected_gradient_descent``.
     ``diversity_prob`` / ``di_shrink`` / ``di_rng`` (extensions, keyword-only): DI-FGSM, as there (one evaluation).
     ``si_copies`` (extension, keyword-only): SI-FGSM scale copies, as there; ``loss`` is copy 0's.
+    ``admix_images`` / ``admix_eta`` / ``admix_rng`` (extensions, keyword-only): Admix, as there (one evaluation); ``loss``
+    is that of the first mixed copy.
     Reference: A fast_gradient_method.py:30-165, V :36-152 (the VLMO copy has no ``bkp``/``bkp_y``)."""
     _check_flavor(flavor)
     _validate_fgm(norm, eps, clip_min, clip_max)
     specs = _validate_stages(ti_kernel=ti_kernel, diversity_prob=diversity_prob, di_shrink=di_shrink, di_rng=di_rng,
                              si_copies=si_copies)
+    aspec = _validate_admix(admix_images, admix_eta, admix_rng)
+    _admix_batch(aspec, x)
     if eps == 0:
         return x
     xin = _as_image(x)
     check_range = sanity_checks and (clip_min is not None or clip_max is not None)
     flag = ops.new_flag(xin.device) if (check_range or norm != np.inf) else None
-    chain = _Chain(specs, xin, norm, eps, eps)
+    chain = _Chain(specs, xin, norm, eps, eps, admix=aspec)
     loss_buf = torch.zeros(1, dtype=torch.float32, device=xin.device)
 
     def call(leaf, first):      # without DI / SI the leaf shares storage with x: nothing is written in place
@@ -752,10 +867,13 @@ def fast_gradient_method(model_fn, x, eps, norm, ori_x, clip_min=None, clip_max=
 
 def fast_gradient_method_vl(model_fn, x, eps, norm, ori_x, clip_min=None, clip_max=None, y=None, targeted=False,
                             sanity_checks=False, ls=None, text_emb_pick=None, *, flavor=ALBEF, ti_kernel=None,
-                            diversity_prob=None, di_shrink=32, di_rng=None, si_copies=None):
+                            diversity_prob=None, di_shrink=32, di_rng=None, si_copies=None, admix_images=None,
+                            admix_eta=0.2, admix_rng=None):
     """FGM on ``x = [image, text_embeds]``; returns ``(adv_image, text_grad[:, text_emb_pick])``.
     ``si_copies`` (extension, keyword-only): SI-FGSM scale copies of the IMAGE, as in ``projected_gradient_descent``;
     ``x[0]`` is then copy 0's leaf, the text gradient is copy 0's and the other copies see the text embeddings detached.
+    ``admix_images`` / ``admix_eta`` / ``admix_rng`` (extensions, keyword-only): Admix on the IMAGE, as there; ``x[0]`` and
+    the text gradient are those of the first mixed copy (the leaf's storage is reused by the later groups).
     ``ti_kernel`` (extension, keyword-only): TI-FGSM smoothing of the IMAGE gradient, as in ``projected_gradient_descent``.
     ``diversity_prob`` / ``di_shrink`` / ``di_rng`` (extensions, keyword-only): DI-FGSM on the IMAGE, as there; ``x[0]`` of
     the caller's list is then the transformed leaf the model saw.
@@ -765,13 +883,15 @@ def fast_gradient_method_vl(model_fn, x, eps, norm, ori_x, clip_min=None, clip_m
     _validate_fgm(norm, eps, clip_min, clip_max)
     specs = _validate_stages(ti_kernel=ti_kernel, diversity_prob=diversity_prob, di_shrink=di_shrink, di_rng=di_rng,
                              si_copies=si_copies)
+    aspec = _validate_admix(admix_images, admix_eta, admix_rng)
+    _admix_batch(aspec, x[0] if aspec is not None else None)
     if eps == 0:
         return x
     img = _as_image(x[0], "x[0]")
     emb = _as_image(x[1], "x[1]")
     check_range = sanity_checks and (clip_min is not None or clip_max is not None)
     flag = ops.new_flag(img.device) if (check_range or norm != np.inf) else None
-    chain = _Chain(specs, img, norm, eps, eps)
+    chain = _Chain(specs, img, norm, eps, eps, admix=aspec)
     x[1] = emb.detach().requires_grad_(True)
     loss_buf = torch.zeros(1, dtype=torch.float32, device=img.device)
 
@@ -836,6 +956,8 @@ def _graphed_linf_loop(model_fn, cur, x0, y, flavor, targeted, eps_iter, eps, cl
     SI: the gradients' addresses, which travel by value in the kernel arguments, are the graph's own and the same at every
     replay.  VT: the neighbour launches are captured against the static key row; a copy of the iteration's key (seed and
     ``t``) into it precedes each replay, like DI's rows, so that every replay draws fresh numbers from the same launches.
+    Admix: the copies launches are captured against the static partner rows; a copy of the iteration's ``(m2, B)`` rows
+    into them precedes each replay, like DI's rows.
     """
     word = torch.zeros(1, dtype=torch.float32, device=cur.device)
 
@@ -870,7 +992,8 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
                                sanity_checks=True, ls=None, *, flavor=ALBEF, init_eta=None, graph=None,
                                per_sample=False, decay_factor=None, momentum=None, ti_kernel=None,
                                diversity_prob=None, di_shrink=32, di_rng=None, si_copies=None, nesterov=False,
-                               vt_neighbors=None, vt_beta=1.5, vt_seed=None):
+                               vt_neighbors=None, vt_beta=1.5, vt_seed=None, admix_images=None, admix_eta=0.2,
+                               admix_rng=None):
     """PGD over a frozen white box; returns ``(adv_x, loss_list)``, bare ``x`` when eps or eps_iter is 0.
 
     ``ls == 1``: feature loss, ``model_fn`` a callable.  Otherwise the dual-loss loop: ``model_fn = [feature_fn,
@@ -935,12 +1058,28 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
     The reported loss is the centre's.  The dual loop keeps one ``v`` for its feature evaluations and one for its MLM
     evaluations.  With ``vt_neighbors=None`` (default) nothing changes, ``vt_beta`` / ``vt_seed`` are ignored and no random
     number is drawn.
+    ``admix_images`` / ``admix_eta`` / ``admix_rng`` (extensions, keyword-only): Admix (Wang et al. 2021; the reference
+    tree has it in no framework).  ``admix_images`` an int m2 in 1..8: every gradient evaluation calls the model on m2
+    groups of the scale copies ``s_i * (p + admix_eta * adv[partner_j])``, ``p`` being ``adv`` or the look-ahead point,
+    ``partner_j`` another sample of the batch per sample, drawn uniformly (``ops.admix_draw``) -- group by group, copies
+    ascending -- and the gradient is ``sum_j sum_i s_i / (m1 * m2) * g_ji``.  Without ``si_copies`` every mixed image is
+    one copy at scale 1; the paper's setting is ``si_copies=5, admix_images=3, admix_eta=0.2``.  Each group's copies come
+    from one launch (``ops.admix_copies``); a finished group is folded into a running sum (``ops.si_combine``, then
+    ``ops.admix_accumulate``), so at most m1 images and gradients are live; the plain L-inf update folds the last group in
+    the same launch (``ops.linf_admix_step``), every other path in front of the DI adjoint, the variance tuning, the
+    smoothing, the momentum and the update, which run unchanged.  All partner rows of the call are drawn once, before the
+    loop and after DI's rows and VT's seed, from ``admix_rng`` (anything with ``.uniform``; None: ``np.random``), one draw
+    per sample, group and evaluation; all copies and VT neighbours of an evaluation share its rows.  The reported loss is
+    that of the first mixed copy.  The batch must hold at least 2 samples (``ValueError``).  With ``admix_images=None``
+    (default) nothing changes, the other two keys are ignored and no random number is drawn.
     Reference: A projected_gradient_descent.py:10-199, V :10-196.
     """
     _check_flavor(flavor)
     unchanged = _validate_pgd(norm, eps, eps_iter, clip_min, clip_max)
     specs = _validate_stages(decay_factor, ti_kernel, diversity_prob, di_shrink, di_rng, si_copies, nesterov,
                              vt_neighbors, vt_beta, vt_seed)
+    aspec = _validate_admix(admix_images, admix_eta, admix_rng)
+    _admix_batch(aspec, x)
     if unchanged:
         return x
     xin = _as_image(x)
@@ -958,7 +1097,7 @@ def projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_m
     loss_buf = torch.zeros(max(nb_iter, 1) * (2 if dual else 1), dtype=torch.float32, device=xin.device)
     n_loss = 0
     chain = _Chain(specs, xin, norm, eps, eps_iter, nb_iter * (2 if dual else 1), kinds=2 if dual else 1,
-                   momentum=momentum)
+                   momentum=momentum, admix=aspec)
     ws = ops.Workspace()       # loss-gradient / CE scratch buffers live for the whole call, not per iteration
     bad_flag = flag if flag is not None else (
         ops.new_flag(xin.device) if ((dual and sanity_checks) or norm != np.inf) else None)
@@ -1014,7 +1153,7 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
                                   sanity_checks=True, ls=None, attack_mask=None, *, flavor=ALBEF, init_eta=None,
                                   decay_factor=None, momentum=None, ti_kernel=None, diversity_prob=None, di_shrink=32,
                                   di_rng=None, si_copies=None, nesterov=False, vt_neighbors=None, vt_beta=1.5,
-                                  vt_seed=None):
+                                  vt_seed=None, admix_images=None, admix_eta=0.2, admix_rng=None):
     """PGD on ``x = [image, text_embeds]`` (only the image moves); returns ``(adv_image, text_embed_gradient)`` of
     the last iteration.  Only ``ls == 1`` is supported (``ValueError`` otherwise), as in the reference.
     ``decay_factor`` / ``momentum`` (extensions, keyword-only): MI-FGSM on the image, as in
@@ -1024,12 +1163,15 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
     keyword-only): SI-NI-FGSM on the image, as there; the text gradient is copy 0's and the other copies see the text
     embeddings detached.  ``vt_neighbors`` / ``vt_beta`` / ``vt_seed`` (extensions, keyword-only): variance tuning, as
     there; only the image is perturbed, the text gradient is the centre evaluation's and the neighbours see the text
-    embeddings detached.
+    embeddings detached.  ``admix_images`` / ``admix_eta`` / ``admix_rng`` (extensions, keyword-only): Admix on the image,
+    as there; the text gradient is that of the first mixed copy and every other copy sees the text embeddings detached.
     Reference: A projected_gradient_descent_vl.py:10-168, V :10-164."""
     _check_flavor(flavor)
     unchanged = _validate_pgd(norm, eps, eps_iter, clip_min, clip_max)
     specs = _validate_stages(decay_factor, ti_kernel, diversity_prob, di_shrink, di_rng, si_copies, nesterov,
                              vt_neighbors, vt_beta, vt_seed)
+    aspec = _validate_admix(admix_images, admix_eta, admix_rng)
+    _admix_batch(aspec, x[0] if aspec is not None else None)
     if unchanged:
         return x
     img = _as_image(x[0], "x[0]")
@@ -1047,7 +1189,7 @@ def projected_gradient_descent_vl(model_fn, x, eps, eps_iter, nb_iter, norm, cli
     text_grad = None
     loss_buf = torch.zeros(max(nb_iter, 1), dtype=torch.float32, device=img.device)
     ws = ops.Workspace()
-    chain = _Chain(specs, img, norm, eps, eps_iter, nb_iter, momentum=momentum)
+    chain = _Chain(specs, img, norm, eps, eps_iter, nb_iter, momentum=momentum, admix=aspec)
     if attack_mask is not None and not isinstance(attack_mask, ops.RowIndex):   # validated + uploaded once per call
         attack_mask = ops.RowIndex(attack_mask, emb.shape[1], emb.device)
     for it in range(nb_iter):
@@ -1077,7 +1219,7 @@ def momentum_iterative_method(model_fn, x, eps, eps_iter, nb_iter, norm, clip_mi
                               ori_x=None, targeted=False, decay_factor=1.0, sanity_checks=True, ls=1, *, flavor=ALBEF,
                               graph=None, momentum=None, ti_kernel=None, diversity_prob=None, di_shrink=32,
                               di_rng=None, si_copies=None, nesterov=False, vt_neighbors=None, vt_beta=1.5,
-                              vt_seed=None):
+                              vt_seed=None, admix_images=None, admix_eta=0.2, admix_rng=None):
     """The momentum iterative method (Dong et al. 2017) on this project's losses; returns ``(adv_x, loss_list)`` like
     ``projected_gradient_descent``, so a driver can swap one for the other.
 
@@ -1089,7 +1231,8 @@ def momentum_iterative_method(model_fn, x, eps, eps_iter, nb_iter, norm, clip_mi
     (TI-MI-FGSM, the combination the TI paper recommends) as in ``projected_gradient_descent``, which runs the loop;
     ``diversity_prob`` / ``di_shrink`` / ``di_rng`` as there too (M-DI2-FGSM; with ``ti_kernel`` TI-DIM), and so are
     ``si_copies`` / ``nesterov`` (SI-NI-FGSM; with the other keys SI-NI-TI-DIM) and ``vt_neighbors`` / ``vt_beta`` /
-    ``vt_seed`` (VMI-FGSM; with ``nesterov`` VNI-FGSM)."""
+    ``vt_seed`` (VMI-FGSM; with ``nesterov`` VNI-FGSM) and ``admix_images`` / ``admix_eta`` / ``admix_rng`` (with the TI and
+    DI keys the Admix paper's Admix-TI-DIM)."""
     if norm != 1 and decay_factor is None:
         raise ValueError("decay_factor must be a number (use projected_gradient_descent for the attack without momentum)")
     return projected_gradient_descent(model_fn, x, eps, eps_iter, nb_iter, norm, clip_min=clip_min, clip_max=clip_max,
@@ -1098,4 +1241,5 @@ def momentum_iterative_method(model_fn, x, eps, eps_iter, nb_iter, norm, clip_mi
                                       decay_factor=decay_factor, momentum=momentum, ti_kernel=ti_kernel,
                                       diversity_prob=diversity_prob, di_shrink=di_shrink, di_rng=di_rng,
                                       si_copies=si_copies, nesterov=nesterov, vt_neighbors=vt_neighbors,
-                                      vt_beta=vt_beta, vt_seed=vt_seed)
+                                      vt_beta=vt_beta, vt_seed=vt_seed, admix_images=admix_images, admix_eta=admix_eta,
+                                      admix_rng=admix_rng)

@@ -14,7 +14,7 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libvqattack_hip.so")
 # the same sources with -DVQA_TUNING: launch-shape knobs behind vqa_set_option() + the A/B kernel variants (tools/ only)
 TUNING_LIB_PATH = os.path.join(LIB_DIR, "libvqattack_hip_tuning.so")
-SOURCES = ["linf.hip", "lnorm.hip", "ti.hip", "di.hip", "si.hip", "vt.hip", "loss.hip", "ce.hip", "text.hip", "image.hip", "attn.hip", "block.hip", "gemm.hip"]
+SOURCES = ["linf.hip", "lnorm.hip", "ti.hip", "di.hip", "si.hip", "admix.hip", "vt.hip", "loss.hip", "ce.hip", "text.hip", "image.hip", "attn.hip", "block.hip", "gemm.hip"]
 # -ffp-contract=off: the reference's op chain rounds after every add/mul; keep it that way (bit-exact parity).
 FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17",
          "-Wall", "-Wno-unused-function"]
@@ -24,7 +24,7 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared"
 # tied to the code that produced them (profiles/*/pmc_traffic.json, bench.py's `traffic` field)
 KERNEL_SOURCES = (("stream4_kernel", "linf.hip"), ("neg_cos_rows", "loss.hip"), ("ce_rows", "ce.hip"), ("ce_count", "ce.hip"),
                   ("attn_", "attn.hip"), ("sumsq", "lnorm.hip"), ("absmax", "lnorm.hip"), ("per_sample", "lnorm.hip"),
-                  ("sum_stage2", "lnorm.hip"), ("sumabs", "lnorm.hip"), ("momentum", "lnorm.hip"), ("ti_kernel", "ti.hip"), ("di_forward", "di.hip"), ("di_adjoint", "di.hip"), ("si_combine", "si.hip"), ("si_copies", "si.hip"), ("vt_neighbors", "vt.hip"), ("vt_accumulate", "vt.hip"), ("vt_tune", "vt.hip"), ("ln_fwd", "block.hip"), ("ln_bwd", "block.hip"), ("gelu", "block.hip"),
+                  ("sum_stage2", "lnorm.hip"), ("sumabs", "lnorm.hip"), ("momentum", "lnorm.hip"), ("ti_kernel", "ti.hip"), ("di_forward", "di.hip"), ("di_adjoint", "di.hip"), ("si_combine", "si.hip"), ("si_copies", "si.hip"), ("admix_copies", "admix.hip"), ("admix_accumulate", "admix.hip"), ("vt_neighbors", "vt.hip"), ("vt_accumulate", "vt.hip"), ("vt_tune", "vt.hip"), ("ln_fwd", "block.hip"), ("ln_bwd", "block.hip"), ("gelu", "block.hip"),
                   ("resize", "image.hip"), ("gather_rows", "text.hip"), ("cand_dir_sim", "text.hip"),
                   ("embed_tokens", "text.hip"), ("greedy_accept", "text.hip"), ("gemm_", "gemm.hip"))
 

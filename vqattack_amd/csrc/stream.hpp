@@ -1,5 +1,5 @@
-// The tile loop of the PGD path's HBM-bound stream kernels (linf.hip, lnorm.hip's momentum step, si.hip, vt.hip), written
-// once, and the small launch rules those files share.
+// The tile loop of the PGD path's HBM-bound stream kernels (linf.hip, lnorm.hip's momentum step, si.hip, admix.hip,
+// vt.hip), written once, and the small launch rules those files share.
 //
 // Such a kernel has arithmetic intensity < 0.5 flop/B: one 16-byte access per lane and stream, U slots of 256 pieces in
 // flight per wave before the first use, 256-thread workgroups, a grid of 12 workgroups per CU that strides over

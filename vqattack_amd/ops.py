@@ -617,6 +617,143 @@ def linf_si_step(x, grads, x0, weights, eps_iter, eps, clip_min, clip_max, flag=
     return out
 
 
+# ----------------------------------------------------------------------------------------- mixed-image copies (Admix)
+ADMIX_MAX_IMAGES = 8   # mixed groups per gradient evaluation (the paper's m2 = 3)
+
+
+def _admix_images(images):
+    if isinstance(images, (bool, np.bool_)) or not isinstance(images, (int, np.integer)) or \
+            not 1 <= int(images) <= ADMIX_MAX_IMAGES:
+        raise ValueError("images must be an int in 1..{}, got {!r}".format(ADMIX_MAX_IMAGES, images))
+    return int(images)
+
+
+def admix_draw(rng, batch, n_evals, images):
+    """The partner table of ``n_evals`` gradient evaluations as an int32 numpy array ``(n_evals, images, batch)``: entry
+    ``[t, j, b]`` is the sample that group ``j`` of evaluation ``t`` mixes into sample ``b``, uniform over the OTHER
+    samples of the batch.  ``rng`` is anything with ``.uniform`` (``np.random``, a ``RandomState``, a ``Generator``); one
+    draw ``u`` per entry, in the order evaluation, group, sample: ``k = min(int(u * (batch - 1)), batch - 2)``,
+    ``partner = (b + 1 + k) mod batch``."""
+    batch, n_evals, images = int(batch), int(n_evals), _admix_images(images)
+    if batch < 2:
+        raise ValueError("admix_draw: mixing needs another sample of the batch, got batch {}".format(batch))
+    if n_evals < 0:
+        raise ValueError("admix_draw: n_evals must be >= 0, got {}".format(n_evals))
+    table = np.empty((n_evals, images, batch), dtype=np.int32)
+    for t in range(n_evals):
+        for j in range(images):
+            for b in range(batch):
+                k = min(int(rng.uniform() * (batch - 1)), batch - 2)
+                table[t, j, b] = (b + 1 + k) % batch
+    return table
+
+
+def admix_check_table(table, batch):
+    """``table`` as a C-contiguous int32 numpy array ``(..., batch)`` with every entry in ``[0, batch)`` and none equal to
+    its own index along the last axis."""
+    t = np.asarray(table)
+    if t.dtype.kind not in "iu" or t.ndim < 1 or t.shape[-1] != int(batch):
+        raise ValueError("an Admix partner table is an integer array (..., {}), got dtype {} shape {}".format(
+            batch, t.dtype, t.shape))
+    t = t.astype(np.int64)
+    own = np.arange(int(batch), dtype=np.int64)
+    bad = (t < 0) | (t >= int(batch)) | (t == own)
+    if bad.any():
+        where = np.unravel_index(int(np.flatnonzero(bad.reshape(-1))[0]), t.shape)
+        raise ValueError("Admix partner {} at {} is outside [0, {}) or is the sample itself".format(
+            int(t[where]), tuple(int(v) for v in where), batch))
+    return np.ascontiguousarray(t.astype(np.int32))
+
+
+def admix_partners(table, batch, device):
+    """Validate a partner table against ``batch`` (every entry in range and not its own sample) and upload it in one
+    copy: an int32 device tensor of the table's shape.  The copies kernel reads one ``(batch,)`` row of it per launch."""
+    return torch.from_numpy(admix_check_table(table, batch)).to(device)
+
+
+def admix_weights(scales, images):
+    """``w_i = float32(s_i) / float32(n * images)``: the paper's average over the ``n`` copies of each of the ``images``
+    mixed groups, with the chain rule through the scaling.  ``images = 1`` gives ``si_weights(scales)``."""
+    s, _ = _si_host(scales, "scales")
+    return (s / np.float32(s.size * _admix_images(images))).astype(np.float32)
+
+
+def _admix_row(row, batch):
+    if not isinstance(row, torch.Tensor) or not row.is_cuda or row.dtype != torch.int32 or not row.is_contiguous() \
+            or tuple(row.shape) != (batch,):
+        raise ValueError("partner_row must be a contiguous int32 device tensor ({},) (ops.admix_partners), got {}".format(
+            batch, (row.dtype, tuple(row.shape), str(row.device)) if isinstance(row, torch.Tensor) else type(row)))
+    return row
+
+
+def admix_copies(x, partner_row, scales, eta, m=None, lookahead=0.0, out=None):
+    """``out[i][b] = s_i * ((x[b] [+ lookahead * m[b]]) + eta * x[partner_row[b]])``: the scaled copies of ONE mixed group
+    in one launch, as an ``(n,) + x.shape`` tensor; the first axis of ``x`` is the batch.  No clamp, no projection.  An
+    entry of the row outside ``[0, B)`` never addresses memory (the kernel takes it for ``b``); ``admix_partners`` refuses
+    such a table on the host.  ``out`` must not overlap ``x``, ``m`` or the row; each ``out[i]`` must be contiguous, and
+    the copies may lie further apart than ``x.numel()`` (the batch prefix of a larger buffer)."""
+    s, buf = _si_host(scales, "scales")
+    dev_f32(x, "x")
+    if x.dim() < 1:
+        raise ValueError("x must have a batch axis")
+    if m is not None:
+        dev_f32(m, "momentum")
+        if m.shape != x.shape:
+            raise ValueError("momentum shape {} != x shape {}".format(tuple(m.shape), tuple(x.shape)))
+    batch = x.shape[0]
+    _admix_row(partner_row, batch)
+    shape = (int(s.size),) + tuple(x.shape)
+    same_device(x, m, out, partner_row)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        dev_f32(out, "out", contiguous=False)
+        if tuple(out.shape) != shape:
+            raise ValueError("out has shape {}, expected {}".format(tuple(out.shape), shape))
+        if not out[0].is_contiguous() or (s.size > 1 and out.stride(0) < x.numel()):
+            raise ValueError("every out[i] must be contiguous and the copies must not overlap")
+    if x.numel() == 0:
+        return out
+    stride = out.stride(0) if s.size > 1 else x.numel()
+    with _on(x):
+        check(lib().vqa_admix_copies(ptr(x), ptr(m), ctypes.c_void_p(partner_row.data_ptr()), ptr(out), batch,
+                                     x.numel() // batch, stride, buf, int(s.size), float(eta), float(lookahead),
+                                     stream_for(x)), "vqa_admix_copies")
+    return out
+
+
+def admix_accumulate(grads, weights, acc):
+    """``acc = (...((acc + w_0 * g_0) + w_1 * g_1) + ...)`` exactly in place (ascending, one rounding per operation): the
+    running sum of a mixed group after the first, which ``si_combine`` starts.  ``acc`` may alias no gradient."""
+    pbuf, wbuf, copies = _si_grads(grads, weights)
+    dev_f32(acc, "acc")
+    if acc.shape != grads[0].shape:
+        raise ValueError("acc has shape {}, grads[0] {}".format(tuple(acc.shape), tuple(grads[0].shape)))
+    same_device(grads[0], acc)
+    if acc.numel() == 0:
+        return acc
+    with _on(acc):
+        check(lib().vqa_admix_accumulate(ptr(acc), pbuf, wbuf, copies, acc.numel(), stream_for(acc)),
+              "vqa_admix_accumulate")
+    return acc
+
+
+def linf_admix_step(x, acc, grads, x0, weights, eps_iter, eps, clip_min, clip_max, flag=None, out=None):
+    """``admix_accumulate`` and ``linf_step`` on its result in one pass, 4 * copies + 16 B/element; ``x0=None``: and
+    ``linf_fgm`` (no projection).  Neither the sum nor ``acc`` is written; ``out`` may be ``x``."""
+    pbuf, wbuf, copies = _si_grads(grads, weights)
+    dev_f32(acc, "acc")
+    if acc.shape != grads[0].shape:
+        raise ValueError("acc has shape {}, grads[0] {}".format(tuple(acc.shape), tuple(grads[0].shape)))
+    out, mode, lo, hi = _fused_step_args(x, grads[0], x0, clip_min, clip_max, flag, out, also=(acc,), what="grads")
+    if x.numel() == 0:
+        return out
+    with _on(x):
+        check(lib().vqa_linf_admix_step(ptr(x), ptr(acc), pbuf, wbuf, copies, ptr(x0), ptr(out), x.numel(), eps_iter,
+                                        eps, lo, hi, mode, ptr(flag), stream_for(x)), "vqa_linf_admix_step")
+    return out
+
+
 # ----------------------------------------------------------------------------------------- variance tuning (VMI / VNI-FGSM)
 VT_MAX_CHUNK = 8       # VQA_VT_MAX_CHUNK of include/vqattack_hip.h (vqa_vt_max_chunk())
 VT_MAX_NEIGHBORS = 64
