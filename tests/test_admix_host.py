@@ -285,20 +285,20 @@ def test_kernel_source_table_knows_the_new_kernels():
     assert "admix.hip" in build.SOURCES and len(set(build.SOURCES)) == len(build.SOURCES)
     keys = [k for k, _ in build.KERNEL_SOURCES]
     for name in ("void vqa::admix_copies_vec_kernel<5, true, 2, 0>(float __vector(4) const*, float __vector(4) const*, "
-                 "int const*, float __vector(4)*, int, unsigned long, unsigned long, vqa::AdmixScales, float, float)",
+                 "int const*, float __vector(4)*, int, unsigned long, unsigned long, vqa::Scales, float, float)",
                  "void vqa::admix_copies_scalar_kernel<1, false>(float const*, float const*, int const*, float*, int, "
-                 "unsigned long, unsigned long, vqa::AdmixScales, float, float)",
-                 "void vqa::admix_accumulate_vec_kernel<0, 5, 0>(float __vector(4) const*, float __vector(4) const*, "
-                 "float __vector(4) const*, vqa::AdmixGrads, float __vector(4)*, unsigned long, vqa::StepParams, int*)",
-                 "void vqa::admix_accumulate_vec_kernel<2, 8, 4>(float __vector(4) const*, float __vector(4) const*, "
-                 "float __vector(4) const*, vqa::AdmixGrads, float __vector(4)*, unsigned long, vqa::StepParams, int*)",
-                 "void vqa::admix_accumulate_scalar_kernel<1, 3>(float const*, float const*, float const*, vqa::AdmixGrads, "
+                 "unsigned long, unsigned long, vqa::Scales, float, float)",
+                 "void vqa::grad_fold_vec_kernel<true, 0, 5, 1, 0>(float __vector(4) const*, float __vector(4) const*, "
+                 "float __vector(4) const*, vqa::GradList, float __vector(4)*, unsigned long, vqa::StepParams, int*)",
+                 "void vqa::grad_fold_vec_kernel<true, 2, 8, 1, 4>(float __vector(4) const*, float __vector(4) const*, "
+                 "float __vector(4) const*, vqa::GradList, float __vector(4)*, unsigned long, vqa::StepParams, int*)",
+                 "void vqa::grad_fold_scalar_kernel<true, 1, 3>(float const*, float const*, float const*, vqa::GradList, "
                  "float*, unsigned long, vqa::StepParams, int*)"):
         first = next(f for k, f in build.KERNEL_SOURCES if k in name)          # the FIRST key that matches decides
         assert first == "admix.hip", (name, first)
         assert build.kernel_source_digest(name) not in (None, build.kernel_source_digest("vqa::si_copies_vec_kernel<1>"))
     assert len(set(keys)) == len(keys)
-    for name in ("vqa::si_copies_vec_kernel<1>", "vqa::si_combine_vec_kernel<2, 8, 1, 0>"):     # SI's stay where they were
+    for name in ("vqa::si_copies_vec_kernel<1>", "vqa::grad_fold_vec_kernel<false, 2, 8, 1, 0>"):   # SI's stay where they were
         assert next(f for k, f in build.KERNEL_SOURCES if k in name) == "si.hip"
 
 

@@ -19,6 +19,13 @@ import numpy as np
 import pytest
 import torch
 
+from tests.pgd_reference import accumulate_np as _accumulate_np
+from tests.pgd_reference import assert_bits as _assert_bits
+from tests.pgd_reference import combine_np as _combine_np
+from tests.pgd_reference import place as _place
+from tests.pgd_reference import same_bits as _same_bits
+from tests.pgd_reference import update_np
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 F = np.float32
@@ -34,16 +41,8 @@ SUM_NAMES = list(_SUM_SHAPES)
 _cache = {}
 
 
-def _place(a, off):
-    """Host array -> device tensor; ``off``: one float behind a 16-byte boundary."""
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    if not off:
-        return t.to(DEV)
-    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=DEV)
-    view = buf[1:].view(t.shape)
-    view.copy_(t)
-    assert view.data_ptr() % 16 == 4 and view.is_contiguous()
-    return view
+def _update_np(x, ghat, x0, clip=True):
+    return update_np(x, ghat, x0, EPS_ITER, EPS, LO, HI, clip)
 
 
 def _round_per():
@@ -103,52 +102,6 @@ def _copies_np(x, row, s, eta, m=None, lookahead=0.0):
         out = np.stack([F(si) * v for si in s])
     assert out.dtype == F
     return out
-
-
-def _accumulate_np(acc, g, w):
-    with np.errstate(all="ignore"):
-        a = acc
-        for i in range(len(w)):
-            a = a + F(w[i]) * g[i]
-    assert a.dtype == F
-    return a
-
-
-def _combine_np(g, w):
-    with np.errstate(all="ignore"):
-        a = F(w[0]) * g[0]
-        for i in range(1, len(w)):
-            a = a + F(w[i]) * g[i]
-    return a
-
-
-def _sign(g):
-    return (g > 0).astype(F) - (g < 0).astype(F)      # torch.sign: sign(NaN) = 0
-
-
-def _update_np(x, ghat, x0, clip=True):
-    """numpy fp32: StepOp (x0 given) or FgmOp (x0 None) of csrc/common.hpp."""
-    a = x + F(EPS_ITER) * _sign(ghat)
-    if clip:
-        a = np.clip(a, F(LO), F(HI))
-    if x0 is None:
-        return a
-    out = x0 + np.clip(a - x0, -F(EPS), F(EPS))
-    if clip:
-        out = np.clip(out, F(LO), F(HI))
-    assert out.dtype == F
-    return out
-
-
-def _assert_bits(got, want, what):
-    got = got.detach().cpu().numpy()
-    assert got.shape == want.shape and got.dtype == want.dtype, what
-    same = np.mean(got.view(np.int32) == want.view(np.int32))
-    assert same == 1.0, (what, same)
-
-
-def _same_bits(a, b):
-    return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 # ------------------------------------------------------------------------------------------------ copies

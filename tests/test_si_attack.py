@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.pgd_reference import combine_np as _combine_np
+from tests.pgd_reference import copies_np as _copies_np
 from tests.test_di_attack import SHRINK, _di_kw, _rows
 from tests.test_di_kernels import di_adjoint, di_forward
 from tests.test_momentum_attack import (CLIP, DEV, EPS, EPS_ITER, IDS, ITERS, _assert_bits, _dev, _grad, _setup,
@@ -40,21 +42,6 @@ def _keys(combo, seed=SEED):
 def _scales(n):
     from vqattack_amd import ops
     return ops.si_scales(1 if n is None else n)
-
-
-def _copies_np(x, s, m=None, lookahead=0.0):
-    base = x if m is None else x + F(lookahead) * m              # multiply, add ...
-    out = [F(si) * base for si in s]                             # ... multiply
-    assert all(c.dtype == np.float32 for c in out)
-    return out
-
-
-def _combine_np(grads, w):
-    acc = F(w[0]) * grads[0]
-    for i in range(1, len(grads)):
-        acc = acc + F(w[i]) * grads[i]
-    assert acc.dtype == np.float32
-    return acc
 
 
 def _step_np(x, d, x0, eps_iter, eps=EPS):

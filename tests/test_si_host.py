@@ -254,14 +254,14 @@ def test_kernel_source_table_knows_the_new_kernels():
     from vqattack_amd import build
     assert "si.hip" in build.SOURCES and len(set(build.SOURCES)) == len(build.SOURCES)
     keys = [k for k, _ in build.KERNEL_SOURCES]
-    for name in ("void vqa::si_combine_vec_kernel<2, 5, 1, 4>(float __vector(4) const*, float __vector(4) const*, "
-                 "vqa::SiGrads, float __vector(4)*, unsigned long, vqa::StepParams, int*)",
-                 "void vqa::si_combine_scalar_kernel<0, 3>(float const*, float const*, vqa::SiGrads, float*, unsigned long, "
-                 "vqa::StepParams, int*)",
+    for name in ("void vqa::grad_fold_vec_kernel<false, 2, 5, 1, 4>(float __vector(4) const*, float __vector(4) const*, "
+                 "float __vector(4) const*, vqa::GradList, float __vector(4)*, unsigned long, vqa::StepParams, int*)",
+                 "void vqa::grad_fold_scalar_kernel<false, 0, 3>(float const*, float const*, float const*, vqa::GradList, "
+                 "float*, unsigned long, vqa::StepParams, int*)",
                  "void vqa::si_copies_vec_kernel<5, true, 2, 0>(float __vector(4) const*, float __vector(4) const*, "
-                 "float __vector(4)*, unsigned long, unsigned long, vqa::SiScales, float)",
+                 "float __vector(4)*, unsigned long, unsigned long, vqa::Scales, float)",
                  "void vqa::si_copies_scalar_kernel<1, false>(float const*, float const*, float*, unsigned long, "
-                 "unsigned long, vqa::SiScales, float)"):
+                 "unsigned long, vqa::Scales, float)"):
         first = next(f for k, f in build.KERNEL_SOURCES if k in name)          # the FIRST key that matches decides
         assert first == "si.hip", (name, first)
         assert build.kernel_source_digest(name) not in (None, build.kernel_source_digest("vqa::ti_kernel<32, 15, 2>"))

@@ -17,6 +17,14 @@ import numpy as np
 import pytest
 import torch
 
+from tests.pgd_reference import accumulate_np as _accumulate_np
+from tests.pgd_reference import assert_bits as _assert_bits
+from tests.pgd_reference import combine_np as _combine_np
+from tests.pgd_reference import copies_np as _copies_np
+from tests.pgd_reference import place as _place
+from tests.pgd_reference import same_bits as _same_bits
+from tests.pgd_reference import update_np
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 F = np.float32
@@ -29,18 +37,6 @@ FLAT = 256 * 12 * 2048 + 5 * 2048 + 1036          # > grid x the larger tile (2 
 _SHAPES = {"3x3x5x7": (3, 3, 5, 7), "2x3x64x64": (2, 3, 64, 64), "2x4100": (2, 4100), "offset": (2, 4100),
            "one_off": (2, 4100), "flat": (FLAT,), "2x11276": (2, 11276)}
 _cache = {}
-
-
-def _place(a, off):
-    """Host array -> device tensor; ``off``: one float behind a 16-byte boundary."""
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    if not off:
-        return t.to(DEV)
-    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=DEV)
-    view = buf[1:].view(t.shape)
-    view.copy_(t)
-    assert view.data_ptr() % 16 == 4 and view.is_contiguous()
-    return view
 
 
 def _data(name):
@@ -62,54 +58,13 @@ def _data(name):
     return _cache[name]
 
 
+def _update_np(x, ghat, x0, clip=True):
+    return update_np(x, ghat, x0, EPS_ITER, EPS, LO, HI, clip)
+
+
 def _weights(copies):
     from vqattack_amd import ops
     return ops.si_weights(ops.si_scales(copies))
-
-
-def _combine_np(g, w):
-    with np.errstate(all="ignore"):
-        acc = F(w[0]) * g[0]
-        for i in range(1, len(w)):
-            acc = acc + F(w[i]) * g[i]
-    assert acc.dtype == F
-    return acc
-
-
-def _sign(g):
-    return (g > 0).astype(F) - (g < 0).astype(F)      # torch.sign: sign(NaN) = 0
-
-
-def _update_np(x, ghat, x0, clip=True):
-    """numpy fp32: StepOp (x0 given) or FgmOp (x0 None) of csrc/common.hpp."""
-    a = x + F(EPS_ITER) * _sign(ghat)
-    if clip:
-        a = np.clip(a, F(LO), F(HI))
-    if x0 is None:
-        return a
-    out = x0 + np.clip(a - x0, -F(EPS), F(EPS))
-    if clip:
-        out = np.clip(out, F(LO), F(HI))
-    assert out.dtype == F
-    return out
-
-
-def _copies_np(x, s, m=None, lookahead=0.0):
-    base = x if m is None else x + F(lookahead) * m
-    out = np.stack([F(si) * base for si in s])
-    assert out.dtype == F
-    return out
-
-
-def _assert_bits(got, want, what):
-    got = got.detach().cpu().numpy()
-    assert got.shape == want.shape and got.dtype == want.dtype, what
-    same = np.mean(got.view(np.int32) == want.view(np.int32))
-    assert same == 1.0, (what, same)
-
-
-def _same_bits(a, b):
-    return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 # ------------------------------------------------------------------------------------------------ copies
@@ -201,6 +156,21 @@ def test_one_copy_of_weight_one_is_the_identity(name):
                       ops.linf_step(dev["x"], gd, dev["x0"], EPS_ITER, EPS, LO, HI))
     assert _same_bits(ops.linf_si_step(dev["x"], [gd], None, [1.0], EPS_ITER, EPS, LO, HI),
                       ops.linf_fgm(dev["x"], gd, EPS_ITER, LO, HI))
+
+
+@pytest.mark.parametrize("shape", [(3, 3, 5, 7), (2, 4100)], ids=["3x3x5x7", "2x4100"])
+def test_the_unseeded_fold_keeps_minus_zero_and_the_seeded_one_adds_it_to_its_seed(shape):
+    """The one place where the two starts of the shared fold kernel differ: 1 * -0 is -0, +0 + 1 * -0 is +0."""
+    from vqattack_amd import ops
+    g = np.full(shape, -0.0, dtype=F)
+    gd = _place(g, False)
+    combined = ops.si_combine([gd], [1.0])
+    assert np.all(combined.cpu().numpy().view(np.int32) == np.int32(-2 ** 31)), "si_combine: not the bits of -0.0"
+    _assert_bits(combined, _combine_np([g], [1.0]), "si_combine")
+    acc = torch.zeros(shape, dtype=torch.float32, device=DEV)
+    summed = ops.admix_accumulate([gd], [1.0], acc)
+    assert np.all(summed.cpu().numpy().view(np.int32) == 0), "admix_accumulate: not the bits of +0.0"
+    _assert_bits(summed, _accumulate_np(np.zeros(shape, dtype=F), [g], [1.0]), "admix_accumulate")
 
 
 # ------------------------------------------------------------------------------------------------ fused step

@@ -21,6 +21,11 @@ import numpy as np
 import pytest
 import torch
 
+from tests.pgd_reference import assert_bits as _assert_bits
+from tests.pgd_reference import place as _place
+from tests.pgd_reference import same_bits as _same_bits
+from tests.pgd_reference import update_np
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 F = np.float32
@@ -69,18 +74,6 @@ def _neighbors_np(x, seed, t, first, count, bound, m=None, lookahead=0.0, block_
     return out
 
 
-def _place(a, off):
-    """Host array -> device tensor; ``off``: one float behind a 16-byte boundary."""
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    if not off:
-        return t.to(DEV)
-    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=DEV)
-    view = buf[1:].view(t.shape)
-    view.copy_(t)
-    assert view.data_ptr() % 16 == 4 and view.is_contiguous()
-    return view
-
-
 def _data(name):
     """x0 in [-1, 1], x inside its ball, 9 gradients drawn as 1e-3 * N(0, 1) (the last one plays the centre's), a
     normal-draw momentum, a variance of the gradients' size: built once per shape and never changed."""
@@ -99,6 +92,10 @@ def _data(name):
                    g=[_place(a, off or (name == "one_off" and i == 1)) for i, a in enumerate(g)])
         _cache[name] = (host, dev)
     return _cache[name]
+
+
+def _update_np(x, ghat, x0, clip=True):
+    return update_np(x, ghat, x0, EPS_ITER, EPS, LO, HI, clip)
 
 
 def _key(t, seed=SEED):
@@ -120,35 +117,6 @@ def _tune_np(g, vsum, v, w):
     nv = F(w) * vsum - g
     assert ghat.dtype == F and nv.dtype == F
     return ghat, nv
-
-
-def _sign(g):
-    return (g > 0).astype(F) - (g < 0).astype(F)      # torch.sign: sign(NaN) = 0
-
-
-def _update_np(x, ghat, x0, clip=True):
-    """numpy fp32: StepOp (x0 given) or FgmOp (x0 None) of csrc/common.hpp."""
-    a = x + F(EPS_ITER) * _sign(ghat)
-    if clip:
-        a = np.clip(a, F(LO), F(HI))
-    if x0 is None:
-        return a
-    out = x0 + np.clip(a - x0, -F(EPS), F(EPS))
-    if clip:
-        out = np.clip(out, F(LO), F(HI))
-    assert out.dtype == F
-    return out
-
-
-def _assert_bits(got, want, what):
-    got = got.detach().cpu().numpy()
-    assert got.shape == want.shape and got.dtype == want.dtype, what
-    same = np.mean(got.view(np.int32) == want.view(np.int32))
-    assert same == 1.0, (what, same)
-
-
-def _same_bits(a, b):
-    return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 # ------------------------------------------------------------------------------------------------ neighbours

@@ -2,7 +2,7 @@
 
 On gfx950 fp32 MFMA and vector instructions of one SIMD do not overlap (tools/mfma_probe.hip), so every vector
 instruction inside a tile loop is paid in matrix-pipe time; the quarter-rate integer multiplies most of all.  This lists,
-per kernel: registers, occupancy, and for the innermost loop the MFMA count, the other vector instructions and the slow
+per kernel: vector registers, scalar registers (the metadata block's `.sgpr_count`), occupancy, and for the innermost loop the MFMA count, the other vector instructions and the slow
 ones (v_mul_lo / v_mul_hi / v_mad_u64) -- all blocks of the loop, so conditional paths (last tile, key hole, lazy
 rescale) are included.
     python tools/isa_loop_mix.py [file.s] [--src loss.hip] [-v] [--waits] [--innermost]
@@ -54,9 +54,12 @@ def innermost_body(kernel_text):
 
 
 def kernels(path, innermost=False):
-    """Per kernel of an assembly file: (demangled name, {NumVgprs, Occupancy, ScratchSize}, loop body text).
-    ``innermost``: of nested loops only the deepest one's blocks (a tile loop around a k-loop: the k-loop)."""
+    """Per kernel of an assembly file: (demangled name, {NumVgprs, Occupancy, ScratchSize, sgpr_count}, loop body text).
+    ``sgpr_count`` is the metadata block's `.sgpr_count`: what the kernel is granted, VCC and the like included (the
+    "; NumSgprs" comment leaves those out).  ``innermost``: of nested loops only the deepest one's blocks (a tile loop
+    around a k-loop: the k-loop)."""
     text = open(path).read()
+    sgprs = dict(re.findall(r"\n    \.name:\s+(\S+)\n(?:    .*\n)*?    \.sgpr_count:\s+(\d+)", text))
     for k in re.split(r"\n(?=_ZN3vqa[^\n]*:\s+; @)", text):
         name = k.split(":")[0]
         if not name.startswith("_ZN3vqa"):
@@ -64,6 +67,7 @@ def kernels(path, innermost=False):
         demangled = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.split("(")[0].strip()
         demangled = demangled[5:] if demangled.startswith("void ") else demangled
         meta = {key: (re.search(r"; %s: (\d+)" % key, k) or [None, "?"])[1] for key in ("NumVgprs", "Occupancy", "ScratchSize")}
+        meta["sgpr_count"] = sgprs.get(name, "?")
         # basic blocks start at a label or a "; %bb.N:" comment; those of a loop say "Loop Header" / "in Loop:"
         body, inside = [], False
         for line in k.split("\n"):
@@ -104,8 +108,8 @@ def main():
         ins = [l.split()[0] for l in body.split("\n") if l.startswith("\t") and l.split() and not l.strip().startswith(";")]
         valu = [x for x in ins if x.startswith("v_") and not x.startswith("v_mfma")]
         slow = [x for x in valu if x.startswith(("v_mul_lo", "v_mul_hi", "v_mad_u64", "v_mad_i64"))]
-        print("{:<62} vgpr {:>3} occ {} scratch {} | loop: mfma {:>3} valu {:>3} (slow {:>2}) lds {:>3} vmem {:>2}".format(
-            demangled, meta["NumVgprs"], meta["Occupancy"], meta["ScratchSize"],
+        print("{:<62} vgpr {:>3} sgpr {:>3} occ {} scratch {} | loop: mfma {:>3} valu {:>3} (slow {:>2}) lds {:>3} vmem {:>2}".format(
+            demangled, meta["NumVgprs"], meta["sgpr_count"], meta["Occupancy"], meta["ScratchSize"],
             sum(x.startswith("v_mfma") for x in ins), len(valu), len(slow), sum(x.startswith("ds_") for x in ins),
             sum(x.startswith(("global_", "buffer_")) for x in ins)))
         if verbose and body:

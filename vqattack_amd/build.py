@@ -24,13 +24,13 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared"
 # tied to the code that produced them (profiles/*/pmc_traffic.json, bench.py's `traffic` field)
 KERNEL_SOURCES = (("stream4_kernel", "linf.hip"), ("neg_cos_rows", "loss.hip"), ("ce_rows", "ce.hip"), ("ce_count", "ce.hip"),
                   ("attn_", "attn.hip"), ("sumsq", "lnorm.hip"), ("absmax", "lnorm.hip"), ("per_sample", "lnorm.hip"),
-                  ("sum_stage2", "lnorm.hip"), ("sumabs", "lnorm.hip"), ("momentum", "lnorm.hip"), ("ti_kernel", "ti.hip"), ("di_forward", "di.hip"), ("di_adjoint", "di.hip"), ("si_combine", "si.hip"), ("si_copies", "si.hip"), ("admix_copies", "admix.hip"), ("admix_accumulate", "admix.hip"), ("vt_neighbors", "vt.hip"), ("vt_accumulate", "vt.hip"), ("vt_tune", "vt.hip"), ("ln_fwd", "block.hip"), ("ln_bwd", "block.hip"), ("gelu", "block.hip"),
+                  ("sum_stage2", "lnorm.hip"), ("sumabs", "lnorm.hip"), ("momentum", "lnorm.hip"), ("ti_kernel", "ti.hip"), ("di_forward", "di.hip"), ("di_adjoint", "di.hip"), ("grad_fold_vec_kernel<false,", "si.hip"), ("grad_fold_scalar_kernel<false,", "si.hip"), ("si_copies", "si.hip"), ("admix_copies", "admix.hip"), ("grad_fold_vec_kernel<true,", "admix.hip"), ("grad_fold_scalar_kernel<true,", "admix.hip"), ("vt_neighbors", "vt.hip"), ("vt_accumulate", "vt.hip"), ("vt_tune", "vt.hip"), ("ln_fwd", "block.hip"), ("ln_bwd", "block.hip"), ("gelu", "block.hip"),
                   ("resize", "image.hip"), ("gather_rows", "text.hip"), ("cand_dir_sim", "text.hip"),
                   ("embed_tokens", "text.hip"), ("greedy_accept", "text.hip"), ("gemm_", "gemm.hip"))
 
 
 def kernel_source_digest(kernel_name):
-    """sha256 over the source file a kernel is compiled from + the shared headers (``common.hpp``, ``gelu.hpp``, ``stream.hpp``) + the
+    """sha256 over the source file a kernel is compiled from + the shared headers (``common.hpp``, ``gelu.hpp``, ``stream.hpp``, ``fold.hpp``) + the
     C-ABI header + the compiler flags: changes whenever that kernel's code object can have changed.  None for a kernel
     this table does not know."""
     import hashlib
@@ -39,7 +39,7 @@ def kernel_source_digest(kernel_name):
         return None
     h = hashlib.sha256(" ".join(FLAGS).encode())
     for path in (os.path.join(SRC_DIR, src), os.path.join(SRC_DIR, "common.hpp"), os.path.join(SRC_DIR, "gelu.hpp"),
-                 os.path.join(SRC_DIR, "stream.hpp"), os.path.join(HERE, "..", "include", "vqattack_hip.h")):
+                 os.path.join(SRC_DIR, "stream.hpp"), os.path.join(SRC_DIR, "fold.hpp"), os.path.join(HERE, "..", "include", "vqattack_hip.h")):
         with open(path, "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()

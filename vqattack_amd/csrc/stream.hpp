@@ -1,5 +1,6 @@
 // The tile loop of the PGD path's HBM-bound stream kernels (linf.hip, lnorm.hip's momentum step, si.hip, admix.hip,
-// vt.hip), written once, and the small launch rules those files share.
+// vt.hip), written once, and the small launch rules and host-side checks those files share.  fold.hpp, on top of this
+// header, holds the one kernel template that si.hip and admix.hip fold their gradient lists with.
 //
 // Such a kernel has arithmetic intensity < 0.5 flop/B: one 16-byte access per lane and stream, U slots of 256 pieces in
 // flight per wave before the first use, 256-thread workgroups, a grid of 12 workgroups per CU that strides over
@@ -141,6 +142,47 @@ inline int stream_grid(size_t items, int U, int share = 1, int per_cu = kStreamB
 inline bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {   // [a, a + na) meets [b, b + nb)
   const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
   return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// `count` copies of n floats, copy_stride floats apart from `out` on, written in one launch from x, the optional m and the
+// optional small device row `row` (row_bytes long).  VQA_ERR_SHAPE: copies that overlap each other or an input;
+// VQA_ERR_ALIGN: a pointer that is not 4-byte aligned.  `bytes`: from the first copy's start to the last one's end;
+// `vec`: whether the 16-byte kernel applies -- `unit`, the run of floats one workgroup row walks, is whole pieces too.
+// The caller has checked its pointers for null and count >= 1.
+struct CopiesSpan {
+  size_t bytes = 0;
+  bool vec = false;
+};
+inline int check_copies(CopiesSpan& s, const float* x, const float* m, const void* row, size_t row_bytes,
+                        const float* out, size_t n, size_t unit, size_t copy_stride, int count) {
+  if (copy_stride < n) return VQA_ERR_SHAPE;
+  s.bytes = (static_cast<size_t>(count - 1) * copy_stride + n) * sizeof(float);
+  const size_t nb = n * sizeof(float);
+  if (n && (ranges_overlap(x, nb, out, s.bytes) || (m && ranges_overlap(m, nb, out, s.bytes)) ||
+            (row && ranges_overlap(row, row_bytes, out, s.bytes))))
+    return VQA_ERR_SHAPE;
+  if (!aligned4(x) || !aligned4(out) || (m && !aligned4(m)) || !aligned4(row)) return VQA_ERR_ALIGN;
+  s.vec = (unit % 4 == 0) && (copy_stride % 4 == 0) && aligned16(x) && aligned16(out) && (!m || aligned16(m));
+  return VQA_OK;
+}
+
+// The host's list of `count` read streams of nb bytes as a by-value array of MAX: entries past count repeat the first
+// (no instance reads them, and none is wild).  VQA_ERR_SHAPE: a count outside 1..MAX or a stream that meets `result`;
+// VQA_ERR_NULL: a missing stream.  `low` collects the low address bits of the streams for the caller, which reports
+// alignment behind overlap checks of its own: (low & 3) != 0 is VQA_ERR_ALIGN, (low & 15) != 0 the scalar path.
+template <int MAX>
+inline int pack_streams(const float* (&g)[MAX], uintptr_t& low, const float* const* host, int count, const void* result,
+                        size_t nb) {
+  if (count < 1 || count > MAX) return VQA_ERR_SHAPE;
+  for (int c = 0; c < count; ++c)
+    if (!host[c]) return VQA_ERR_NULL;
+  for (int c = 0; c < count; ++c)
+    if (nb && ranges_overlap(host[c], nb, result, nb)) return VQA_ERR_SHAPE;
+  for (int c = 0; c < MAX; ++c) {
+    g[c] = c < count ? host[c] : host[0];
+    low |= reinterpret_cast<uintptr_t>(g[c]);
+  }
+  return VQA_OK;
 }
 
 // f(std::integral_constant<int, C>) with C = count clamped to 1..MAX: one kernel instance per count.

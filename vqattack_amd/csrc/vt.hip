@@ -319,22 +319,17 @@ int vqa_vt_neighbors(const float* x, const float* m, float* out, size_t n, size_
                      vqa_stream_t stream) {
   clear_stale_error();
   if (!x || !out || !key_dev) return VQA_ERR_NULL;
-  if (count < 1 || count > kVtMax || first < 0 || copy_stride < n) return VQA_ERR_SHAPE;
-  const size_t span = (static_cast<size_t>(count - 1) * copy_stride + n) * sizeof(float);
-  const size_t nb = n * sizeof(float);
-  if (n && (ranges_overlap(x, nb, out, span) || (m && ranges_overlap(m, nb, out, span)) ||
-            ranges_overlap(key_dev, 3 * sizeof(unsigned), out, span)))
-    return VQA_ERR_SHAPE;
-  if (!aligned4(x) || !aligned4(out) || (m && !aligned4(m)) || !aligned4(key_dev)) return VQA_ERR_ALIGN;
+  if (count < 1 || count > kVtMax || first < 0) return VQA_ERR_SHAPE;
+  CopiesSpan span;
+  if (const int err = check_copies(span, x, m, key_dev, 3 * sizeof(unsigned), out, n, n, copy_stride, count)) return err;
   if (n == 0) return VQA_OK;
-  const bool vec = (n % 4 == 0) && (copy_stride % 4 == 0) && aligned16(x) && aligned16(out) && (!m || aligned16(m));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const uint32_t f = static_cast<uint32_t>(first);
   const uint64_t off = static_cast<uint64_t>(block_offset);
   dispatch_count<kVtMax>(count, [&](auto c) {
     constexpr int C = decltype(c)::value;
-    if (m) launch_vt_neighbors_c<C, true>(vec, span, st, x, m, out, n, copy_stride, f, off, bound, lookahead, key_dev);
-    else launch_vt_neighbors_c<C, false>(vec, span, st, x, nullptr, out, n, copy_stride, f, off, bound, lookahead, key_dev);
+    if (m) launch_vt_neighbors_c<C, true>(span.vec, span.bytes, st, x, m, out, n, copy_stride, f, off, bound, lookahead, key_dev);
+    else launch_vt_neighbors_c<C, false>(span.vec, span.bytes, st, x, nullptr, out, n, copy_stride, f, off, bound, lookahead, key_dev);
   });
   return launch_status();
 }
@@ -342,21 +337,12 @@ int vqa_vt_neighbors(const float* x, const float* m, float* out, size_t n, size_
 int vqa_vt_accumulate(const float* const* grads_host, int count, float* sum, size_t n, int init, vqa_stream_t stream) {
   clear_stale_error();
   if (!grads_host || !sum) return VQA_ERR_NULL;
-  if (count < 1 || count > kVtMax) return VQA_ERR_SHAPE;
-  for (int c = 0; c < count; ++c)
-    if (!grads_host[c]) return VQA_ERR_NULL;
-  const size_t nb = n * sizeof(float);
-  for (int c = 0; c < count; ++c)
-    if (n && ranges_overlap(grads_host[c], nb, sum, nb)) return VQA_ERR_SHAPE;          // sum may alias no gradient
-  if (!aligned4(sum)) return VQA_ERR_ALIGN;
-  bool vec = (n % 4 == 0) && aligned16(sum);
   VtGrads a;
-  for (int c = 0; c < kVtMax; ++c) {
-    a.g[c] = c < count ? grads_host[c] : grads_host[0];
-    if (!aligned4(a.g[c])) return VQA_ERR_ALIGN;
-    vec = vec && aligned16(a.g[c]);
-  }
+  uintptr_t low = reinterpret_cast<uintptr_t>(sum);
+  if (const int err = pack_streams(a.g, low, grads_host, count, sum, n * sizeof(float))) return err;   // sum may alias no gradient
+  if (low & 3u) return VQA_ERR_ALIGN;
   if (n == 0) return VQA_OK;
+  const bool vec = (n % 4 == 0) && (low & 15u) == 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
   dispatch_count<kVtMax>(count, [&](auto c) {
     constexpr int C = decltype(c)::value;

@@ -31,6 +31,14 @@ def _clip_args(clip_min, clip_max):
     return VQA_CLIP, (-_INF if clip_min is None else float(clip_min)), (_INF if clip_max is None else float(clip_max))
 
 
+def _clip_mode(clip_min, clip_max, flag, check_range=True):
+    """``_clip_args``; with a ``flag`` and a clip range the mode also asks for the range check (unless switched off)."""
+    mode, lo, hi = _clip_args(clip_min, clip_max)
+    if flag is not None and mode and check_range:
+        mode |= VQA_CHECK_RANGE
+    return mode, lo, hi
+
+
 def _out_like(x, out):
     if out is None:
         return torch.empty_like(x, memory_format=torch.contiguous_format)
@@ -38,6 +46,46 @@ def _out_like(x, out):
     if out.shape != x.shape:
         raise ValueError("out has shape {}, expected {}".format(tuple(out.shape), tuple(x.shape)))
     return out
+
+
+def _momentum_like(x, m):
+    """The optional momentum of a copies kernel: checked against ``x``."""
+    if m is not None:
+        dev_f32(m, "momentum")
+        if m.shape != x.shape:
+            raise ValueError("momentum shape {} != x shape {}".format(tuple(m.shape), tuple(x.shape)))
+
+
+def _copies_out(x, count, out, what):
+    """``(out, stride)`` of a copies kernel: the ``(count,) + x.shape`` result, allocated or the caller's -- every
+    ``out[i]`` contiguous, the copies possibly further apart than ``x.numel()`` -- and the distance between two copies
+    in elements.  ``what``: the message's words for one copy and for all of them, ``("out[i]", "copies")``."""
+    shape = (count,) + tuple(x.shape)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        dev_f32(out, "out", contiguous=False)
+        if tuple(out.shape) != shape:
+            raise ValueError("out has shape {}, expected {}".format(tuple(out.shape), shape))
+        if not out[0].is_contiguous() or (count > 1 and out.stride(0) < x.numel()):
+            raise ValueError("every {} must be contiguous and the {} must not overlap".format(*what))
+    return out, (out.stride(0) if count > 1 else x.numel())
+
+
+def _grad_ptrs(grads, limit, like=None):
+    """The ctypes pointer array of a list of 1..``limit`` gradient tensors of one shape: that of ``like``, the running
+    ``sum`` they are added to (checked here), or their first's."""
+    if isinstance(grads, torch.Tensor) or not isinstance(grads, (list, tuple)):
+        raise TypeError("grads must be a list or tuple of tensors{}, got {}".format(
+            "" if like is not None else " (autograd hands back one per copy)", type(grads)))
+    if len(grads) < 1 or len(grads) > limit:
+        raise ValueError("grads must hold 1..{} tensors, got {}".format(limit, len(grads)))
+    ref, name = (grads[0], "grads[0]") if like is None else (dev_f32(like, "sum"), "sum")
+    for i, g in enumerate(grads):
+        dev_f32(g, "grads[{}]".format(i))
+        if g.shape != ref.shape:
+            raise ValueError("grads[{}] has shape {}, {} {}".format(i, tuple(g.shape), name, tuple(ref.shape)))
+    return (ctypes.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
 
 
 def _fused_step_args(x, g, x0, clip_min, clip_max, flag, out, also=(), what="grad"):
@@ -52,9 +100,7 @@ def _fused_step_args(x, g, x0, clip_min, clip_max, flag, out, also=(), what="gra
             tuple(x.shape), what, tuple(g.shape), None if x0 is None else tuple(x0.shape)))
     same_device(x, g, x0, out, flag, *also)
     out = _out_like(x, out)
-    mode, lo, hi = _clip_args(clip_min, clip_max)
-    if flag is not None and mode:
-        mode |= VQA_CHECK_RANGE
+    mode, lo, hi = _clip_mode(clip_min, clip_max, flag)
     return out, mode, lo, hi
 
 
@@ -72,9 +118,7 @@ def linf_init(x, eta, eps, clip_min, clip_max, flag=None, out=None):
             raise ValueError("eta shape {} != x shape {}".format(tuple(eta.shape), tuple(x.shape)))
     same_device(x, eta, out, flag)
     out = _out_like(x, out)
-    mode, lo, hi = _clip_args(clip_min, clip_max)
-    if flag is not None and mode:
-        mode |= VQA_CHECK_RANGE
+    mode, lo, hi = _clip_mode(clip_min, clip_max, flag)
     if x.numel() == 0:
         return out
     with _on(x):
@@ -89,9 +133,7 @@ def linf_fgm(x, g, eps_iter, clip_min, clip_max, flag=None, out=None):
         raise ValueError("grad shape {} != x shape {}".format(tuple(g.shape), tuple(x.shape)))
     same_device(x, g, out, flag)
     out = _out_like(x, out)
-    mode, lo, hi = _clip_args(clip_min, clip_max)
-    if flag is not None and mode:
-        mode |= VQA_CHECK_RANGE
+    mode, lo, hi = _clip_mode(clip_min, clip_max, flag)
     if x.numel() == 0:
         return out
     with _on(x):
@@ -108,9 +150,7 @@ def linf_step(x, g, x0, eps_iter, eps, clip_min, clip_max, flag=None, out=None):
                                                                           tuple(x0.shape)))
     same_device(x, g, x0, out, flag)
     out = _out_like(x, out)
-    mode, lo, hi = _clip_args(clip_min, clip_max)
-    if flag is not None and mode:
-        mode |= VQA_CHECK_RANGE
+    mode, lo, hi = _clip_mode(clip_min, clip_max, flag)
     if x.numel() == 0:
         return out
     with _on(x):
@@ -228,9 +268,7 @@ def l2_fgm(x, g, eps_iter, clip_min, clip_max, flag=None, out=None, check_range=
     ss = sumsq_per_sample(g)
     out = _out_like(x, out)
     batch, n_per = _per_sample(x)
-    mode, lo, hi = _clip_args(clip_min, clip_max)
-    if flag is not None and mode and check_range:
-        mode |= VQA_CHECK_RANGE
+    mode, lo, hi = _clip_mode(clip_min, clip_max, flag, check_range)
     if x.numel() == 0:
         return out
     with _on(x):
@@ -263,9 +301,7 @@ def l1_fgm(x, g, eps_iter, clip_min, clip_max, flag=None, out=None, check_range=
     amax, ties = absmax_ties_per_sample(g)
     out = _out_like(x, out)
     batch, n_per = _per_sample(x)
-    mode, lo, hi = _clip_args(clip_min, clip_max)
-    if flag is not None and mode and check_range:
-        mode |= VQA_CHECK_RANGE
+    mode, lo, hi = _clip_mode(clip_min, clip_max, flag, check_range)
     if x.numel() == 0:
         return out
     with _on(x):
@@ -550,23 +586,11 @@ def si_copies(x, scales, m=None, lookahead=0.0, out=None):
     contiguous, and the copies may lie further apart than ``x.numel()`` (the batch prefix of a larger buffer)."""
     s, buf = _si_host(scales, "scales")
     dev_f32(x, "x")
-    if m is not None:
-        dev_f32(m, "momentum")
-        if m.shape != x.shape:
-            raise ValueError("momentum shape {} != x shape {}".format(tuple(m.shape), tuple(x.shape)))
-    shape = (int(s.size),) + tuple(x.shape)
+    _momentum_like(x, m)
     same_device(x, m, out)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    else:
-        dev_f32(out, "out", contiguous=False)
-        if tuple(out.shape) != shape:
-            raise ValueError("out has shape {}, expected {}".format(tuple(out.shape), shape))
-        if not out[0].is_contiguous() or (s.size > 1 and out.stride(0) < x.numel()):
-            raise ValueError("every out[i] must be contiguous and the copies must not overlap")
+    out, stride = _copies_out(x, int(s.size), out, ("out[i]", "copies"))
     if x.numel() == 0:
         return out
-    stride = out.stride(0) if s.size > 1 else x.numel()
     with _on(x):
         check(lib().vqa_si_copies(ptr(x), ptr(m), ptr(out), x.numel(), stride, buf, int(s.size), float(lookahead),
                                   stream_for(x)), "vqa_si_copies")
@@ -575,20 +599,12 @@ def si_copies(x, scales, m=None, lookahead=0.0, out=None):
 
 def _si_grads(grads, weights):
     """(ctypes pointer array, ctypes float array, copies) of a list of same-shape gradient tensors and their weights."""
-    if isinstance(grads, torch.Tensor) or not isinstance(grads, (list, tuple)):
-        raise TypeError("grads must be a list or tuple of tensors (autograd hands back one per copy), got {}".format(
-            type(grads)))
-    if len(grads) < 1 or len(grads) > SI_MAX_COPIES:
-        raise ValueError("grads must hold 1..{} tensors, got {}".format(SI_MAX_COPIES, len(grads)))
-    for i, g in enumerate(grads):
-        dev_f32(g, "grads[{}]".format(i))
-        if g.shape != grads[0].shape:
-            raise ValueError("grads[{}] has shape {}, grads[0] {}".format(i, tuple(g.shape), tuple(grads[0].shape)))
+    pbuf = _grad_ptrs(grads, SI_MAX_COPIES)
     w, wbuf = _si_host(weights, "weights")
     if w.size != len(grads):
         raise ValueError("{} weights for {} gradients".format(w.size, len(grads)))
     same_device(*grads)
-    return (ctypes.c_void_p * len(grads))(*[g.data_ptr() for g in grads]), wbuf, len(grads)
+    return pbuf, wbuf, len(grads)
 
 
 def si_combine(grads, weights, out=None):
@@ -696,25 +712,13 @@ def admix_copies(x, partner_row, scales, eta, m=None, lookahead=0.0, out=None):
     dev_f32(x, "x")
     if x.dim() < 1:
         raise ValueError("x must have a batch axis")
-    if m is not None:
-        dev_f32(m, "momentum")
-        if m.shape != x.shape:
-            raise ValueError("momentum shape {} != x shape {}".format(tuple(m.shape), tuple(x.shape)))
+    _momentum_like(x, m)
     batch = x.shape[0]
     _admix_row(partner_row, batch)
-    shape = (int(s.size),) + tuple(x.shape)
     same_device(x, m, out, partner_row)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    else:
-        dev_f32(out, "out", contiguous=False)
-        if tuple(out.shape) != shape:
-            raise ValueError("out has shape {}, expected {}".format(tuple(out.shape), shape))
-        if not out[0].is_contiguous() or (s.size > 1 and out.stride(0) < x.numel()):
-            raise ValueError("every out[i] must be contiguous and the copies must not overlap")
+    out, stride = _copies_out(x, int(s.size), out, ("out[i]", "copies"))
     if x.numel() == 0:
         return out
-    stride = out.stride(0) if s.size > 1 else x.numel()
     with _on(x):
         check(lib().vqa_admix_copies(ptr(x), ptr(m), ctypes.c_void_p(partner_row.data_ptr()), ptr(out), batch,
                                      x.numel() // batch, stride, buf, int(s.size), float(eta), float(lookahead),
@@ -722,13 +726,17 @@ def admix_copies(x, partner_row, scales, eta, m=None, lookahead=0.0, out=None):
     return out
 
 
+def _acc_like(acc, g0):
+    dev_f32(acc, "acc")
+    if acc.shape != g0.shape:
+        raise ValueError("acc has shape {}, grads[0] {}".format(tuple(acc.shape), tuple(g0.shape)))
+
+
 def admix_accumulate(grads, weights, acc):
     """``acc = (...((acc + w_0 * g_0) + w_1 * g_1) + ...)`` exactly in place (ascending, one rounding per operation): the
     running sum of a mixed group after the first, which ``si_combine`` starts.  ``acc`` may alias no gradient."""
     pbuf, wbuf, copies = _si_grads(grads, weights)
-    dev_f32(acc, "acc")
-    if acc.shape != grads[0].shape:
-        raise ValueError("acc has shape {}, grads[0] {}".format(tuple(acc.shape), tuple(grads[0].shape)))
+    _acc_like(acc, grads[0])
     same_device(grads[0], acc)
     if acc.numel() == 0:
         return acc
@@ -742,9 +750,7 @@ def linf_admix_step(x, acc, grads, x0, weights, eps_iter, eps, clip_min, clip_ma
     """``admix_accumulate`` and ``linf_step`` on its result in one pass, 4 * copies + 16 B/element; ``x0=None``: and
     ``linf_fgm`` (no projection).  Neither the sum nor ``acc`` is written; ``out`` may be ``x``."""
     pbuf, wbuf, copies = _si_grads(grads, weights)
-    dev_f32(acc, "acc")
-    if acc.shape != grads[0].shape:
-        raise ValueError("acc has shape {}, grads[0] {}".format(tuple(acc.shape), tuple(grads[0].shape)))
+    _acc_like(acc, grads[0])
     out, mode, lo, hi = _fused_step_args(x, grads[0], x0, clip_min, clip_max, flag, out, also=(acc,), what="grads")
     if x.numel() == 0:
         return out
@@ -801,23 +807,11 @@ def vt_neighbors(x, key, count, bound, first=0, m=None, lookahead=0.0, block_off
         raise ValueError("block_offset must be in [0, 2^64), got {}".format(block_offset))
     dev_f32(x, "x")
     _vt_key(key)
-    if m is not None:
-        dev_f32(m, "momentum")
-        if m.shape != x.shape:
-            raise ValueError("momentum shape {} != x shape {}".format(tuple(m.shape), tuple(x.shape)))
-    shape = (count,) + tuple(x.shape)
+    _momentum_like(x, m)
     same_device(x, m, out, key)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    else:
-        dev_f32(out, "out", contiguous=False)
-        if tuple(out.shape) != shape:
-            raise ValueError("out has shape {}, expected {}".format(tuple(out.shape), shape))
-        if not out[0].is_contiguous() or (count > 1 and out.stride(0) < x.numel()):
-            raise ValueError("every out[c] must be contiguous and the neighbours must not overlap")
+    out, stride = _copies_out(x, count, out, ("out[c]", "neighbours"))
     if x.numel() == 0:
         return out
-    stride = out.stride(0) if count > 1 else x.numel()
     with _on(x):
         check(lib().vqa_vt_neighbors(ptr(x), ptr(m), ptr(out), x.numel(), stride, count, first, block_offset,
                                      float(bound), float(lookahead), ctypes.c_void_p(key.data_ptr()), stream_for(x)),
@@ -828,19 +822,10 @@ def vt_neighbors(x, key, count, bound, first=0, m=None, lookahead=0.0, block_off
 def vt_accumulate(grads, sum, init):
     """``sum = (g_0 if init else sum + g_0) + g_1 + ...`` in place (ascending, one rounding per addition): 1..VT_MAX_CHUNK
     gradients per launch; grouping them differently gives the same bits.  ``sum`` may alias no gradient."""
-    if isinstance(grads, torch.Tensor) or not isinstance(grads, (list, tuple)):
-        raise TypeError("grads must be a list or tuple of tensors, got {}".format(type(grads)))
-    if len(grads) < 1 or len(grads) > VT_MAX_CHUNK:
-        raise ValueError("grads must hold 1..{} tensors, got {}".format(VT_MAX_CHUNK, len(grads)))
-    dev_f32(sum, "sum")
-    for i, g in enumerate(grads):
-        dev_f32(g, "grads[{}]".format(i))
-        if g.shape != sum.shape:
-            raise ValueError("grads[{}] has shape {}, sum {}".format(i, tuple(g.shape), tuple(sum.shape)))
+    pbuf = _grad_ptrs(grads, VT_MAX_CHUNK, like=sum)
     same_device(sum, *grads)
     if sum.numel() == 0:
         return sum
-    pbuf = (ctypes.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
     with _on(sum):
         check(lib().vqa_vt_accumulate(pbuf, len(grads), ptr(sum), sum.numel(), 1 if init else 0, stream_for(sum)),
               "vqa_vt_accumulate")
